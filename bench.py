@@ -9,11 +9,18 @@ bags (BASELINE.json metric, configs[1]: 8 bags x 256 tiles per GPU, bf16 operand
 One step = zero the flat gradient bucket, re-pack the filters (they changed), one encoder pass over every tile of
 this rank's bags (full-bag path: all tiles through the backbone, gradients enabled), the segmented MIL head, the
 full backward, — for N>1 — one RCCL all-reduce (sum) of the flat gradient bucket, and one fused Adam step.  Weak
-scaling: every rank owns 8 bags.  Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`,
-`cpu_baseline` and — at N=1 — three sub-records timed by the same command: `bf16x3_path` (fp32 tensors, split-precision
-products: the fast path that meets the north star's 1e-3 gate on the logits, with its own roofline), `fp32_path` (the
-exact-f32 MFMA kernels, bit-level parity) and `alt_resnet_path` (the 64-512-channel encoder of alt_resnet.py, the
-MFMA-bound datapoint).
+scaling: every rank owns 8 bags.  Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the line.  `--full` adds
+everything else the benchmark measures: `roofline` (HIP events around the layer-1 launches, the stream-copy calibration,
+in-run rocprofv3 traffic passes), `cpu_baseline`, for N>1 the replica self-check and the collective's own time
+(`allreduce_ms`), and — at N=1 — four sub-records timed by the same command: `s2d_feed_path`, `bf16x3_path` (fp32 tensors,
+split-precision products: the fast path that meets the north star's 1e-3 gate on the logits, with its own roofline),
+`fp32_path` (the exact-f32 MFMA kernels, bit-level parity) and `alt_resnet_path` (the 64-512-channel encoder of
+alt_resnet.py, the MFMA-bound datapoint).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as float32 .npy files (see dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Other workloads (their own labels, never the headline metric's):
     --size 512 --tiles 128        BASELINE configs[2]
@@ -62,7 +69,39 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true", help="(default now) weight-gradient launches on the main stream")
     ap.add_argument("--infer", action="store_true",
                     help="BASELINE config 5 instead of the headline metric: forward only, no_grad (attention-map extraction)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, sub-records of the other paths, "
+                         "CPU baseline, multi-rank self-check and collective time (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outs, flat, train):
+    """What the timed path handed its caller in its last step, as float32 .npy files under out_dir: every tensor of the
+    per-bag output dicts stacked over this rank's bags (`<key>.npy`, leading axis = bag), and for a training step the
+    gradient bucket after the all-reduce (`grad_flat.npy`) and the parameters after the Adam update (`params_flat.npy`).
+    8 bags x 256 tiles: about 6 MB in all."""
+    arrays = {}
+    for k in outs[0]:
+        vals = [o[k] for o in outs]
+        if all(torch.is_tensor(v) for v in vals):
+            arrays[k] = torch.stack([v.detach().float() for v in vals]).cpu().numpy()
+    if train:
+        arrays["grad_flat"] = flat.flat_grad.detach().float().cpu().numpy()
+        arrays["params_flat"] = flat.flat.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def cpu_baseline(size, weights_npz):
@@ -611,15 +650,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # calibration: what a plain device copy reaches on this box (read + write bytes / time), outside the timed region.
-    # Every rank runs it, for about half a second: it doubles as the clock ramp of a freshly started box (three warm-up
-    # steps are 35 ms of GPU work, far less than the power-state transition).  The W warm-up steps follow directly.
+    # --full: calibration of the roofline, what a plain device copy reaches on this box (read + write bytes / time),
+    # outside the timed region.  Every rank runs it, for about half a second.  The W warm-up steps follow directly.
     copy_gbps = None
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         copy_gbps = stream_copy_gbps(dev)
     for i in range(args.warmup):
         step()
-        if i == 0 and world > 1 and not args.infer:
+        if i == 0 and world > 1 and not args.infer and args.full:
             # self-check of the data-parallel step: after one all-reduce + Adam step every rank must hold bit-identical
             # parameters (same summed gradient, same update), or the replicas have diverged
             lo_, hi_ = flat.flat.clone(), flat.flat.clone()
@@ -630,11 +668,11 @@ def main():
     # Every launch of the layer-1 kernel families (see roofline_record) is bracketed with HIP events on the launch
     # stream; the one with the largest total time in the timed region is reported as `roofline`.
     timer = None
-    if not args.no_kernel_timer and not args.infer:
+    if args.full and not args.no_kernel_timer and not args.infer:
         timer = ops.KernelTimer(timer_wants)
         ops.TIMER = timer
     fence()
-    if world > 1 and not args.infer:
+    if world > 1 and not args.infer and args.full:
         comm_events = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -657,6 +695,8 @@ def main():
     loss_val = float(torch.stack([o["loss"].detach() for o in outs]).mean())
     if not np.isfinite(loss_val):
         raise SystemExit("non-finite loss in benchmark step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs, flat, train=not args.infer)
 
     if rank == 0:
         tiles_per_step = args.tiles if tile_parallel else n_tiles * world
@@ -692,7 +732,7 @@ def main():
             line["step_ms_no_comm"] = elapsed / args.steps * 1e3 - allreduce_ms
         if args.infer:
             line["model_tflops"] = achieved_model_tflops
-        extra = world == 1 and not args.infer and not args.no_extra_paths
+        extra = args.full and world == 1 and not args.infer and not args.no_extra_paths
         if extra and args.dtype == "bf16":
             line["s2d_feed_path"] = path_record(args, "s2d", w, x_all, sizes, labels, dev, copy_gbps)
             line["bf16x3_path"] = path_record(args, "bf16x3", w, x_all, sizes, labels, dev, copy_gbps)
@@ -705,13 +745,13 @@ def main():
         elif "bf16x3_path" in line and line["bf16x3_path"]:
             line["value_within_tolerance"], line["tolerance_dtype"] = line["bf16x3_path"].get("value"), "bf16x3"
         else:
-            line["value_within_tolerance"], line["tolerance_dtype"] = None, "bf16x3 (sub-record skipped in this run)"
+            line["value_within_tolerance"], line["tolerance_dtype"] = None, "bf16x3 (sub-record skipped in this run; it needs --full)"
         line["tolerance"] = "Mterm / Aterm / y_pred / loss within 1e-3 abs of the fp32 CPU reference (tests/test_gpu_configs.py)"
         del x_all
         torch.cuda.empty_cache()
         if extra:
             line["alt_resnet_path"] = alt_resnet_record(dev)
-        if world == 1 and not args.no_cpu_baseline and not args.infer:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.infer:
             line["cpu_baseline"] = cpu_baseline(args.size, w)
         print(json.dumps(line))
     if world > 1:

@@ -354,3 +354,29 @@ def test_bench_roofline_accounting():
             assert isinstance(name, str) and len(keys) >= 1
     assert "fused16x3" in bench._family_kernel("bwd_fused", "bf16x3")[0] and "fused16_kernel" in bench._family_kernel("bwd_fused", "bf16")[0]
     assert "x3" in bench._family_kernel("block_fwd", "bf16x3")[0] and "x3" not in bench._family_kernel("block_fwd", "bf16")[0]
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs: every tensor of the per-bag output dicts stacked over the bags, the gradient bucket and the
+    parameters, all float32, and nothing written past the 64 MB limit."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    flat = types.SimpleNamespace(flat=torch.randn(100), flat_grad=torch.randn(100))
+    outs = [{"Aterm": torch.rand(3, 5), "Fterm": torch.randn(5, 80, dtype=torch.bfloat16),
+             "loss": torch.tensor(float(b), requires_grad=True) * 2, "y_pred_hat": torch.tensor(b), "name": "not an array"}
+            for b in range(4)]
+    bench.dump_outputs(str(tmp_path / "train"), outs, flat, train=True)
+    got = {f[:-4]: np.load(tmp_path / "train" / f) for f in os.listdir(tmp_path / "train")}
+    assert sorted(got) == ["Aterm", "Fterm", "grad_flat", "loss", "params_flat", "y_pred_hat"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["Aterm"].shape == (4, 3, 5) and got["Fterm"].shape == (4, 5, 80)
+    assert np.array_equal(got["loss"], [0, 2, 4, 6]) and np.array_equal(got["grad_flat"], flat.flat_grad.numpy())
+    bench.dump_outputs(str(tmp_path / "infer"), outs, flat, train=False)
+    assert "grad_flat" not in {f[:-4] for f in os.listdir(tmp_path / "infer")}
+    big = [{"Fterm": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)}]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), big, flat, train=False)
+    assert not (tmp_path / "big").exists()

@@ -52,19 +52,19 @@ python3 profiles/summarise_sq_counters.py $OUT/alt_sq1 $OUT/alt_sq2 profiles/sq_
 cp profiles/sq_counters_alt.json profiles/${ROUND}_sq_counters_alt.json
 echo "alt_resnet stats + SQ counters done"
 # the bench lines last: their roofline.traffic / sq_counters fields read the PMC summaries written just above
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
 tail -n 1 $OUT/bench_line.json > profiles/${ROUND}_bench_line.json
 echo "bench done"
 # the other single-GPU configurations of BASELINE.json (512x512 tiles; one 4096-tile bag, forward only)
-python3 bench.py --size 512 --tiles 128 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_cfg3_512.json
-python3 bench.py --infer --bags 1 --tiles 4096 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_cfg5_infer4096.json
+python3 bench.py --full --size 512 --tiles 128 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_cfg3_512.json
+python3 bench.py --full --infer --bags 1 --tiles 4096 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_cfg5_infer4096.json
 # the split-precision path at the other single-GPU configurations
-python3 bench.py --dtype bf16x3 --size 512 --tiles 128 --steps 5 --warmup 2 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_cfg3_512.json
-python3 bench.py --dtype bf16x3 --infer --bags 1 --tiles 4096 --steps 5 --warmup 2 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_cfg5_infer4096.json
+python3 bench.py --full --dtype bf16x3 --size 512 --tiles 128 --steps 5 --warmup 2 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_cfg3_512.json
+python3 bench.py --full --dtype bf16x3 --infer --bags 1 --tiles 4096 --steps 5 --warmup 2 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_cfg5_infer4096.json
 echo "cfg3 / cfg5 lines done"
 # the live driver's size (gbm/classify_combined.py:412: 300x300 tiles; no BASELINE config): 8 bags x 200 tiles, both compute modes
-python3 bench.py --size 300 --tiles 200 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_live300.json
-python3 bench.py --dtype bf16x3 --size 300 --tiles 200 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_live300.json
+python3 bench.py --full --size 300 --tiles 200 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_live300.json
+python3 bench.py --full --dtype bf16x3 --size 300 --tiles 200 --steps 10 --warmup 3 --no-cpu-baseline --no-extra-paths --no-traffic-pass 2>> $OUT/bench.err | tail -n 1 > profiles/${ROUND}_bench_line_bf16x3_live300.json
 echo "live-driver-size lines done"
 
 echo "all profiles written"
