@@ -15,12 +15,8 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 // against the constant pair (-1, 0) / (0, -1) computes it straight from the PACKED hi pair: one conversion, two dot
 // instructions and one conversion per two values (the plain form unpacks hi first: 13 vector instructions per four values
 // against 8).  Every commit and every split epilogue of the MIL_DT_F32S kernels goes through these two.
-#ifndef MIL_SPLIT_DOT2
-#define MIL_SPLIT_DOT2 1
-#endif
 __device__ __forceinline__ void mil_split2(float v0, float v1, bf16x2_t& hi, bf16x2_t& lo) {
     hi[0] = (__bf16)v0; hi[1] = (__bf16)v1;
-#if MIL_SPLIT_DOT2
     // The constant pairs go through an opaque SGPR: written as literals, hipcc (ROCm 7.2) folds {-1, 0} into the INLINE constant
     // -1.0, which v_dot2c_f32_bf16 reads as 0xBF800000 = {0, -1} — the wrong operand, no diagnostic (tools/dev/split_probe.hip:
     // every second value wrong as literals, 0 differences in 4 M values incl. zeros, denormals and 3e38 this way).
@@ -30,9 +26,6 @@ __device__ __forceinline__ void mil_split2(float v0, float v1, bf16x2_t& hi, bf1
     const bf16x2_t m0 = __builtin_bit_cast(bf16x2_t, c0), m1 = __builtin_bit_cast(bf16x2_t, c1);
     lo[0] = (__bf16)__builtin_amdgcn_fdot2_f32_bf16(hi, m0, v0, false);
     lo[1] = (__bf16)__builtin_amdgcn_fdot2_f32_bf16(hi, m1, v1, false);
-#else
-    lo[0] = (__bf16)(v0 - (float)hi[0]); lo[1] = (__bf16)(v1 - (float)hi[1]);
-#endif
 }
 __device__ __forceinline__ void mil_split4(const f32x4_t& v, bf16x4_t& hi, bf16x4_t& lo) {
     bf16x2_t h0, l0, h1, l1;
@@ -227,21 +220,11 @@ __device__ __forceinline__ void mil_poison_lds(void* base) {
 #define MIL_POISON(base) ((void)0)
 #endif
 
-// A/B switches of the development builds.  The shipped library reads NO ambient environment for kernel selection: the
-// switches exist only in `make VARIANT=<name> EXTRA=-DMIL_AB_SWITCHES` builds (tools/README.md).  (Five TEST knobs stay in
-// every build, because the -m gpu tests drive small inputs through the large-launch paths with them: MIL_PF_MIN_TILES,
-// MIL_BUFFER_LIMIT_BYTES, MIL_RES_GRID_CAP, MIL_BLOCK_STRIP and MIL_STEM_WALK (0 / 1: the tiled / the row-walk form of the
-// identity-block forward / of the fused stem forward whatever the launch size); and MIL_LIB_PATH on the Python side selects
-// which build is loaded.)
+// The only environment the library reads: five TEST knobs that drive small inputs through the large-launch paths, read on
+// every call so that a test can set them in the middle of a process (MIL_PF_MIN_TILES, MIL_BUFFER_LIMIT_BYTES,
+// MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK; see include/mil_hip.h).
 #include <cstdlib>
-__host__ inline const char* mil_ab_env(const char* name) {
-#ifdef MIL_AB_SWITCHES
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
+__host__ inline const char* mil_test_knob(const char* name) { return getenv(name); }
 
 // "Has this been done on the CURRENT device yet?" for per-device one-time set-up (hipFuncSetAttribute is a per-device
 // setting: a process-wide flag would leave a second GPU at the 64 KB default).  `done` is one bit per device ordinal;

@@ -13,9 +13,7 @@
 #include "pf_common.cuh"
 #include <cstdlib>
 
-#ifndef MIL_BLOCK_LOOKAHEAD
-#define MIL_BLOCK_LOOKAHEAD 2      // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs; 0 = compiler order
-#endif
+constexpr int MIL_BLOCK_LOOKAHEAD = 2;      // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs
 
 struct BlockFwdArgs {
     const __bf16* x;        // [n,H,W,CP]
@@ -30,9 +28,9 @@ struct BlockFwdArgs {
     float slope;
 };
 
-// NW waves per workgroup (4 or 8).  With 8 waves every per-wave quantity halves (3 + 2 row tiles of accumulators, 3 halo
-// pieces in flight), the kernel fits 128 VGPRs and a CU holds 16 waves instead of 8 on the same LDS tiles and filters:
-// kept as an experiment (MIL_BLOCK_WAVES=8): it measured no faster, see mil_block_waves().
+// NW waves per workgroup: 4.  Measured on the 64x64x24 maps: 434 us with 4 waves per workgroup, 446 us with 8 (16 resident
+// waves per CU at 127 VGPRs) — more resident waves do not help: LDS operand bandwidth (~450 KB per tile) and the MFMA pipe set
+// the pace.
 template <int CP, int NT, int NW>
 __global__ __launch_bounds__(64 * NW, (CP <= 24 ? 2 : 1) * (NW == 8 ? 2 : 1)) void conv_block_fwd_kernel(BlockFwdArgs a, int ntiles, unsigned bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -161,28 +159,8 @@ __global__ __launch_bounds__(64 * NW, (CP <= 24 ? 2 : 1) * (NW == 8 ? 2 : 1)) vo
             for (int i = 0; i < MT1; ++i)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[i][nt] = b1r[nt];
-#if MIL_BLOCK_LOOKAHEAD > 0
             mil_conv_ring<NT, MT1, KSTEPS, MIL_BLOCK_LOOKAHEAD>(acc, ldsW1, lane,
                 [&](int sl, int i) { return ldsX + pixbase1[i] + toff1[sl]; });
-#else
-#pragma unroll
-            for (int sl = 0; sl < KSTEPS; ++sl) {
-                Frag8<BF16> wf[NT];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) wf[nt] = lds_frag<BF16>(ldsW1 + ((sl * NT + nt) * 64 + lane) * 16);
-#pragma unroll
-                for (int i = 0; i < MT1; ++i) {
-#ifndef MIL_BLOCK_KEEP_DUMMY
-                    // row tiles 21..23 lie entirely behind the 324 mid pixels (their results go to the dump slot): skipped
-                    // under a scalar (wave-uniform) branch — 3 of 24 row tiles of conv1's MFMA work
-                    if (i == MT1 - 1 && (wave + NW * i) * 16 >= 324) continue;
-#endif
-                    const Frag8<BF16> xf = lds_frag<BF16>(ldsX + pixbase1[i] + toff1[sl]);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[i][nt] = mma8(wf[nt], xf, acc[i][nt]);
-                }
-            }
-#endif
             // mid pixels outside the image are conv2's zero padding (only tiles on the image border have any)
             const int my0 = o.oy0 - 1, mx0 = o.ox0 - 1;
             const bool border = my0 < 0 || mx0 < 0 || my0 + 18 > H || mx0 + 18 > W;
@@ -222,23 +200,8 @@ __global__ __launch_bounds__(64 * NW, (CP <= 24 ? 2 : 1) * (NW == 8 ? 2 : 1)) vo
         for (int m = 0; m < MT2; ++m)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[m][nt] = b2r[nt];
-#if MIL_BLOCK_LOOKAHEAD > 0
         mil_conv_ring<NT, MT2, KSTEPS, MIL_BLOCK_LOOKAHEAD>(acc, ldsW2, lane,
             [&](int sl, int m) { return ldsO + pixbase2[m] + toff2[sl]; });
-#else
-#pragma unroll
-        for (int sl = 0; sl < KSTEPS; ++sl) {
-            Frag8<BF16> wf[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wf[nt] = lds_frag<BF16>(ldsW2 + ((sl * NT + nt) * 64 + lane) * 16);
-#pragma unroll
-            for (int m = 0; m < MT2; ++m) {
-                const Frag8<BF16> of = lds_frag<BF16>(ldsO + pixbase2[m] + toff2[sl]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mma8(wf[nt], of, acc[m][nt]);
-            }
-        }
-#endif
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) {
             const bool ok = (o_pos[p] >> 10) < ylim && (o_pos[p] & 1023) < xlim;
@@ -264,13 +227,6 @@ __global__ __launch_bounds__(64 * NW, (CP <= 24 ? 2 : 1) * (NW == 8 ? 2 : 1)) vo
     }
 }
 
-static int mil_block_waves() {
-    // measured on the 64x64x24 maps: 434 us with 4 waves per workgroup, 446 us with 8 (16 resident waves per CU at 127
-    // VGPRs) — more resident waves do not help: LDS operand bandwidth (~450 KB per tile) and the MFMA pipe set the pace
-    static const int v = [] { const char* e = mil_ab_env("MIL_BLOCK_WAVES"); return (e && atoi(e) == 8) ? 8 : 4; }();
-    return v;
-}
-
 template <int CP, int NT>
 static int launch_block_fwd(BlockFwdArgs a, hipStream_t st) {
     constexpr int PIXB = mil_pix_pitch(CP, 2), CG = CP / 8;
@@ -283,13 +239,8 @@ static int launch_block_fwd(BlockFwdArgs a, hipStream_t st) {
     a.lds_o_off = x_bytes; a.lds_w_off = x_bytes + o_bytes; a.lds_dump_off = x_bytes + o_bytes + w_bytes;
     const int lds = a.lds_dump_off + 64;
     if (lds > 160 * 1024) return MIL_ERR_UNSUPPORTED;
-#ifdef MIL_AB_SWITCHES
-    const int nw = mil_block_waves();
-    auto kern = nw == 8 ? conv_block_fwd_kernel<CP, NT, 8> : conv_block_fwd_kernel<CP, NT, 4>;
-#else
-    constexpr int nw = 4;              // the 8-wave form (A/B builds only) measured no faster and spills at 128 VGPRs
-    auto kern = conv_block_fwd_kernel<CP, NT, 4>;
-#endif
+    constexpr int nw = 4;
+    auto kern = conv_block_fwd_kernel<CP, NT, nw>;
     if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
     static thread_local int occ_lds = -1, occ_n = 1;
@@ -333,9 +284,7 @@ static int launch_block_fwd(BlockFwdArgs a, hipStream_t st) {
 // either way; rings of 2R rows.  Row tile m of a wave = (row m % R2, column block wave + 4 * (m / R2)) with R2 = rows per
 // column block = R (64 wide) or 2 (128 wide: two column blocks per wave), so that row tiles 2p, 2p+1 are always two rows of
 // the same columns (the epilogue's permlane pairs).
-#ifndef MIL_STRIP_LA
-#define MIL_STRIP_LA 2                // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs
-#endif
+constexpr int MIL_STRIP_LA = 2;      // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs (1, 2, 3 within 1 %)
 template <int SW, int R> struct StripCfg {
     static constexpr int RP = SW + 1, ROW = RP * 48, NR = 2 * R, PLANE = (NR * RP + 1) * 48;
     static constexpr int W_BYTES = 7 * 2 * 64 * 16;
@@ -511,11 +460,11 @@ __global__ __launch_bounds__(256, 2) void conv_block_strip_kernel(BlockFwdArgs a
 
 // The row-walk forms take 64-pixel-wide (bf16: also 128-pixel-wide) maps when whole images fill the resident workgroups well: their unit of work is an image
 // (`steps` steps of `strip_cost` each), the tiled forms' a tile (`tile_cost` each; costs in k cycles, measured).
-// MIL_BLOCK_STRIP (a TEST knob, read per call: "0" never, "1" whenever the map is 64 wide) lets the tests compare the two forms
+// MIL_BLOCK_STRIP (a TEST knob: "0" never, "1" whenever the map is 64 wide) lets the tests compare the two forms
 // bit for bit on small inputs.
 static bool mil_block_strip_wanted(bool width_ok, int n_img, long tiles_per_img, int steps, int tile_cost, int strip_cost, int grid_cap) {
     if (!width_ok) return false;
-    const char* e = getenv("MIL_BLOCK_STRIP");
+    const char* e = mil_test_knob("MIL_BLOCK_STRIP");
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
     const long cost_tile = (n_img * tiles_per_img + grid_cap - 1) / grid_cap * tile_cost;
     const long cost_strip = (long)((n_img + grid_cap - 1) / grid_cap) * steps * strip_cost;

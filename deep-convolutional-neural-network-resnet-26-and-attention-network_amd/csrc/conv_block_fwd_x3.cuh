@@ -17,9 +17,7 @@
 //   * x / o1 / y are addressed at a RUN-TIME pixel stride a.apx: 96 bytes (24 padded channels) or 80 (dense 20 channels).
 #pragma once
 #include "stamp.cuh"
-#ifndef MIL_BFX3_STORE_AUX
-#define MIL_BFX3_STORE_AUX 0            // cache policy of the o1 / y stores (gfx940 encoding: 1 = sc0, 2 = nt, 16 = sc1).  Measured (round 5, 2048 tiles): plain 0.84 ms per launch, nt 1.12, sc1 1.75 — write-through stores do not buy the x halo more L2, they stall the epilogue
-#endif
+constexpr int MIL_BFX3_STORE_AUX = 0;            // cache policy of the o1 / y stores (gfx940 encoding: 1 = sc0, 2 = nt, 16 = sc1).  Measured (round 5, 2048 tiles): plain 0.84 ms per launch, nt 1.12, sc1 1.75 — write-through stores do not buy the x halo more L2, they stall the epilogue
 
 struct BlockFwdX3Args {
     const float* x;         // [n,H,W,apx/4]

@@ -19,9 +19,7 @@
 // A step costs an image prologue (step 0 computes mid rows -1 and 0 only: +3 % of conv1) and whole images are the unit of
 // work, so the launcher takes this form only when the images fill the resident workgroups evenly enough (launch_block_fwd_x3).
 #pragma once
-#ifndef MIL_STRIP_X3_LA
-#define MIL_STRIP_X3_LA 2             // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs
-#endif
+constexpr int MIL_STRIP_X3_LA = 2;      // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs (1, 2, 3 within 1 %)
 
 __global__ __launch_bounds__(256, 2) void conv_block_strip_x3_kernel(BlockFwdX3Args a, int n_img, unsigned bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -242,11 +240,7 @@ __global__ __launch_bounds__(256, 2) void conv_block_strip_x3_kernel(BlockFwdX3A
                 const int jy = 2 * s - 1 + m;
                 const bool inside = (unsigned)jy < (unsigned)H;      // wave-uniform: a mid row outside the image is conv2's zero padding
                 const int sdst = ((nb + m) * RP + col + 1) * PIXB;
-#ifdef MIL_EXP_STRIP_NO_O1
-                const unsigned ooff = MIL_OOB;
-#else
                 const unsigned ooff = inside ? (unsigned)(ibase + (jy * SW + col) * APX + gq * 16) : MIL_OOB;
-#endif
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {            // column tile 1: rows 4-7 (the lane group gq == 1) hold wl*xh of rows 0-3
                     float t0 = acc[m][1][e], t1 = t0;

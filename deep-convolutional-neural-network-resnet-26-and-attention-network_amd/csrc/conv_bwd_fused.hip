@@ -49,33 +49,26 @@ struct BwdFusedArgs {
 #define MIL_ST_MARK(i)
 #endif
 
-#ifndef MIL_BWD_WAVES
-#define MIL_BWD_WAVES 2
-#endif
+constexpr int MIL_BWD_WAVES = 2;
 // NW = waves per workgroup: 4 for the 24-channel layers (two workgroups per CU), 8 for the 40/64-channel layers, whose
 // filter + tiles leave one workgroup per CU: eight waves share its LDS, every per-wave quantity halves (two row tiles of
 // data-gradient accumulators, three to five of weight-gradient ones) and each SIMD still holds two waves.
-#ifndef MIL_BWD_PIPE_MAXC
-#define MIL_BWD_PIPE_MAXC 40      // explicit one-step-ahead operand prefetch for layers up to this many channels (the 64-channel
-#endif                            // instantiation already sits at 256 VGPRs: the second operand set would spill)
+constexpr int MIL_BWD_PIPE_MAXC = 40;    // explicit one-step-ahead operand prefetch (split precision: hi and lo planes) for layers
+                                         // up to this many channels (the 64-channel instantiation already sits at 256 VGPRs: the
+                                         // second operand set would spill)
+constexpr int MIL_BWD24_EU = 3;          // waves per SIMD the 8-wave 24-channel generic form is compiled for: 3 = 168 VGPRs, no spill (at 4 = 128
+                                         // it spilled 18-26; the 16x16-tile kernel below takes the BASELINE sizes and the 300x300 driver size)
 // T = BF16, or F32S (round 3: MIL_DT_F32S — fp32 dz / x / addend / dx, bf16x3 split products).  The pointers of BwdFusedArgs
 // are then float tensors behind their __bf16 type; the dz halo and the x centre tile hold [hi | lo] planes per pixel record,
 // both MFMA loops take three products per fragment pair, the epilogue adds / masks / stores fp32.  24 channels only (one
 // 8-wave workgroup per CU on 94 KB of LDS): the 40-channel filter, halo and x tile do not fit together.
 template <typename T, int CZ, int NTX, int KS, bool ADD, bool MASK, int NW = 4>
-#ifndef MIL_BWD24_EU
-#define MIL_BWD24_EU 3          // waves per SIMD the 8-wave 24-channel generic form is compiled for: 3 = 168 VGPRs, no spill (at 4 = 128
-                                // it spilled 18-26; the 16x16-tile kernel below takes the BASELINE sizes and the 300x300 driver size)
-#endif
 __global__ __launch_bounds__(64 * NW, T::SPLIT ? 2 : ((NW == 8 && CZ <= 24) ? MIL_BWD24_EU : MIL_BWD_WAVES)) void conv_bwd_fused_kernel(BwdFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MIL_POISON(smem);
     constexpr int ESZ = T::ESZ, FRAGB = 8 * ESZ;
     constexpr int NE = T::SPLIT ? 2 : 1;                  // 16-byte registers per 8 channels of an epilogue operand
-#ifndef MIL_BWD_X3_PIPE
-#define MIL_BWD_X3_PIPE 1         // split precision: the same one-step-ahead operand sets (hi and lo planes)
-#endif
-    constexpr bool PIPE = (T::SPLIT ? MIL_BWD_X3_PIPE != 0 : true) && CZ <= MIL_BWD_PIPE_MAXC;
+    constexpr bool PIPE = CZ <= MIL_BWD_PIPE_MAXC;
     constexpr int NL2 = T::SPLIT ? 2 : 1;                 // operand planes of the weight-gradient loop: hi (+ lo)
     constexpr int PIXB = mil_pix_pitch(CZ, ESZ);          // dz halo pixel pitch
     constexpr int CG = CZ / 8;
@@ -181,10 +174,9 @@ __global__ __launch_bounds__(64 * NW, T::SPLIT ? 2 : ((NW == 8 && CZ <= 24) ? MI
     // The tile's x (mask + wgrad operand) and addend are needed only after the data-gradient MFMA loop; their loads are
     // issued a phase early — behind the previous tile's last barrier, under its weight-gradient loop — into the registers
     // that tile has just finished with, so the ~2 us round trip is no longer waited for in the middle of the tile.
-#ifndef MIL_BWD_LATE_ADD_C
-#define MIL_BWD_LATE_ADD_C 64     // from this many channels on, the addend is fetched behind the data-gradient loop instead of a
-#endif                            // phase early: its registers are not live across that loop (the 64-channel form spilled 15-18 VGPRs)
-    constexpr bool LATE_ADD = ADD && CZ >= MIL_BWD_LATE_ADD_C;
+    // From 64 channels on, the addend is fetched behind the data-gradient loop instead of a phase early: its registers are
+    // not live across that loop (the 64-channel form spilled 15-18 VGPRs).
+    constexpr bool LATE_ADD = ADD && CZ >= 64;
     unsigned ooff[NPAIR];
     u32x4_t rxc[NPAIR][NTX][NE], radd[NPAIR][NTX][NE];
     auto fetch_add_late = [&]() {
@@ -521,12 +513,6 @@ __global__ __launch_bounds__(64 * NW, T::SPLIT ? 2 : ((NW == 8 && CZ <= 24) ? MI
 //     RUN-TIME pixel stride a.gpx: 48 bytes (the padded 24-channel layout every activation has) or 40 (dense: the
 //     gradient chain of the 20-channel layer is produced and consumed only by kernels that know this layout —
 //     MIL_DT_BF16_DGRAD —, 17 % fewer bytes on three of the four tensor passes).
-#ifndef MIL_BWD16_K20
-#define MIL_BWD16_K20 1
-#endif
-#ifndef MIL_BWD16_PRIO
-#define MIL_BWD16_PRIO 0      // measured: no difference either way (366-385 us with and without on the same box)
-#endif
 template <bool ADD, bool MASK>
 __global__ __launch_bounds__(512, 4) void conv_bwd_fused16_kernel(BwdFusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -650,11 +636,8 @@ __global__ __launch_bounds__(512, 4) void conv_bwd_fused16_kernel(BwdFusedArgs a
 
     const int buf_step = a.lds_a2_off, xbuf_step = a.lds_x2_off;
     int buf = 0, xbuf = 0;
-#if MIL_BWD16_PRIO
-    // the second-dispatched half of an 8-wave workgroup loses issue arbitration to the older half (priority, then age) and
-    // sets the pace at every barrier (finding 3 of DESIGN.md): one static priority raise for it, no per-phase flips
-    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
+    // (a static priority raise for the second-dispatched half of the workgroup, which loses issue arbitration to the older
+    // half: measured no difference, 366-385 us with and without on the same box)
     MIL_ST_DECL
     for (int tile = bid; tile < a.ntiles; tile += gridDim.x) {
         MIL_ST_BEGIN()
@@ -850,13 +833,6 @@ __global__ __launch_bounds__(512, 4) void conv_bwd_fused16_kernel(BwdFusedArgs a
 
 // (the slab reduction for this layout — rows tap'*CZ + co with tap' the flipped tap, cols ci — is kind 1 of reduce.cuh)
 
-// MIL_BWD16=0 falls back to the generic kernel on 16x16 tiles too (A/B runs, bit-compatible results up to the bias
-// gradient's summation path)
-static bool mil_bwd16_enabled() {
-    static const bool v = [] { const char* e = mil_ab_env("MIL_BWD16"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 template <typename T, int CZ, int NTX, int KS, int NW = 4>
 static int run_bwd_fused(BwdFusedArgs a, float* dw, float* db, void* ws, size_t ws_bytes, int cout, int cin, int accumulate, bool query,
@@ -892,7 +868,7 @@ static int run_bwd_fused(BwdFusedArgs a, float* dw, float* db, void* ws, size_t 
     // (two halo buffers AND two x-tile buffers: 70 KB, two workgroups per CU)
     bool t16 = false;
     if constexpr (CZ == 24 && NTX == 2 && KS == 3 && NW == 8 && !T::SPLIT)
-        t16 = mil_bwd16_enabled() && dbuf && a.g.tw_log2 == 4 && a.g.th_log2 == 4 && a.g.ti_log2 == 0 && a.g.H < 1024 && a.g.W < 1024 &&
+        t16 = dbuf && a.g.tw_log2 == 4 && a.g.th_log2 == 4 && a.g.ti_log2 == 0 && a.g.H < 1024 && a.g.W < 1024 &&
               cout == 20;      // the K20 order (and the packed filter's second section) exists for 20 dz channels
     if (dense_grads && !t16) return MIL_ERR_UNSUPPORTED;      // only the 16x16-tile kernel reads the dense gradient layout
     const int lds = (dbuf ? 2 : 1) * a_bytes + w_bytes + (t16 ? 2 : 1) * x_bytes + DUMPX;          // + dump slot for the x-tile writes
@@ -1068,9 +1044,8 @@ static int bwd_fused_entry(const void* dz, const void* wpack, const void* x, con
     a.g.n_img = n_img; a.g.H = H; a.g.W = W; a.g.Ho = H; a.g.Wo = W; a.g.ks = ks; a.g.stride = 1; a.g.pad = pad; a.g.zins = 0;
     const int czp = mil_cpad(cout), cxp = mil_cpad(cin);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#ifndef MIL_BWD24_WAVES
-#define MIL_BWD24_WAVES 8       // measured in the model: 397/428/401 us per launch with 4 waves per workgroup (two per SIMD), 356/397/371 us with 8 (four per SIMD, 122-128 VGPRs)
-#endif
+    // 24 channels on 8 waves: measured in the model 397/428/401 us per launch with 4 waves per workgroup (two per SIMD),
+    // 356/397/371 us with 8 (four per SIMD, 122-128 VGPRs)
     if (dtype == MIL_DT_F32S || dtype == MIL_DT_F32S_DGRAD) {      // fp32 tensors, bf16x3 products: the 24-channel layers
         if (czp != 24 || cxp != 24) return MIL_ERR_UNSUPPORTED;
         // 16x16 tiles of one image: the compile-time-geometry kernel (two 4-wave workgroups per CU; dense or padded gradients)
@@ -1078,7 +1053,7 @@ static int bwd_fused_entry(const void* dz, const void* wpack, const void* x, con
         if (rc != MIL_ERR_UNSUPPORTED || dense_grads) return rc;          // only that kernel reads the dense layout
         return run_bwd_fused<F32S, 24, 2, 3, 8>(a, dw, db, ws, ws_bytes, cout, cin, accumulate, query, need, st);
     }
-    if (czp == 24 && cxp == 24) return run_bwd_fused<BF16, 24, 2, 3, MIL_BWD24_WAVES>(a, dw, db, ws, ws_bytes, cout, cin, accumulate, query, need, st, dense_grads);
+    if (czp == 24 && cxp == 24) return run_bwd_fused<BF16, 24, 2, 3, 8>(a, dw, db, ws, ws_bytes, cout, cin, accumulate, query, need, st, dense_grads);
     if (dense_grads) return MIL_ERR_UNSUPPORTED;
     if (czp == 40 && cxp == 40) return run_bwd_fused<BF16, 40, 3, 3, 8>(a, dw, db, ws, ws_bytes, cout, cin, accumulate, query, need, st);
     if (czp == 64 && cxp == 64) return run_bwd_fused<BF16, 64, 4, 3, 8>(a, dw, db, ws, ws_bytes, cout, cin, accumulate, query, need, st);

@@ -10,9 +10,6 @@
 // second compact tile.  Wave w owns row tile w (16 pixels) of every class; the paired 16-byte register epilogue
 // of the persistent conv kernel then stores two horizontally adjacent output pixels per lane pair.
 #include "pf_common.cuh"
-#ifndef MIL_DGRAD_S2_X3_NW8
-#define MIL_DGRAD_S2_X3_NW8 1
-#endif
 
 template <typename T>
 struct DgradS2Args {
@@ -202,7 +199,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (STREAM && CZ < 80) || (CZ <= 
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[c][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#ifndef MIL_DGRAD_S2_NO_PIPE
         {
             // one k-step ahead (the steps of the four parity classes flattened into one sequence): the fragments of step
             // s+1 are read before the MFMAs of step s and scheduling fences keep that order (see mil_conv_ring)
@@ -237,23 +233,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (STREAM && CZ < 80) || (CZ <= 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#else
-        {
-            int s = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                for (int sl = 0; sl < mil_s2_steps(c, CG); ++sl, ++s) {
-                    const Frag8<T> xf = lds_pix_frag<T, CZ * 2>(ldsZ + pixbase + toff[s]);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const Frag8<T> wf = lds_frag<T>(ldsW + ((s * NT + nt) * 64 + lane) * FRAGB);
-                        acc[c][nt] = mma8(wf, xf, acc[c][nt]);          // D[channel][pixel]
-                    }
-                }
-            }
-        }
-#endif
         if constexpr (NOPF) fetch_epi(o_cur, ooff, ract);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -363,7 +342,7 @@ extern "C" int mil_conv_dgrad_s2(const void* dz1, const void* dz2, const void* w
         b.slope = slope; b.ypx = dtype == MIL_DT_F32S_DGRAD ? 80 : cx_p * 4;      // y [n,H,W,20] dense fp32, or padded
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         if (cz_p == 40) {               // staged filter: 0.52 ms against 0.60 ms streamed; eight waves on one staged filter where the map allows
-            if (MIL_DGRAD_S2_X3_NW8 && H >= 16 && W >= 32) return launch_dgrad_s2<F32S, 40, 2, false, 8>(b, st);
+            if (H >= 16 && W >= 32) return launch_dgrad_s2<F32S, 40, 2, false, 8>(b, st);
             return launch_dgrad_s2<F32S, 40, 2>(b, st);
         }
         if (cz_p == 64) return launch_dgrad_s2<F32S, 64, 3, true>(b, st);

@@ -23,7 +23,7 @@
 //   + halo-resident form (one halo image per 64-channel chunk read at nine row offsets: 20.6 instead of 48 KB per K-step),
 //     fragment reads of the next half K-step and the copies interleaved between the MFMAs (sched_group_barrier)  766 / 902 / 921
 //   two wave groups staggered by one barrier, four barriers per K-step (reads of one group under the MFMAs of the other)
-//     559 / 605 / 654: slower — kept out; sixteen waves per workgroup (64 x 32 wave tiles): 722 / 798 / 889 — kept as an A/B knob
+//     559 / 605 / 654: slower — kept out; sixteen waves per workgroup (64 x 32 wave tiles): 722 / 798 / 889 — kept out
 //   + the nine taps of a chunk unrolled, the 36 swizzled fragment offsets of a lane precomputed, chunk pairs unrolled so the
 //     halo buffer offset is a ds_read immediate (the loop form spent ~45 of its ~65 vector instructions per K-step beside
 //     the 32 MFMAs on that address arithmetic: the kernel was instruction-issue-bound)                               913 / 1061 / 1063
@@ -85,12 +85,12 @@ __device__ __forceinline__ void gc_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)
 //         K-step s: two K-steps to land), HD = 7 (8x8 pixels of four images) for three.
 // The loop bodies are branch-free — copies that would run past the end get an out-of-range offset and land as zeros in a slot
 // nobody reads again — so that reads, copies and MFMAs of a K-step sit in ONE basic block and can be interleaved.
-// NW = waves per workgroup (8 or 16; one workgroup per CU either way).  A bare loop of 16x16x32 bf16 MFMAs on random operands
+// NW = waves per workgroup: 8 (one workgroup per CU).  A bare loop of 16x16x32 bf16 MFMAs on random operands
 // with one barrier per 32 MFMAs per wave runs at 1.56 PFLOP/s with two waves per SIMD and at 1.83 with four (no barrier: 1.79 /
 // 1.81; one wave per SIMD: 1.13): with sixteen waves the wave tile is 64 pixels x 32 channels (16 MFMAs, 12 fragment reads and
 // at most 2 copies per wave and K-step) and the scheduler has four waves per SIMD to cover reads, copies and barriers with.
 // Measured in this kernel: 722/798/889 TFLOP/s forward with sixteen waves against 749/866/926 with eight (stride-2 shapes equal):
-// the barrier structure is not what holds it, eight stays the default (MIL_GCONV_WAVES=16 for A/B runs).
+// the barrier structure is not what holds it, so eight.
 template <int HD, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void gconv_kernel(GConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -145,7 +145,6 @@ __global__ __launch_bounds__(64 * NW, 1) void gconv_kernel(GConvArgs a) {
     };
     // the schedule of one half: nv copies and NTW + 4 reads spread over NTW * 4 MFMAs
     auto pin_half = [&](int nv) {
-#ifndef GC_NO_PIN
         constexpr int NR = NTW + 4, MPR = (NTW * 4) / NR;       // reads, MFMAs per read: 8 / 2 or 6 / 1
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
@@ -153,7 +152,6 @@ __global__ __launch_bounds__(64 * NW, 1) void gconv_kernel(GConvArgs a) {
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // 1 DS read
             if (i < nv) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // 1 VMEM read (LDS-DMA copy)
         }
-#endif
     };
     Half f0, f1;
 
@@ -295,125 +293,87 @@ __global__ __launch_bounds__(64 * NW, 1) void gconv_kernel(GConvArgs a) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         read_half(f0, 0, 0, 0, 0);
-#ifndef GC_UNROLL_TAPS
-#define GC_UNROLL_TAPS 1
-#endif
-        if constexpr (NW == 8 && GC_UNROLL_TAPS) {
-            // The nine taps of a chunk unrolled, with the 36 swizzled fragment offsets of this lane (tap x pixel tile) computed
-            // once: the loop form spends ~45 of its ~65 vector instructions per K-step beside the 32 MFMAs on that arithmetic.
-            // Tap-dependent decisions (which K-steps carry a halo piece, the counted waits) become compile-time.
-            int xoff[9][4];
+        // The nine taps of a chunk unrolled, with the 36 swizzled fragment offsets of this lane (tap x pixel tile) computed
+        // once: the loop form spends ~45 of its ~65 vector instructions per K-step beside the 32 MFMAs on that arithmetic.
+        // Tap-dependent decisions (which K-steps carry a halo piece, the counted waits) become compile-time.
+        int xoff[9][4];
 #pragma unroll
-            for (int t = 0; t < 9; ++t)
+        for (int t = 0; t < 9; ++t)
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const int row = prow[mt] + (t / 3) * hw + (t % 3);
-                    xoff[t][mt] = row * 128 + ((((row >> 1) & 7) ^ gq) * 16);
-                }
-            auto read_half_u = [&](Half& h, int hb, int t, int slot, int k32) {      // t: compile-time; hb: halo buffer offset
-                read_w(h, ring + slot * GC_B_BYTES, k32);
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) h.x[mt] = *reinterpret_cast<const bf16x8_t*>(smem + hb + (xoff[t][mt] ^ (k32 * 64)));
-            };
-            auto issue_halo_u = [&](int c, int j) {                // j: compile-time; past the last chunk: zeros into the idle buffer
-                const unsigned o = (h_off[j] == (int)MIL_OOB || c >= nchunks) ? MIL_OOB : (unsigned)(h_off[j] + c * (GC_BK * 2));
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, GC_LDS_PTR(smem + (c & 1) * hbytes + (j * NW + wave) * 1024), 16, o, 0, 0, 0);
-            };
-            // one chunk = nine K-steps; PAR = the chunk's halo buffer (compile-time, so the buffer offset folds into the
-            // ds_read immediates)
-            auto chunk = [&](int c, auto par) {
-                constexpr int PAR = decltype(par)::value;
-                constexpr int hb = PAR * hbytes, hbn = hbytes - hb;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    // K-step s = 9c + t in ring slot s % RS (9 = 1 mod 4, 0 mod 3).  Three ring slots: ONE barrier, in the middle of the
-                    // K-step:
-                    //   first half : request filter image s + RS - 1 into the slot K-step s-1 read (every wave finished those reads
-                    //                before the previous mid-step barrier) and, t < NHP, a piece of the next chunk's halo; read the
-                    //                second-half fragments of stage s; MFMAs of the first half
-                    //   middle     : this wave's pieces of filter image s+1 (and everything older) have landed — counted wait over the
-                    //                copies requested since — its fragment reads are back; barrier
-                    //   second half: read the first-half fragments of stage s+1; MFMAs of the second half
-                    // so a copy has a whole K-step (RS = 3) or two (RS = 4) to land; with the barrier at the top of the K-step the
-                    // second piece of a filter image had half a K-step at RS = 3 and the wait stalled every K-step.
-                    const int slot = RS == 4 ? ((c + t) & 3) : (t % 3);
-                    const int nslot = RS == 4 ? ((c + t + 1) & 3) : ((t + 1) % 3);
-                    const int islot = RS == 4 ? ((c + t + 3) & 3) : ((t + 2) % 3);      // the slot K-step s-1 read
-                    const int tb = (t + RS - 1) % 9, cb = c + (t + RS - 1) / 9;         // filter image s + RS - 1
-                    if constexpr (RS == 3) {
-                        if (t < NHP) issue_halo_u(c + 1, t);
-#pragma unroll
-                        for (int j = 0; j < NBP; ++j) issue_b(cb, tb, islot, j);
-                        read_half_u(f1, hb, t, slot, 1);
-                        mfma_half(f0);
-                        pin_half((t < NHP ? 1 : 0) + NBP);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (t < NHP) gc_wait_vm<NBP + 1>(); else gc_wait_vm<NBP>();      // younger: this K-step's halo piece and filter image s+2
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                        read_half_u(f0, t == 8 ? hbn : hb, t == 8 ? 0 : t + 1, nslot, 0);
-                        mfma_half(f1);
-                        pin_half(0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else {
-                        // four ring slots: a filter image is requested two K-steps before its first read, the barrier at the top of
-                        // the K-step costs nothing in latency (the mid-step form measured 4-7 % slower here: its lgkmcnt(0))
-                        if (t >= 1 && t - 1 < NHP) gc_wait_vm<NBP + 1>(); else gc_wait_vm<NBP>();
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (t < NHP) issue_halo_u(c + 1, t);
-                        issue_b(cb, tb, islot, 0);
-                        read_half_u(f1, hb, t, slot, 1);
-                        mfma_half(f0);
-                        pin_half(t < NHP ? 2 : 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (NBP == 2) issue_b(cb, tb, islot, 1);
-                        read_half_u(f0, t == 8 ? hbn : hb, t == 8 ? 0 : t + 1, nslot, 0);
-                        mfma_half(f1);
-                        pin_half(NBP == 2 ? 1 : 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            };
-            for (int c = 0; c < nchunks; c += 2) {
-                chunk(c, std::integral_constant<int, 0>{});
-                if (c + 1 < nchunks) chunk(c + 1, std::integral_constant<int, 1>{});
+            for (int mt = 0; mt < 4; ++mt) {
+                const int row = prow[mt] + (t / 3) * hw + (t % 3);
+                xoff[t][mt] = row * 128 + ((((row >> 1) & 7) ^ gq) * 16);
             }
-        } else {
-        int slot = 0, c = 0, t = 0, kx = 0, toff = 0;            // K-step s = 9c + t; toff = (t/3)*hw + t%3
-            int cb = 0, tb = RS - 1;                                 // filter image s + RS - 1
-            bool prev_h = false;
-            for (int s = 0; s < KT; ++s) {
-                // Filter image s+1 has landed (and, older than it, the next chunk's halo when s+1 starts a chunk): the copies
-                // requested after it — the previous K-step's halo piece and, RS == 4, filter image s+2 — may still be in flight
-                if constexpr (RS == 4) { if (prev_h) gc_wait_vm<NBP + 1>(); else gc_wait_vm<NBP>(); }
-                else gc_wait_vm<0>();
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                int nslot = slot + 1; if (nslot == RS) nslot = 0;
-                int islot = slot - 1; if (islot < 0) islot = RS - 1;        // the slot K-step s-1 read
-                // the next K-step: tap, row offset, chunk
-                int tn = t + 1, kxn = kx + 1, toffn = toff + 1, cn = c;
-                if (kxn == 3) { kxn = 0; toffn += hw - 3; }
-                if (tn == 9) { tn = 0; toffn = 0; ++cn; }
-                prev_h = t < NHP && piece_exists(t) && c + 1 < nchunks;
-                if (prev_h) issue_halo(c + 1, t);
-                __builtin_amdgcn_sched_barrier(0);
-                issue_b(cb, tb, islot, 0);
-                read_half(f1, c, toff, slot, 1);
-                mfma_half(f0);
-                pin_half(1);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (NBP == 2) issue_b(cb, tb, islot, 1);
-                read_half(f0, cn, toffn, nslot, 0);
-                mfma_half(f1);
-                pin_half(NBP == 2 ? 1 : 0);
-                __builtin_amdgcn_sched_barrier(0);
-                slot = nslot; t = tn; kx = kxn; toff = toffn; c = cn;
-                if (++tb == 9) { tb = 0; ++cb; }
+        auto read_half_u = [&](Half& h, int hb, int t, int slot, int k32) {      // t: compile-time; hb: halo buffer offset
+            read_w(h, ring + slot * GC_B_BYTES, k32);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) h.x[mt] = *reinterpret_cast<const bf16x8_t*>(smem + hb + (xoff[t][mt] ^ (k32 * 64)));
+        };
+        auto issue_halo_u = [&](int c, int j) {                // j: compile-time; past the last chunk: zeros into the idle buffer
+            const unsigned o = (h_off[j] == (int)MIL_OOB || c >= nchunks) ? MIL_OOB : (unsigned)(h_off[j] + c * (GC_BK * 2));
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, GC_LDS_PTR(smem + (c & 1) * hbytes + (j * NW + wave) * 1024), 16, o, 0, 0, 0);
+        };
+        // one chunk = nine K-steps; PAR = the chunk's halo buffer (compile-time, so the buffer offset folds into the
+        // ds_read immediates)
+        auto chunk = [&](int c, auto par) {
+            constexpr int PAR = decltype(par)::value;
+            constexpr int hb = PAR * hbytes, hbn = hbytes - hb;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                // K-step s = 9c + t in ring slot s % RS (9 = 1 mod 4, 0 mod 3).  Three ring slots: ONE barrier, in the middle of the
+                // K-step:
+                //   first half : request filter image s + RS - 1 into the slot K-step s-1 read (every wave finished those reads
+                //                before the previous mid-step barrier) and, t < NHP, a piece of the next chunk's halo; read the
+                //                second-half fragments of stage s; MFMAs of the first half
+                //   middle     : this wave's pieces of filter image s+1 (and everything older) have landed — counted wait over the
+                //                copies requested since — its fragment reads are back; barrier
+                //   second half: read the first-half fragments of stage s+1; MFMAs of the second half
+                // so a copy has a whole K-step (RS = 3) or two (RS = 4) to land; with the barrier at the top of the K-step the
+                // second piece of a filter image had half a K-step at RS = 3 and the wait stalled every K-step.
+                const int slot = RS == 4 ? ((c + t) & 3) : (t % 3);
+                const int nslot = RS == 4 ? ((c + t + 1) & 3) : ((t + 1) % 3);
+                const int islot = RS == 4 ? ((c + t + 3) & 3) : ((t + 2) % 3);      // the slot K-step s-1 read
+                const int tb = (t + RS - 1) % 9, cb = c + (t + RS - 1) / 9;         // filter image s + RS - 1
+                if constexpr (RS == 3) {
+                    if (t < NHP) issue_halo_u(c + 1, t);
+#pragma unroll
+                    for (int j = 0; j < NBP; ++j) issue_b(cb, tb, islot, j);
+                    read_half_u(f1, hb, t, slot, 1);
+                    mfma_half(f0);
+                    pin_half((t < NHP ? 1 : 0) + NBP);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t < NHP) gc_wait_vm<NBP + 1>(); else gc_wait_vm<NBP>();      // younger: this K-step's halo piece and filter image s+2
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    read_half_u(f0, t == 8 ? hbn : hb, t == 8 ? 0 : t + 1, nslot, 0);
+                    mfma_half(f1);
+                    pin_half(0);
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+                    // four ring slots: a filter image is requested two K-steps before its first read, the barrier at the top of
+                    // the K-step costs nothing in latency (the mid-step form measured 4-7 % slower here: its lgkmcnt(0))
+                    if (t >= 1 && t - 1 < NHP) gc_wait_vm<NBP + 1>(); else gc_wait_vm<NBP>();
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t < NHP) issue_halo_u(c + 1, t);
+                    issue_b(cb, tb, islot, 0);
+                    read_half_u(f1, hb, t, slot, 1);
+                    mfma_half(f0);
+                    pin_half(t < NHP ? 2 : 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (NBP == 2) issue_b(cb, tb, islot, 1);
+                    read_half_u(f0, t == 8 ? hbn : hb, t == 8 ? 0 : t + 1, nslot, 0);
+                    mfma_half(f1);
+                    pin_half(NBP == 2 ? 1 : 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-    }
+        };
+        for (int c = 0; c < nchunks; c += 2) {
+            chunk(c, std::integral_constant<int, 0>{});
+            if (c + 1 < nchunks) chunk(c + 1, std::integral_constant<int, 1>{});
+        }
         gc_wait_vm<0>();
     }
 
@@ -508,41 +468,31 @@ static int gconv_launch(GConvArgs a, hipStream_t st) {
     int tw, th;
     if (Wg > 8 || Hg > 8) {
         const long c16 = (long)((Wg + 15) >> 4) * ((Hg + 15) >> 4) * 4, c8 = (long)((Wg + 7) >> 3) * ((Hg + 7) >> 3);
-        static const bool tile8 = [] { const char* e = mil_ab_env("MIL_GCONV_TILE8"); return e && e[0] == '1'; }();      // A/B runs
-        tw = th = (c8 < c16 || (tile8 && c8 <= c16)) ? 3 : 4;
+        tw = th = c8 < c16 ? 3 : 4;
     } else if (Wg > 4 || Hg > 4) tw = th = 3;
     else tw = th = 2;
     a.tw_log2 = tw; a.th_log2 = th; a.ti_log2 = 8 - tw - th;
     a.tiles_x = (Wg + (1 << tw) - 1) >> tw; a.tiles_y = (Hg + (1 << th) - 1) >> th;
     const int groups = (a.n_img + (1 << a.ti_log2) - 1) >> a.ti_log2;
-    static const bool no_halo = [] { const char* e = mil_ab_env("MIL_GCONV_NO_HALO"); return e && e[0] == '1'; }();      // A/B runs: per-K-step gather everywhere
     // the canonical 3x3 stride-1 tap list runs on the halo-resident form when two halo images fit beside the filter ring
-    bool canon = a.ncls == 1 && a.ss == 1 && a.os == 1 && a.c_ntaps[0] == 9 && a.ktaps == 9 && !no_halo;
+    bool canon = a.ncls == 1 && a.ss == 1 && a.os == 1 && a.c_ntaps[0] == 9 && a.ktaps == 9;
     for (int t = 0; t < 9 && canon; ++t) canon = a.c_tap[0][t] == (((t / 3 - 1 + 8) << 16) | ((t % 3 - 1 + 8) << 8) | t);
     // halo-resident forms exist for the two tile shapes the choice above produces on maps of 8 pixels and more: 16x16 pixels of one
     // image (324 halo rows: six 64-row pieces per wave-set) and 8x8 pixels of four images (400 rows: seven)
     const int hd = canon ? (tw == 4 ? 6 : (tw == 3 ? 7 : 0)) : 0;
-    static const int nw = [] { const char* e = mil_ab_env("MIL_GCONV_WAVES"); return e && atoi(e) == 16 ? 16 : 8; }();      // A/B runs
     static std::atomic<unsigned long long> attr_set{0};      // per device
     if (mil_device_needs(attr_set)) {
-        const void* ks[6] = {reinterpret_cast<const void*>(gconv_kernel<0, 8>), reinterpret_cast<const void*>(gconv_kernel<6, 8>),
-                             reinterpret_cast<const void*>(gconv_kernel<7, 8>), reinterpret_cast<const void*>(gconv_kernel<0, 16>),
-                             reinterpret_cast<const void*>(gconv_kernel<6, 16>), reinterpret_cast<const void*>(gconv_kernel<7, 16>)};
+        const void* ks[3] = {reinterpret_cast<const void*>(gconv_kernel<0, 8>), reinterpret_cast<const void*>(gconv_kernel<6, 8>),
+                             reinterpret_cast<const void*>(gconv_kernel<7, 8>)};
         for (const void* k : ks)
             if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MIL_ERR_LAUNCH;
         mil_device_done(attr_set);
     }
     const dim3 grid(groups * a.tiles_y * a.tiles_x, a.cout / GC_BN, a.ncls);
     const int lds = hd == 6 ? 2 * 6 * 8192 + 4 * GC_B_BYTES : (hd == 7 ? 2 * 7 * 8192 + 3 * GC_B_BYTES : GC_LDS_BYTES);
-    if (nw == 16) {
-        if (hd == 6) hipLaunchKernelGGL((gconv_kernel<6, 16>), grid, dim3(1024), lds, st, a);
-        else if (hd == 7) hipLaunchKernelGGL((gconv_kernel<7, 16>), grid, dim3(1024), lds, st, a);
-        else hipLaunchKernelGGL((gconv_kernel<0, 16>), grid, dim3(1024), lds, st, a);
-    } else {
-        if (hd == 6) hipLaunchKernelGGL((gconv_kernel<6, 8>), grid, dim3(512), lds, st, a);
-        else if (hd == 7) hipLaunchKernelGGL((gconv_kernel<7, 8>), grid, dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((gconv_kernel<0, 8>), grid, dim3(512), lds, st, a);
-    }
+    if (hd == 6) hipLaunchKernelGGL((gconv_kernel<6, 8>), grid, dim3(512), lds, st, a);
+    else if (hd == 7) hipLaunchKernelGGL((gconv_kernel<7, 8>), grid, dim3(512), lds, st, a);
+    else hipLaunchKernelGGL((gconv_kernel<0, 8>), grid, dim3(512), lds, st, a);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

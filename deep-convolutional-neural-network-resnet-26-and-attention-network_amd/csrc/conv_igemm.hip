@@ -157,15 +157,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
 // FLAGS: -1 = epilogue options read from the arguments at run time; otherwise a bit mask fixed at compile time
 // (1 residual/addend, 2 lrelu' mask, 4 LeakyReLU): the unused operand prefetch registers and branches disappear, which
 // for the 24-channel layers is the difference between two and three resident waves per SIMD.
-#ifndef MIL_PF_WAVES_24
-#define MIL_PF_WAVES_24 2       // (3 waves per SIMD = 168 VGPRs spilled 13 in the residual / mask variants; the whole-block forward and the fused backward have taken the hot launches)
-#endif
-// which instantiations get the explicit one-step-ahead operand prefetch (it costs a second operand register set)
-#ifndef MIL_PF_PIPE
-// measured: no gain on the 64/80-channel forms (56.0/52.5 -> 56.8/50.2 us per launch); the 24/40-channel forms sit at their
-// VGPR cap (3-4 waves per SIMD) and a second operand set spills -> off
-#define MIL_PF_PIPE(CINP, NT, MTW, NW) false
-#endif
+constexpr int MIL_PF_WAVES_24 = 2;       // (3 waves per SIMD = 168 VGPRs spilled 13 in the residual / mask variants; the whole-block forward and the fused backward have taken the hot launches)
 // NW = waves per workgroup: 4, or 8 for the layers whose resident filter leaves room for only ONE workgroup per CU
 // (64 channels: 72 KB of filter) — eight waves on the same LDS tiles give every SIMD a second wave to overlap with.
 // T = BF16, or F32S: the same pipeline on fp32 tensors with split-precision products (MIL_DT_F32S) — the halo pieces are
@@ -181,30 +173,27 @@ template <> struct Epi8<F32S> { u32x4_t v[2]; };
 // fit LDS whole (split precision, 64 channels: 147 KB of [hi | lo] fragments; a half is 74 KB next to a 128-pixel halo tile).
 // Every grid row walks all tiles, so the input is read once per row (the second read mostly from L2 / Infinity Cache: the
 // rows run side by side), the output once.
-template <typename T, int CINP, int NT, int KS, int MTW, int FLAGS = -1, int NW = 4, int NTALL = NT>
 // Waves per SIMD the 8-wave 24/40-channel forms are compiled for.  The forward variants that BASELINE configurations launch
 // (FLAGS 4 / 5: bias + LeakyReLU, + residual) stay at 4 (128 VGPRs; the residual form spills 6 of them): measured round 4 on
 // MI355X, 113 us per launch at 4 against 139 us at 3 waves per SIMD with no spill (256x256 tiles; 136 vs 179 us at 300x300) — two
 // resident workgroups beat a spill-free single one.  The data-gradient variants (FLAGS -1, 2, 3: 12-27 spills at 128) are compiled
 // for 3 waves per SIMD (168 VGPRs, no spill): the fused backward kernels have taken their launches at every BASELINE size.
-#ifndef MIL_PF40_EU
-#define MIL_PF40_EU(FLAGS) (((FLAGS) == 4 || (FLAGS) == 5) ? 4 : 3)
-#endif
-__global__ __launch_bounds__(64 * NW, T::SPLIT ? (NW == 8 ? 2 : (CINP <= 24 ? 2 : 1)) : (NW == 8 ? (CINP <= 40 ? MIL_PF40_EU(FLAGS) : 2) : ((MTW == 2 && CINP <= 24) ? 4 : (CINP <= 24 && FLAGS >= 0 && FLAGS != 3) ? MIL_PF_WAVES_24 : (CINP <= 40 ? 2 : 1))))
+constexpr int mil_pf40_eu(int flags) { return (flags == 4 || flags == 5) ? 4 : 3; }
+template <typename T, int CINP, int NT, int KS, int MTW, int FLAGS = -1, int NW = 4, int NTALL = NT>
+__global__ __launch_bounds__(64 * NW, T::SPLIT ? (NW == 8 ? 2 : (CINP <= 24 ? 2 : 1)) : (NW == 8 ? (CINP <= 40 ? mil_pf40_eu(FLAGS) : 2) : ((MTW == 2 && CINP <= 24) ? 4 : (CINP <= 24 && FLAGS >= 0 && FLAGS != 3) ? MIL_PF_WAVES_24 : (CINP <= 40 ? 2 : 1))))
 void conv_igemm_pf_kernel(ConvArgs<T> a, int ntiles, unsigned x_bytes, unsigned y_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MIL_POISON(smem);
     constexpr int ESZ = T::ESZ;
     constexpr int FRAGB = 8 * ESZ;              // bytes of one packed filter fragment per lane
-#ifndef MIL_PF_PIPE_X3
-// split precision: the one-step-ahead operand sets where they fit the 256-VGPR budget of two waves per SIMD
-// (measured with everything on: 24 channels spill 47-145 VGPRs, the 40-channel res+mask variant 64; the 40-channel 8-wave forms
-// with one epilogue operand fit at 230-252, the 64-channel column-split form at 178-194)
-// Only the 8-wave forms: the 4-wave 64-channel 1x1 zero-insert form (256 VGPRs + 216 AGPRs either way) went from 0.21 to
-// 0.53 ms with it.
-#define MIL_PF_PIPE_X3(CINP, NT, MTW, NW, FLAGS) ((NW) == 8 && ((CINP) == 64 || ((CINP) == 40 && (FLAGS) >= 0 && (FLAGS) != 3)))
-#endif
-    constexpr bool PIPE = T::SPLIT ? MIL_PF_PIPE_X3(CINP, NT, MTW, NW, FLAGS) : MIL_PF_PIPE(CINP, NT, MTW, NW);
+    // Which instantiations get the explicit one-step-ahead operand prefetch (it costs a second operand register set).
+    // bf16: none — measured no gain on the 64/80-channel forms (56.0/52.5 -> 56.8/50.2 us per launch); the 24/40-channel
+    // forms sit at their VGPR cap (3-4 waves per SIMD) and a second operand set spills.
+    // Split precision: where it fits the 256-VGPR budget of two waves per SIMD (measured with everything on: 24 channels
+    // spill 47-145 VGPRs, the 40-channel res+mask variant 64; the 40-channel 8-wave forms with one epilogue operand fit at
+    // 230-252, the 64-channel column-split form at 178-194).  Only the 8-wave forms: the 4-wave 64-channel 1x1 zero-insert
+    // form (256 VGPRs + 216 AGPRs either way) went from 0.21 to 0.53 ms with it.
+    constexpr bool PIPE = T::SPLIT && NW == 8 && (CINP == 64 || (CINP == 40 && FLAGS >= 0 && FLAGS != 3));
     constexpr int PIXB = mil_pix_pitch(CINP, ESZ);
     constexpr int CG = CINP / 8;
     constexpr int COUTP = mil_nt_to_cp(NTALL);
@@ -323,19 +312,12 @@ void conv_igemm_pf_kernel(ConvArgs<T> a, int ntiles, unsigned x_bytes, unsigned 
 
     // EPI_AHEAD: request the epilogue operands a whole tile ahead (costs one more register set; the 40/64-channel
     // instantiations have no room for it and request them at the start of their own tile instead).
-    // DEPTH: how many tiles ahead the halo loads run.  A load round trip under load is ~2 us whether it hits
-    // L2 or HBM, about one tile time, so the narrowest layers keep TWO tiles of halo loads in flight (two
-    // register sets, tile loop unrolled by two).
+    // DEPTH: how many tiles ahead the halo loads run.  A load round trip under load is ~2 us whether it hits L2 or HBM, about
+    // one tile time; measured twice, a second tile of halo loads in flight (two register sets, tile loop unrolled by two) is 8%
+    // slower on the 24-channel layers and no faster on the 40-channel ones (108 -> 107 us plain, 142 -> 230 us with both
+    // epilogue operands: the second register set spills).
     constexpr bool EPI_AHEAD = CINP <= 24 && !T::SPLIT;
-#ifndef MIL_PF_DEPTH40
-#define MIL_PF_DEPTH40 1
-#endif
-    // measured twice: a second tile of halo loads in flight is 8% slower on the 24-channel layers and no faster on the
-    // 40-channel ones (108 -> 107 us plain, 142 -> 230 us with both epilogue operands: the second register set spills)
-#ifndef MIL_PF_DEPTH80
-#define MIL_PF_DEPTH80 1
-#endif
-    constexpr int DEPTH = (CINP == 40 && NW == 4) ? MIL_PF_DEPTH40 : (CINP == 80 ? MIL_PF_DEPTH80 : 1);
+    constexpr int DEPTH = 1;
     const int G = gridDim.x;
     TileWalker nx2 = nxt;
     nx2.advance();
@@ -585,31 +567,11 @@ static int launch_conv(const ConvArgs<T>& a0, hipStream_t stream) {
 // threshold (the parity tests set it to 1 so that small cases run the persistent kernels too).
 #include <cstdlib>
 static int mil_pf_min_tiles() {
-    const char* e = getenv("MIL_PF_MIN_TILES");
+    const char* e = mil_test_knob("MIL_PF_MIN_TILES");
     return e ? atoi(e) : 512;
 }
 
-static int mil_pf_rounds() {
-    static const int r = [] { const char* e = mil_ab_env("MIL_PF_ROUNDS"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
-    return r;
-}
-
-static bool mil_pf_double_buffer() {
-    static const bool v = [] { const char* e = mil_ab_env("MIL_PF_DBUF"); return !(e && atoi(e) == 0); }();
-    return v;
-}
-
-static int mil_pf_waves64() {
-    static const int v = [] { const char* e = mil_ab_env("MIL_PF_WAVES64"); return (e && atoi(e) == 4) ? 4 : 8; }();
-    return v;
-}
-
-#ifndef MIL_PF_WG_PER_CU
-#define MIL_PF_WG_PER_CU 4
-#endif
-#ifndef MIL_PF_MTW_24
-#define MIL_PF_MTW_24 4
-#endif
+constexpr int MIL_PF_WG_PER_CU = 4;
 template <typename T, int CINP, int NT, int KS, int MTW, int FLAGS, int NW = 4, int NTALL = NT>
 static auto conv_pf_variant() { return conv_igemm_pf_kernel<T, CINP, NT, KS, MTW, FLAGS, NW, NTALL>; }
 
@@ -627,7 +589,7 @@ static int launch_conv_pf_ks(const ConvArgs<T>& a0, hipStream_t stream, bool* ta
     const int a_bytes = ((halo_px * PIXB + 15) & ~15) + DUMPB;  // + dump slot for the branch-free halo commit
     const int w_bytes = a.nsteps * NT * 64 * 8 * ESZ;
     // a second halo buffer (one barrier per tile instead of two) when it does not cost a resident workgroup
-    const bool dbuf = mil_pf_double_buffer() && (160 * 1024) / (2 * a_bytes + w_bytes) >= ((160 * 1024) / (a_bytes + w_bytes) > 2 ? 3 : (160 * 1024) / (a_bytes + w_bytes));
+    const bool dbuf = (160 * 1024) / (2 * a_bytes + w_bytes) >= ((160 * 1024) / (a_bytes + w_bytes) > 2 ? 3 : (160 * 1024) / (a_bytes + w_bytes));
     const int lds = (dbuf ? 2 : 1) * a_bytes + w_bytes;
     if (lds > 160 * 1024) return MIL_OK;
     if (a.g.hh >= 1024 || a.g.hw >= 1024 || a.slope < 0.f || a.slope >= 1.f) return MIL_OK;   // max(v, slope*v) form
@@ -649,7 +611,7 @@ static int launch_conv_pf_ks(const ConvArgs<T>& a0, hipStream_t stream, bool* ta
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
             return MIL_ERR_LAUNCH;
     }
-    const int per_cu = mil_resident_per_cu(kern, lds, MIL_PF_WG_PER_CU, 64 * NW) * mil_pf_rounds();   // rounds of resident workgroups
+    const int per_cu = mil_resident_per_cu(kern, lds, MIL_PF_WG_PER_CU, 64 * NW);
     // buffer descriptors address < 2 GiB: split the launch by images when a tensor is larger
     const size_t x_img = (size_t)a.g.H * a.g.W * CINP * ESZ, y_img = (size_t)a.g.Ho * a.g.Wo * COUTP * ESZ;
     int chunk = mil_imgs_under_2g(x_img > y_img ? x_img : y_img);
@@ -679,16 +641,10 @@ template <typename T, int CINP, int NT>
 static int launch_conv_pf(const ConvArgs<T>& a, hipStream_t stream, bool* taken) {
     *taken = false;
     if constexpr (CINP == 16 && NT == 2) { if (a.g.ks == 4) return launch_conv_pf_ks<T, 16, 2, 4>(a, stream, taken); }
-    if constexpr (CINP == 24 && NT == 2) { if (a.g.ks == 3) return launch_conv_pf_ks<T, 24, 2, 3, MIL_PF_MTW_24>(a, stream, taken); }
-#ifndef MIL_PF40_WAVES
-#define MIL_PF40_WAVES 8        // measured in the model: 122 / 100 us per launch with 4 waves, 114 / 88 us with 8 (four waves per SIMD)
-#endif
+    if constexpr (CINP == 24 && NT == 2) { if (a.g.ks == 3) return launch_conv_pf_ks<T, 24, 2, 3>(a, stream, taken); }
     if constexpr (CINP == 40 && NT == 3) {
-#if MIL_PF40_WAVES == 8
+        // 8 waves: measured in the model 122 / 100 us per launch with 4 waves, 114 / 88 us with 8 (four waves per SIMD)
         if (a.g.ks == 3) return launch_conv_pf_ks<T, 40, 3, 3, 2, 8>(a, stream, taken);
-#else
-        if (a.g.ks == 3) return launch_conv_pf_ks<T, 40, 3, 3>(a, stream, taken);
-#endif
     }
     if constexpr (CINP == 40 && NT == 2) {
         if (a.g.ks == 3) return launch_conv_pf_ks<T, 40, 2, 3>(a, stream, taken);
@@ -698,7 +654,7 @@ static int launch_conv_pf(const ConvArgs<T>& a, hipStream_t stream, bool* taken)
         // split precision: the 147 KB filter does not fit — two grid rows of 32 output channels each on 128-pixel tiles
         if constexpr (T::SPLIT) { if (a.g.ks == 3) return launch_conv_pf_ks<T, 64, 2, 3, 1, 8, 4>(a, stream, taken); }
         else
-        if (a.g.ks == 3) return mil_pf_waves64() == 8 ? launch_conv_pf_ks<T, 64, 4, 3, 2, 8>(a, stream, taken) : launch_conv_pf_ks<T, 64, 4, 3>(a, stream, taken);
+        if (a.g.ks == 3) return launch_conv_pf_ks<T, 64, 4, 3, 2, 8>(a, stream, taken);
     }
     if constexpr (CINP == 64 && NT == 3) {
         // split precision (the 64 -> 40 channel stage-entry data gradient, zero-insert): three grid rows of one column tile
@@ -714,10 +670,10 @@ static int launch_conv_pf(const ConvArgs<T>& a, hipStream_t stream, bool* taken)
         // 128-pixel tiles — measured 124 us per conv against 103 us on the K-chunked generic kernel: not dispatched)
         if constexpr (T::SPLIT) { return MIL_OK; }
         else
-        if (a.g.ks == 3) return mil_pf_waves64() == 8 ? launch_conv_pf_ks<T, 80, 5, 3, 1, 8>(a, stream, taken) : launch_conv_pf_ks<T, 80, 5, 3, 2>(a, stream, taken);
+        if (a.g.ks == 3) return launch_conv_pf_ks<T, 80, 5, 3, 1, 8>(a, stream, taken);
     }
     if constexpr (CINP == 80 && NT == 4) {
-        if (a.g.ks == 3) return mil_pf_waves64() == 8 ? launch_conv_pf_ks<T, 80, 4, 3, 1, 8>(a, stream, taken) : launch_conv_pf_ks<T, 80, 4, 3, 2>(a, stream, taken);
+        if (a.g.ks == 3) return launch_conv_pf_ks<T, 80, 4, 3, 1, 8>(a, stream, taken);
         if (a.g.ks == 1) return launch_conv_pf_ks<T, 80, 4, 1, 2>(a, stream, taken);
     }
     return MIL_OK;

@@ -46,12 +46,7 @@ struct ResArgs {
     float slope;
 };
 
-#ifndef MIL_RES_WARM
-#define MIL_RES_WARM 1          // touch the filters at kernel start (see the kernel)
-#endif
-#ifndef MIL_RES_BDEPTH
-#define MIL_RES_BDEPTH 2        // k-steps of filter fragments in flight per wave
-#endif
+constexpr int MIL_RES_BDEPTH = 2;        // k-steps of filter fragments in flight per wave
 
 template <int C, int S, int IMGS>
 struct ResGeom {
@@ -89,7 +84,6 @@ __global__ __launch_bounds__(512, 2) void conv_resident_kernel(ResArgs a) {
     const int r = lane & 15, gq = lane >> 4;
     const __amdgpu_buffer_rsrc_t rs_x = mil_rsrc(a.x, a.bytes);
 
-#if MIL_RES_WARM
     // ---- pull every conv's filter into L2 now: the k-step loops read it fragment by fragment two k-steps ahead, which
     // hides an L2 hit but not the HBM miss a filter packed 9 ms (30 GB of traffic) ago costs — every k-step's first touch
     // would stall all waves of all workgroups at once.  One dword per 128-byte line and thread, results never used.
@@ -101,7 +95,6 @@ __global__ __launch_bounds__(512, 2) void conv_resident_kernel(ResArgs a) {
         for (int line = tid; line < KSTEPS * NT * 8; line += 512)
             sink ^= __builtin_amdgcn_raw_buffer_load_b32(rs_wk, (unsigned)line * 128u, 0, 0);
     }
-#endif
     // ---- zero border records, once: the commits and the first conv's epilogue only ever write interiors ----------------
     {
         constexpr int NB = 4 * S + 4, PPR = PIX / 16;
@@ -250,17 +243,18 @@ __global__ __launch_bounds__(512, 2) void conv_resident_kernel(ResArgs a) {
 #pragma unroll 1
         for (int k = 0; k < a.nconv; ++k) run_conv(a.conv[k], k + 1 < a.nconv, k == 0);
     }
-#if MIL_RES_WARM
     asm volatile("" :: "v"(sink));
-#endif
+}
+
+// MIL_RES_GRID_CAP (tests): fewer workgroups than image groups, so that a workgroup walks several groups — the persistent
+// loop (re-copy behind a barrier, partial last group) otherwise needs more than 2048 images to run at all
+static int mil_res_grid_cap(int grid) {
+    const char* e = mil_test_knob("MIL_RES_GRID_CAP");
+    const int cap = e ? atoi(e) : 0;
+    return (cap > 0 && grid > cap) ? cap : grid;
 }
 
 #include "conv_resident_x3.cuh"
-
-static bool mil_resident_enabled() {
-    static const bool v = [] { const char* e = mil_ab_env("MIL_RESIDENT"); return !(e && e[0] == '0'); }();
-    return v;
-}
 
 template <int C, int S, int IMGS>
 static int launch_resident(ResArgs a, hipStream_t st) {
@@ -272,12 +266,7 @@ static int launch_resident(ResArgs a, hipStream_t st) {
     // one workgroup per CU is resident (137-138 KB of LDS): groups beyond that are walked by the same workgroups
     int grid = mil_num_cus();
     if (grid > a.ngroups) grid = a.ngroups;
-    {   // MIL_RES_GRID_CAP (tests): fewer workgroups than image groups, so that a workgroup walks several groups — the
-        // persistent loop (re-copy behind a barrier, partial last group) otherwise needs more than 2048 images to run at all
-        const char* e = getenv("MIL_RES_GRID_CAP");
-        const int cap = e ? atoi(e) : 0;
-        if (cap > 0 && grid > cap) grid = cap;
-    }
+    grid = mil_res_grid_cap(grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G::TILE, st, a);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
@@ -296,10 +285,10 @@ static int resident_dispatch(ResArgs a, int cp, int H, int W, hipStream_t st) {
 }
 
 // One conv: the contract of mil_conv_igemm for (C -> C, 3x3, stride 1, pad 1, bf16) on the shapes above.  Returns
-// MIL_ERR_UNSUPPORTED for any other shape (or MIL_RESIDENT=0): the caller runs the generic kernels.
+// MIL_ERR_UNSUPPORTED for any other shape: the caller runs the generic kernels.
 int mil_resident_conv(const void* x, const void* wpack, const float* bias_pad, const void* res, const void* act, void* y, int n_img,
                       int H, int W, int cp, int apply_lrelu, float slope, hipStream_t st) {
-    if (!mil_resident_enabled() || n_img <= 0 || slope < 0.f || slope >= 1.f) return MIL_ERR_UNSUPPORTED;
+    if (n_img <= 0 || slope < 0.f || slope >= 1.f) return MIL_ERR_UNSUPPORTED;
     // one conv at a time only where it wins: 80 channels (19-22 us against 29.5); on the 64-channel 16x16 maps the filter-resident
     // kernel is as fast (51-58 us against 53-62: three images per workgroup are 2.7 rounds of copy-then-compute without a
     // prefetch) and only the two-conv form pays (91 us against 2 x 52)
@@ -314,7 +303,7 @@ int mil_resident_conv(const void* x, const void* wpack, const float* bias_pad, c
 // The same for MIL_DT_F32S (fp32 tensors, split products): 80 channels on 8x8 maps and 64 channels on 16x16 maps.
 int mil_resident_conv_x3(const void* x, const void* wpack, const float* bias_pad, const void* res, const void* act, void* y, int n_img,
                          int H, int W, int cp, int apply_lrelu, float slope, hipStream_t st) {
-    if (!mil_resident_enabled() || n_img <= 0 || slope < 0.f || slope >= 1.f) return MIL_ERR_UNSUPPORTED;
+    if (n_img <= 0 || slope < 0.f || slope >= 1.f) return MIL_ERR_UNSUPPORTED;
     ResArgsX3 a{};
     a.x = (const float*)x; a.n_img = n_img; a.slope = slope; a.nconv = 1;
     a.conv[0].w = (const char*)wpack; a.conv[0].bias = bias_pad; a.conv[0].res = (const float*)res; a.conv[0].act = (const float*)act;
@@ -332,7 +321,7 @@ extern "C" int mil_conv_chain(const void* x, const MilChainConv* convs, int ncon
                               int dtype, void* stream) {
     if (!x || !convs || nconv < 1 || nconv > MIL_CHAIN_MAX || n_img < 0) return MIL_ERR_ARG;
     for (int k = 0; k < nconv; ++k) if (!convs[k].wpack || !convs[k].out) return MIL_ERR_ARG;
-    if ((dtype != MIL_DT_BF16 && dtype != MIL_DT_F32S) || slope < 0.f || slope >= 1.f || !mil_resident_enabled()) return MIL_ERR_UNSUPPORTED;
+    if ((dtype != MIL_DT_BF16 && dtype != MIL_DT_F32S) || slope < 0.f || slope >= 1.f) return MIL_ERR_UNSUPPORTED;
     if (n_img == 0) return MIL_OK;
     if (dtype == MIL_DT_F32S) {
         ResArgsX3 b{};

@@ -13,9 +13,7 @@
 // fp32 piece, so the epilogue needs no lane exchange: residual / mask operands are loaded and the output is stored 16 bytes
 // per (row tile, column tile) and lane.
 #pragma once
-#ifndef MIL_RESX3_BD
-#define MIL_RESX3_BD 2
-#endif
+constexpr int MIL_RESX3_BD = 2;
 
 struct ResConvX3 {
     const char* w;          // packed MIL_DT_F32S fragments [KSTEPS][NT][64][32 B] (MIL_PACK_FWD or MIL_PACK_DGRAD)
@@ -262,11 +260,7 @@ static int launch_resident_x3(ResArgsX3 a, hipStream_t st) {
     a.ngroups = (a.n_img + IMGS - 1) / IMGS;
     int grid = mil_num_cus();                  // one workgroup per CU is resident (93-141 KB of LDS)
     if (grid > a.ngroups) grid = a.ngroups;
-    {
-        const char* e = getenv("MIL_RES_GRID_CAP");        // tests: fewer workgroups than image groups (see launch_resident)
-        const int cap = e ? atoi(e) : 0;
-        if (cap > 0 && grid > cap) grid = cap;
-    }
+    grid = mil_res_grid_cap(grid);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G::TILE, st, a);
     MIL_CHECK_LAUNCH();
     return MIL_OK;

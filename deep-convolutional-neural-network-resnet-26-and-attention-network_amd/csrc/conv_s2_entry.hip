@@ -102,36 +102,9 @@ __global__ __launch_bounds__(256, CINP <= 24 ? 2 : 1) void conv_s2_entry_kernel(
         for (int m = 0; m < MTW; ++m)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) { acc1[m][nt] = bias_r[nt]; acc2[m][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-#ifndef MIL_S2_ENTRY_NO_PIPE
         // both GEMMs as flattened software pipelines with fragments read two steps ahead (mil_conv_ring, pf_common.cuh)
         mil_conv_ring<NT, MTW, K1, 2>(acc1, ldsW, lane, [&](int sl, int m) { return ldsA + pixbase[m] + toff[sl]; });
         mil_conv_ring<NT, MTW, K2, 2>(acc2, ldsW + K1 * NT * 64 * 16, lane, [&](int sl, int m) { return ldsA + pixbase[m] + toff2[sl]; });
-#else
-#pragma unroll
-        for (int sl = 0; sl < K1; ++sl) {
-            Frag8<BF16> wf[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wf[nt] = lds_frag<BF16>(ldsW + ((sl * NT + nt) * 64 + lane) * 16);
-#pragma unroll
-            for (int m = 0; m < MTW; ++m) {
-                const Frag8<BF16> xf = lds_frag<BF16>(ldsA + pixbase[m] + toff[sl]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc1[m][nt] = mma8(wf[nt], xf, acc1[m][nt]);
-            }
-        }
-#pragma unroll
-        for (int sl = 0; sl < K2; ++sl) {
-            Frag8<BF16> wf[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wf[nt] = lds_frag<BF16>(ldsW + (((K1 + sl) * NT + nt) * 64 + lane) * 16);
-#pragma unroll
-            for (int m = 0; m < MTW; ++m) {
-                const Frag8<BF16> xf = lds_frag<BF16>(ldsA + pixbase[m] + toff2[sl]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc2[m][nt] = mma8(wf[nt], xf, acc2[m][nt]);
-            }
-        }
-#endif
         const int obase = ((o.img0 * g.Ho + o.oy0) * g.Wo + o.ox0) * (COUTP * 2);
         const bool ok = (o_pos >> 20) < g.n_img - o.img0 && ((o_pos >> 10) & 1023) < g.Ho - o.oy0 && (o_pos & 1023) < g.Wo - o.ox0;
         const unsigned ooff = ok ? (unsigned)(obase + o_rel) : MIL_OOB;

@@ -10,9 +10,6 @@
 // pixel = one 16-byte fp32 piece: out = mask( lrelu?( acc + bias? + res? ) ), the contract of mil_conv_igemm.
 #pragma once
 #include "stamp.cuh"
-#ifndef MIL_STREAM_FULL_EPI
-#define MIL_STREAM_FULL_EPI 0
-#endif
 
 struct StreamX3Args {
     const float* x;         // [n,H,W,C]
@@ -122,10 +119,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_x3_kernel(StreamX3Args a, 
             // the (k-step, row tile) loop flattened: pixel fragments one row-tile step ahead, the filter
             // fragments of k-step sl+1 requested from L1/L2 at the start of k-step sl (four row tiles = 36 MFMAs to land)
             constexpr int TOT = KSTEPS * MTW, LA = 1, R = LA + 1;      // one row-tile step (9 MFMAs) covers an LDS read; two spill
-#ifndef MIL_STREAM_WD
-#define MIL_STREAM_WD 1
-#endif
-            constexpr int WD = MIL_STREAM_WD, WR = WD + 1;             // filter fragments: k-steps ahead / ring slots
+            constexpr int WD = 1, WR = WD + 1;             // filter fragments: k-steps ahead / ring slots
             Frag8<F32S> wq[WR][NT], ring[R];
             // The last column tile of a 40-channel filter holds channels 32-39: rows 8-15 idle (zero weights).  Lanes of rows 8-15 read
             // the LO half of row r-8 instead, so ONE fragment F = [w_hi ; w_lo] serves both planes — F x x_hi and F x x_lo, two MFMAs
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_x3_kernel(StreamX3Args a, 
         f32x4_t bias_r[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) bias_r[nt] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (unsigned)(nt * 64 + gq * 16), 0, 0));      // no bias: zeros
-        constexpr int MH = (RES && ACT && !MIL_STREAM_FULL_EPI) ? MTW / 2 : MTW;             // both operands: 96 registers beside the halo pieces do not fit -> two halves
+        constexpr int MH = (RES && ACT) ? MTW / 2 : MTW;             // both operands: 96 registers beside the halo pieces do not fit -> two halves
         u32x4_t rr[RES ? MH : 1][NT], ra[ACT ? MH : 1][NT];
         auto epi_off = [&](int m, int nt) {
             return (m < ylim && xok && nt * 16 + gq * 4 < C) ? (unsigned)(obase + o_rel + m * W * (C * 4) + nt * 64) : MIL_OOB;

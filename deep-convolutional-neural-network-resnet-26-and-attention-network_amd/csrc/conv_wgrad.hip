@@ -45,39 +45,20 @@ __device__ __forceinline__ bf16x8_t tr_pair(const char* p0, const char* p1) {
 // dWp[ci][co] = sum_q x[2q][ci] * dz2[q][co] has the 3x3 conv's CENTRE-TAP rows as its A operand, so the row tiles that
 // hold those rows get a second accumulator set fed by a second dz tile — the block input is read once for both filters
 // instead of once per weight-gradient launch.  Its rows are appended to the slab behind the bias tile.
-// which instantiations take the explicit one-step-ahead operand prefetch (second operand register set): the persistent
-// bf16 forms below 64 input channels; the 64/80-channel forms sit at 232-256 VGPRs already
-#ifndef MIL_WGRAD_X3_WIDE_PF
-#define MIL_WGRAD_X3_WIDE_PF 1      // split precision, 64 channels: register prefetch of the next 128-pixel tile (80 channels: 26 VGPRs spilled)
-#endif
-#ifndef MIL_WGRAD_X3_HALF40
-#define MIL_WGRAD_X3_HALF40 1       // split precision, 40 -> 40 channels: 128-pixel tiles on TWO 4-wave workgroups per CU
-#endif
 // Split precision, 3x3 stride-1 40 -> 40 channels: 128-pixel tiles (58 KB of LDS) on 4-wave workgroups, two per CU, instead of
 // 256-pixel tiles on one 8-wave workgroup (123 KB): the phase stamps had 45 % of a tile outside the MFMA loop (request burst,
 // commit, barriers) with every wave of the CU in the same phase; two independent workgroups run those phases under each
 // other's MFMAs.
 __host__ __device__ constexpr bool mil_wgrad_x3_half(bool split, int ks, int cinp, int nt, int msplit, bool proj) {
-    return MIL_WGRAD_X3_HALF40 && split && ks == 3 && cinp == 40 && nt == 3 && msplit == 1 && !proj;
+    return split && ks == 3 && cinp == 40 && nt == 3 && msplit == 1 && !proj;
 }
 __host__ __device__ constexpr int mil_wgrad_halo_max(int cinp, bool proj, bool split = false, bool half = false) {
     if ((split && cinp >= 64) || half) return 200;  // 128-pixel tiles: 18x10 pixels, or two 10x10 images
-#ifdef MIL_WGRAD_PAIR24_64PX
-    return 400;
-#else
     return (proj && cinp <= 24) ? 576 : 400;
-#endif
 }
 __host__ __device__ constexpr int mil_wgrad_tile_max(int cinp, bool split, bool half = false) { return ((split && cinp >= 64) || half) ? 128 : 256; }
-#ifdef MIL_WGRAD_NO_PIPE
-#define MIL_WGRAD_PIPE(BF, PF, CINP, NW, PROJ) false
-#else
-#define MIL_WGRAD_PIPE(BF, PF, CINP, NW, PROJ) ((BF) && (PF) && (CINP) < 64)
-#endif
+constexpr int MIL_WGRAD_X3_WAVES = 2;        // split precision, 8-wave workgroups: waves per SIMD the register budget is held to (4 = 128 VGPRs spilled 22)
 template <typename T, int KS, int CINP, int NT, int MSPLIT, bool PF, int NW = 4, bool PROJ = false>
-#ifndef MIL_WGRAD_X3_WAVES
-#define MIL_WGRAD_X3_WAVES 2        // split precision, 8-wave workgroups: waves per SIMD the register budget is held to (4 = 128 VGPRs spilled 22)
-#endif
 __global__ __launch_bounds__(64 * NW, NW == 8 ? ((T::SPLIT && CINP <= 24 && NT <= 2) ? MIL_WGRAD_X3_WAVES : 2) : ((PF && CINP > 40) ? 1 : ((PF && T::SPLIT) ? 2 : 0))) void wgrad_kernel(WgradArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MIL_POISON(smem);
@@ -92,15 +73,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((T::SPLIT && CINP <= 24 && NT <
     constexpr int NTHR = 64 * NW;
     constexpr int MW = (MT_S + NW - 1) / NW;    // tiles per wave
     constexpr int PM0 = 2 * CG, PM1 = (5 * CG - 1) / 2, PMN = PROJ ? PM1 - PM0 + 1 : 0;    // row tiles holding centre-tap rows
-    constexpr bool WPIPE = MIL_WGRAD_PIPE(T::DT == MIL_DT_BF16, PF, CINP, NW, PROJ);
+    // the explicit one-step-ahead operand prefetch (second operand register set): the persistent bf16 forms below 64 input
+    // channels; the 64/80-channel forms sit at 232-256 VGPRs already
+    constexpr bool WPIPE = T::DT == MIL_DT_BF16 && PF && CINP < 64;
     // Split precision, 24 or 40 output channels: the last column tile holds eight real columns, columns 8-15 idle.  The lanes that
     // read the pieces of columns 8-15 (p >= 2) read the LO plane's pieces of the tile's eight channels instead, so x_lo * [dz_hi |
     // dz_lo] and x_hi * [dz_hi | dz_lo] are two MFMAs for what took three (columns 8-15 also collect x_lo*dz_lo, the 2^-18 term the
     // three-product form drops); they are added onto columns 0-7 when the slab is written.
-#ifndef MIL_WGRAD_ZFOLD
-#define MIL_WGRAD_ZFOLD 1
-#endif
-    constexpr bool ZFOLD = MIL_WGRAD_ZFOLD && T::SPLIT && (COUTP % 16) == 8;
+    // (measured: same-box 17.92 -> 17.78 ms per step against three MFMAs on that tile)
+    constexpr bool ZFOLD = T::SPLIT && (COUTP % 16) == 8;
     constexpr int ZFOLD_D = COUTP * 2 - 16;
     const ConvGeom& g = a.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -486,7 +467,7 @@ static int plan_wgrad(ConvGeom& g, WgradPlan& pl, int* lds_z_off, bool proj = fa
     constexpr int RG = KS * KS * (CINP / 8);
     constexpr int MT = (RG + 1) / 2;
     // 256-px tiles when the halo fits comfortably, else 64-px tiles (stride-2 layers, f32 wide layers)
-    constexpr bool PF_OK = T::TR16 && (!T::SPLIT || CINP < 64 || (MIL_WGRAD_X3_WIDE_PF && (CINP == 64 || (CINP == 80 && MSPLIT >= 3))));            // bf16, and fp32 with split-precision products: the register-prefetch pipeline
+    constexpr bool PF_OK = T::TR16 && (!T::SPLIT || CINP < 64 || (CINP == 64 || (CINP == 80 && MSPLIT >= 3)));            // bf16, and fp32 with split-precision products: the register-prefetch pipeline
     constexpr bool HALF = mil_wgrad_x3_half(T::SPLIT, KS, CINP, NT, MSPLIT, false);
     const bool half = HALF && !proj;
     const int hmax = mil_wgrad_halo_max(CINP, proj, T::SPLIT, half);
@@ -532,7 +513,7 @@ static int run_wgrad(const void* x, const void* dz, float* dw, float* db, void* 
     a.lds_z2_off = lds_z_off + (1 << pl.tile_px_log2) * mil_pix_pitch(mil_nt_to_cp(NT), T::ESZ);
     // register-prefetch pipeline for the bf16 path when the halo is small enough for its register budget
     // (split precision at >= 64 channels: the doubled prefetch registers spill — 130-250 VGPRs — so those keep the plain loader)
-    constexpr bool PF_OK = T::TR16 && (!T::SPLIT || CINP < 64 || (MIL_WGRAD_X3_WIDE_PF && (CINP == 64 || (CINP == 80 && MSPLIT >= 3))));
+    constexpr bool PF_OK = T::TR16 && (!T::SPLIT || CINP < 64 || (CINP == 64 || (CINP == 80 && MSPLIT >= 3)));
     const size_t xb_total = (size_t)g.n_img * g.H * g.W * CINP * T::ESZ;
     const size_t zb_total = (size_t)g.n_img * g.Ho * g.Wo * mil_nt_to_cp(NT) * T::ESZ;
     // buffer descriptors address < 2 GiB: a larger tensor is walked in image chunks, one launch and one set of slabs per chunk
@@ -641,9 +622,6 @@ static int dispatch_wgrad_pair(const void* x, const void* dz1, const void* dz2, 
     if (cinp == 40 && coutp == 64) MIL_WGP(40, 4, 1);
     // (64 -> 80: NOT paired.  The paired instantiation spilled 59 VGPRs at its 256-register cap and measured 124 us per launch
     // against 56 + 25 us for the two separate weight-gradient launches (round 4, 256x256 tiles; 306 vs 138 + 54 us at 300x300).)
-#ifdef MIL_PAIR64
-    if (cinp == 64 && coutp == 80) MIL_WGP(64, 5, 2);
-#endif
 #undef MIL_WGP
     return MIL_ERR_UNSUPPORTED;
     }
@@ -717,13 +695,8 @@ struct StemBwdArgs {
     unsigned long long* stamp;      // MIL_STAMP diagnostic build only
 };
 
-#ifndef MIL_STEM_BWD_WAVES
-#define MIL_STEM_BWD_WAVES 2       // measured (us per launch, 2048 tiles): no prefetch 1285 @2 waves/SIMD, 1083 @3 (30 spilled VGPRs), 2102 @4;
-                                   // one-step-ahead prefetch (MIL_STEM_BWD_PIPE) 1025 @2 (193 VGPRs, no spill), 1237 @3 (spills)
-#endif
-#ifndef MIL_STEM_BWD_PIPE
-#define MIL_STEM_BWD_PIPE 1
-#endif
+constexpr int MIL_STEM_BWD_WAVES = 2;  // measured (us per launch, 2048 tiles): no prefetch 1285 @2 waves/SIMD, 1083 @3 (30 spilled VGPRs), 2102 @4;
+                                        // one-step-ahead prefetch 1025 @2 (193 VGPRs, no spill), 1237 @3 (spills)
 // X3 (MIL_DT_F32S, FROM_X only): fp32 pooled gradient; the s2d tile and the dz tile hold hi and lo bf16 planes ([hi | lo] per
 // pixel record), the weight-gradient GEMM takes x_lo*dz_hi + x_hi*dz_lo + x_hi*dz_hi, the bias sums are the un-rounded fp32 values.
 // NPW = pooled-window pieces per thread: 1 when the tile's windows x 3 pieces fit 256 threads (16 x 16 tiles of one image: 81
@@ -930,7 +903,6 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
         cur = nxt; nxt.advance();
         MIL_STAMP_MARK(3)
 
-#ifndef MIL_EXP_STEM_NO_GATHER
         // ---- dz tile = lrelu'(stem) * maxpool^T(g): gather over the 4 windows that cover a 2x2 block --------
         // A window's gradient goes to exactly one pixel (its recorded winner tap); per (window, channel) the tap and
         // the masked gradient are decoded once, then tested against the (at most 4) taps this block's pixels have in
@@ -991,18 +963,15 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
                     }
                 }
         }
-#endif
         MIL_STAMP_MARK(4)
         __syncthreads();
         MIL_STAMP_MARK(5)
 
         // ---- weight gradient: rows (tap, s2d channel), cols stem channel, K = the tile's 256 pixels ---------
-#ifndef MIL_EXP_STEM_NO_MFMA
-        // One 32-pixel k-step ahead (MIL_STEM_BWD_PIPE): the transposed reads of step k+1 are issued before the MFMAs of
+        // One 32-pixel k-step ahead: the transposed reads of step k+1 are issued before the MFMAs of
         // step k and scheduling fences keep that order.  Left to itself hipcc reads each row tile's fragment right in
         // front of its two MFMAs behind an lgkmcnt(0): five LDS round trips per k-step, forty per tile — the whole tile
         // time of this kernel.  Every wave owns MW = 3 row tiles that all exist (MT = 12), so there is no validity branch.
-#if MIL_STEM_BWD_PIPE
         {
             static_assert(MT == 4 * MW, "every wave owns MW full row tiles");
             constexpr int NL2 = X3 ? 2 : 1;                  // operand planes: hi (+ lo)
@@ -1052,28 +1021,6 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
                 }
             }
         }
-#else
-#pragma unroll 2
-        for (int k32 = 0; k32 < 256; k32 += 32) {
-            const int kb = mil_pix_base<PIXB>(g, k32, 1);
-            const int pb0 = kb + wpl0, pb1 = kb + wpl1;
-            const char* z0 = ldsZ + (k32 + 8 * gq + q4) * PIXZ + p4 * 8;
-            const char* z1 = z0 + 4 * PIXZ;
-            bf16x8_t bf[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bf[nt] = mil_tr_pair(z0 + nt * 32, z1 + nt * 32);
-#pragma unroll
-            for (int i = 0; i < MW; ++i) {
-                if (mvalid[i]) {
-                    const bf16x8_t af = mil_tr_pair(ldsX + pb0 + toff[i], ldsX + pb1 + toff[i]);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[nt], acc[i][nt], 0, 0, 0);
-                }
-            }
-        }
-#endif
-#endif      // MIL_EXP_STEM_NO_MFMA
         MIL_STAMP_MARK(6)
     }
     MIL_STAMP_STORE(a.stamp, 4)
@@ -1091,7 +1038,7 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float v = acc[i][nt][e];
-                if (X3 && nt == 1 && MIL_STEM_BWD_PIPE) {      // folded column tile: columns 4-7 (the lo products) onto columns 0-3
+                if (X3 && nt == 1) {      // folded column tile: columns 4-7 (the lo products) onto columns 0-3
                     const float up = __shfl_down(v, 4, 16);
                     v = col < 4 ? v + up : 0.f;
                 }
@@ -1130,10 +1077,8 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
     ConvGeom& g = a.g;
     g.n_img = n; g.H = H2; g.W = W2; g.Ho = H2; g.Wo = W2; g.ks = 4; g.stride = 1; g.pad = 2; g.zins = 0;
     mil_geom_tiles(g, 8);
-#ifndef MIL_STEM_BWD_WIDE
-#define MIL_STEM_BWD_WIDE 0           // 1: 32 x 8 tiles instead of 16 x 16 where the map allows (35 x 11 halo: 280-byte row segments instead of 152)
-#endif
-    if (MIL_STEM_BWD_WIDE && g.tw_log2 == 4 && g.th_log2 == 4 && g.ti_log2 == 0 && W2 >= 32) mil_geom_set(g, 5, 3, 0);
+    // (32 x 8 tiles instead of 16 x 16 — 280-byte instead of 152-byte row segments of the colour planes — measured 784 -> 773 us
+    // bf16, 1307 -> 1301 us split: inside the run-to-run spread)
     a.Hp = (H2 - 1) / 2 + 1; a.Wp = (W2 - 1) / 2 + 1;
     a.H = 2 * H2; a.W = 2 * W2;
     const int halo_px = (g.hh * g.hw) << g.ti_log2;
@@ -1150,11 +1095,7 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
     const int lds = xb + zb + gb + ib + 48;                 // + dump slot (FROM_X: second pixel of a pair behind an odd-width halo; hi + lo)
     const int groups = (chunk + (1 << g.ti_log2) - 1) >> g.ti_log2;
     const int ntiles_max = groups * g.tiles_y * g.tiles_x;
-#ifdef MIL_EXP_STEM_BWD_NPW2                                // A/B build: always two window slots per thread (the form until round 5)
-    const bool one = false;
-#else
     const bool one = nwin * 3 <= 256;                       // one window piece per thread
-#endif
     auto kern = x3 ? (one ? stem_bwd_fused_kernel<true, true, 1> : stem_bwd_fused_kernel<true, true, 2>)
               : from_x ? (one ? stem_bwd_fused_kernel<true, false, 1> : stem_bwd_fused_kernel<true, false, 2>)
                        : (one ? stem_bwd_fused_kernel<false, false, 1> : stem_bwd_fused_kernel<false, false, 2>);

@@ -360,12 +360,6 @@ extern "C" int mil_wide_pack_weights(const float* w, void* wpack, int cout, int 
     return MIL_OK;
 }
 
-#include <cstdlib>
-static bool mil_wide_pf_enabled() {          // MIL_WIDE_PF=0: the plain kernel everywhere (A/B runs)
-    static const bool v = [] { const char* e = mil_ab_env("MIL_WIDE_PF"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 template <typename T>
 static int launch_wide(WideArgs<T> a, hipStream_t st) {
     constexpr int ESZ = T::ESZ;
@@ -389,7 +383,7 @@ static int launch_wide(WideArgs<T> a, hipStream_t st) {
         // resolution grid) whose halo fits the register prefetch: the pipelined form
         const int halo_px = (a.g.hh * a.g.hw) << a.g.ti_log2;
         const size_t xb = (size_t)a.g.n_img * a.g.H * a.g.W * a.cin * 2;
-        if (mil_wide_pf_enabled() && a.g.stride == 1 && halo_px <= 256 && xb < ((size_t)1 << 31) && (a.g.ks == 3 || a.g.ks == 1)) {
+        if (a.g.stride == 1 && halo_px <= 256 && xb < ((size_t)1 << 31) && (a.g.ks == 3 || a.g.ks == 1)) {
             const int a_pf = a_bytes + 16;                    // + dump slot for the unused halo piece slots
             int lds_pf = a_pf + w_bytes;
             if (lds_pf < 128 * WIDE_NB * 4) lds_pf = 128 * WIDE_NB * 4;
@@ -731,9 +725,8 @@ static int run_wide_wgrad(const void* x, const void* dz, float* dw, void* ws, si
     const int ntiles = g.n_groups * g.tiles_y * g.tiles_x;
     const int npairs = (cout / WIDE_NB) * (cin / WIDE_CK);
     // one fp32 slab per workgroup: 512 workgroups (two per CU) keep the slab write + fixed-order reduce at 37 MB per launch —
-    // the 2048 of earlier rounds moved 151 MB for a 9 MB gradient (MIL_WIDE_WGRAD_WGS: A/B runs)
-    static const int wg_target = [] { const char* e = mil_ab_env("MIL_WIDE_WGRAD_WGS"); return e ? atoi(e) : 512; }();
-    int gx = wg_target / npairs;
+    // the 2048 of earlier rounds moved 151 MB for a 9 MB gradient
+    int gx = 512 / npairs;
     if (gx < 4) gx = 4;
     if (gx > 64) gx = 64;
     if (gx > ntiles) gx = ntiles;
@@ -748,7 +741,7 @@ static int run_wide_wgrad(const void* x, const void* dz, float* dw, void* ws, si
     if constexpr (T::DT == MIL_DT_BF16) {
         const size_t xbytes = (size_t)g.n_img * g.H * g.W * cin * 2, zbytes = (size_t)g.n_img * g.Ho * g.Wo * cout * 2;
         const int halo_px = (g.hh * g.hw) << g.ti_log2;
-        if (mil_wide_pf_enabled() && g.stride == 1 && halo_px <= 256 && g.hh < 1024 && g.hw < 1024 &&
+        if (g.stride == 1 && halo_px <= 256 && g.hh < 1024 && g.hw < 1024 &&
             xbytes < ((size_t)1 << 31) && zbytes < ((size_t)1 << 31)) {
             a.lds_z_off = xb + 16;                              // + dump slot for the unused halo piece slots
             auto kpf = wide_wgrad_pf_kernel<KS>;
@@ -778,10 +771,6 @@ static int run_wide_wgrad(const void* x, const void* dz, float* dw, void* ws, si
 // conv_gather.hip: the gather form of the weight gradient (bf16; any stride / 1x1)
 int mil_gwgrad(const void* x, const void* dz, float* dw, void* ws, size_t ws_bytes, int n_img, int H, int W, int cin, int Ho, int Wo,
                int cout, int ks, int stride, int pad, int accumulate, bool query, size_t* need, hipStream_t st);
-static int mil_gwgrad_mode() {           // MIL_GWGRAD: 0 = never, 1 = stride-2 and 1x1 launches (default), 2 = every eligible launch
-    static const int v = [] { const char* e = mil_ab_env("MIL_GWGRAD"); return e ? atoi(e) : 1; }();
-    return v;
-}
 
 static int wide_wgrad_entry(const void* x, const void* dz, float* dw, void* ws, size_t ws_bytes, int n_img, int H, int W, int cin,
                             int Ho, int Wo, int cout, int ks, int stride, int pad, int accumulate, int dtype, bool query,
@@ -791,7 +780,7 @@ static int wide_wgrad_entry(const void* x, const void* dz, float* dw, void* ws, 
     ConvGeom g{};
     g.n_img = n_img; g.H = H; g.W = W; g.Ho = Ho; g.Wo = Wo; g.ks = ks; g.stride = stride; g.pad = pad; g.zins = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MIL_DT_BF16 && (mil_gwgrad_mode() == 2 || (mil_gwgrad_mode() == 1 && (stride == 2 || ks == 1)))) {
+    if (dtype == MIL_DT_BF16 && (stride == 2 || ks == 1)) {
         // the stride-2 3x3 and the 1x1 gradients have no pipelined form here (wide_wgrad_pf_kernel is stride 1): gather form
         const int rc = mil_gwgrad(x, dz, dw, ws, ws_bytes, n_img, H, W, cin, Ho, Wo, cout, ks, stride, pad, accumulate, query, need, st);
         if (rc != MIL_ERR_UNSUPPORTED) return rc;

@@ -81,9 +81,7 @@ __global__ __launch_bounds__(1024) void head_colstats_kernel(const float* __rest
 // registers; an instance's normalised / dropped-out feature rows are staged in the wave's LDS strip and read back as
 // broadcasts.  Every dot product runs in the same order as the one-thread-per-instance form it replaces (which spent 44 us
 // on 16 workgroups: 6.4 k serial FMAs per thread, each with its weight read from LDS): same bits, ~256 waves.
-#ifndef HSL
-#define HSL 8
-#endif
+constexpr int HSL = 8;
 __global__ __launch_bounds__(256) void head_inst_fwd_kernel(const float* __restrict__ H, const int* __restrict__ inst_bag,
                                                             const float* __restrict__ stats, const uint8_t* __restrict__ keep,
                                                             HeadWeights w, float* __restrict__ t_out, float* __restrict__ v_out,

@@ -288,9 +288,8 @@ __host__ inline int mil_num_cus() {
 
 // How many images of `bytes_per_img` bytes fit under the 2 GiB buffer limit.
 // (MIL_BUFFER_LIMIT_BYTES lowers the limit: the tests use it to drive small launches through the chunked paths)
-#include <cstdlib>
 __host__ inline size_t mil_buffer_limit() {
-    const char* e = getenv("MIL_BUFFER_LIMIT_BYTES");           // read per call (launch path, ~100 ns): a test can change it
+    const char* e = mil_test_knob("MIL_BUFFER_LIMIT_BYTES");
     const size_t v = e ? (size_t)atoll(e) : 0;
     return (v >= 65536 && v < ((size_t)1 << 31)) ? v : ((size_t)1 << 31) - 4096;
 }

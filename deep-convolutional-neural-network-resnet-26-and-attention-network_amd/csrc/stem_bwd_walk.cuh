@@ -290,10 +290,10 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_walk_kernel(StemBwdArgs a) {
 }
 
 // bf16, from the fp32 tiles, 256-pixel-wide tiles, whole images filling the resident workgroups evenly (cost: rounds x steps x
-// time per step against rounds x tiles x time per tile); MIL_STEM_WALK = 0 / 1 forces either form (TEST knob, read per call).
+// time per step against rounds x tiles x time per tile); MIL_STEM_WALK = 0 / 1 forces either form (TEST knob).
 static bool mil_stem_walk_wanted_bwd(int n_img, int H2, int W2, bool from_x, bool bf16, int tiles_per_img, int grid_cap) {
     if (!from_x || !bf16 || W2 != 128 || (H2 & 1)) return false;
-    const char* e = getenv("MIL_STEM_WALK");
+    const char* e = mil_test_knob("MIL_STEM_WALK");
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
     // measured (windows decoded once in both forms): 6.3 k cycles per 16 x 16 tile, 6.0 k per two-row step
     const long cost_tile = ((long)n_img * tiles_per_img + 2 * grid_cap - 1) / (2 * grid_cap) * 2 * 63;     // the tiled form runs two rounds of the resident set

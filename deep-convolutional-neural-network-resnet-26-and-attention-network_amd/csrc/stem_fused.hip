@@ -16,10 +16,6 @@
 #include "stamp.cuh"
 #include <type_traits>
 
-#ifndef MIL_STEM_FWD_LOOKAHEAD
-#define MIL_STEM_FWD_LOOKAHEAD 2      // pixel fragments read this many (k-step, row tile) steps ahead of their MFMAs; 0 = compiler order
-#endif
-
 struct StemFwdArgs {
     const float* x;            // [n,3,H,W] (FROM_XS: null)
     const __bf16* xs_in;       // FROM_XS: the input already as bf16 space-to-depth NHWC [n,H2,W2,16] (mil_tile_preprocess_s2d)
@@ -33,54 +29,39 @@ struct StemFwdArgs {
     unsigned long long* stamp;      // MIL_STAMP diagnostic build only
 };
 
-// Tile = PH x 16 pooled pixels.  PH = 8 (bf16): 17x33 stem pixels <- 20x38 s2d pixels.  PH = 4 (split precision): 9x33 <- 12x38,
-// which, with the filter streamed from L1/L2 instead of staged, is 70 KB of LDS: TWO 4-wave workgroups per CU, each running its
-// convert / store / pool phases under the other's MFMAs (the 8x16 form was one 8-wave workgroup per CU on 156 KB, every wave of
-// the CU in the same phase: gemm 39 % of a tile in the phase stamps).  Measured: 2.00 -> 1.89 ms per launch (2048 tiles of 256x256).
-#ifndef MIL_STEM_X3_PH
-#define MIL_STEM_X3_PH 4
-#endif
-__host__ __device__ constexpr int sf_ph(bool x3) { return x3 ? MIL_STEM_X3_PH : 8; }
-__host__ __device__ constexpr bool sf_wstream(bool x3) { return x3 && MIL_STEM_X3_PH < 8; }
+// Tile = 8 x 16 pooled pixels: 17x33 stem pixels <- 20x38 s2d pixels.
+constexpr int SF_PH = 8;
 constexpr int SF_SW = 33;                           // stem tile width
 constexpr int SF_XW = 38, SF_NPAIR = 19;            // s2d tile width; a "pair" = 2 s2d pixels = 4 input columns
 __host__ __device__ constexpr int sf_sh(int ph) { return 2 * ph + 1; }      // stem tile rows
 __host__ __device__ constexpr int sf_xh(int ph) { return 2 * ph + 4; }      // s2d tile rows
 // s2d pixel record in LDS: 16 ch bf16 = 32 B at an odd 16-B slot pitch (48); split precision (X3): [hi 32 B][lo 32 B] at pitch 80
 __host__ __device__ constexpr int sf_xpix(bool x3) { return x3 ? 80 : 48; }
-__host__ __device__ constexpr int sf_xbytes(bool x3) { return sf_xh(sf_ph(x3)) * SF_XW * sf_xpix(x3); }  // 36480 (bf16, 20 rows) / 36480 (split, 12 rows)
+__host__ __device__ constexpr int sf_xbytes() { return sf_xh(SF_PH) * SF_XW * sf_xpix(false); }  // 36480
 __host__ __device__ constexpr int sf_nitem(int ph) { return sf_xh(ph) * SF_NPAIR * 3; }      // (row, pair, colour) load items
 __host__ __device__ constexpr int sf_nstem(int ph) { return sf_sh(ph) * SF_SW; }             // 561 / 297
 __host__ __device__ constexpr int sf_mtiles(int ph) { return (sf_nstem(ph) + 15) / 16; }     // 16-pixel row tiles of the stem tile: 36 / 19
 
-template <int NT, bool X3 = false>
+template <int NT>
 __host__ __device__ constexpr int sf_lds_bytes() {
-    return sf_xbytes(X3) + ((sf_nstem(sf_ph(X3)) * mil_pix_pitch(mil_nt_to_cp(NT), X3 ? 4 : 2) + 15) & ~15) +
-           (sf_wstream(X3) ? 0 : 8 * NT * 64 * (X3 ? 32 : 16)) + 256;   // + dump slot
+    return sf_xbytes() + ((sf_nstem(SF_PH) * mil_pix_pitch(mil_nt_to_cp(NT), 2) + 15) & ~15) + 8 * NT * 64 * 16 + 256;   // + dump slot
 }
 
-// NW = waves per workgroup.  The kernel is VALU-bound (pool compare/select, activation, conversions) and at 4 waves per
-// workgroup its 238 VGPRs leave two waves per SIMD, which keep the vector pipe only half busy; with 8 waves every
-// per-wave quantity halves (5 row tiles, 3 load items, 2 pool items) and four waves per SIMD fit on the same LDS tiles.
-// X3 (MIL_DT_F32S: fp32 tensors, bf16x3 split products): the s2d tile holds hi and lo bf16 planes, every (filter, pixel)
-// fragment pair costs three MFMAs, the stem tile and the pooled output are fp32.  156 KB of LDS: one 8-wave workgroup per CU.
+// bf16 only (X3 = false): the 20-channel stem, and with it every split-precision launch, runs on stem_fwd_pool_kernel /
+// stem_fwd_walk_kernel below.  NW = 4 waves per workgroup: measured (24 channels, bf16) 1120 us with 4 waves at 238 VGPRs,
+// 1428 us with 8 waves squeezed into 128 VGPRs (15 spilled).
 // FROM_XS (bf16 only): the tiles arrive as the bf16 space-to-depth tensor itself — the s2d tile is a plain halo copy in
 // 16-byte pieces (1.07 GB read per 2048 tiles of 256x256 instead of 1.6 GB of fp32 in 304-byte plane segments), everything
 // behind it is the same code on the same LDS bytes: bit-identical pooled map and winner records.
 template <int NT, int NW, bool X3 = false, bool FROM_XS = false>
-__global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 6 ? 3 : 2)) : 1)) void stem_fwd_fused_kernel(StemFwdArgs a) {
-    static_assert(!(X3 && FROM_XS), "the space-to-depth feed is bf16");
-    using T = typename std::conditional<X3, F32S, BF16>::type;
-    constexpr int PH = sf_ph(X3);                             // pooled rows per tile
-    constexpr bool WSTREAM = sf_wstream(X3);                  // filter fragments from L1/L2, not from LDS
-    // the streamed branch of wfrag() is written for the folded split-precision form only (column tile 1 = [wh ; wl]) and for the
-    // pipelined loop (the MIL_STEM_FWD_LOOKAHEAD == 0 loop reads ldsW, which is not staged when the filter streams)
-    static_assert(!WSTREAM || (X3 && NT == 2), "streamed filter fragments: folded split-precision form only");
-    static_assert(!WSTREAM || MIL_STEM_FWD_LOOKAHEAD > 0, "streamed filter fragments need the pipelined MFMA loop");
+__global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kernel(StemFwdArgs a) {
+    static_assert(!X3, "bf16 only");
+    using T = BF16;
+    constexpr int PH = SF_PH;                                 // pooled rows per tile
     constexpr int SF_SH = sf_sh(PH), SF_XH = sf_xh(PH), SF_NITEM = sf_nitem(PH), SF_NSTEM = sf_nstem(PH), SF_MTILES = sf_mtiles(PH);
-    constexpr int SF_XPIX = sf_xpix(X3), SF_XBYTES = sf_xbytes(X3);
-    constexpr int OESZ = X3 ? 4 : 2;                          // bytes per element of the stem tile / pooled output
-    constexpr int FRAGB = X3 ? 32 : 16;
+    constexpr int SF_XPIX = sf_xpix(false), SF_XBYTES = sf_xbytes();
+    constexpr int OESZ = 2;                                   // bytes per element of the stem tile / pooled output
+    constexpr int FRAGB = 16;
     constexpr int COUTP = mil_nt_to_cp(NT);
     constexpr int SPIX = mil_pix_pitch(COUTP, OESZ);
     constexpr int KSTEPS = 8;
@@ -98,12 +79,12 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
     char* ldsW = ldsS + ((SF_NSTEM * SPIX + 15) & ~15);
     // LDS writes of unused slots (the last partial rounds of the tables below) go to a dump area instead of being
     // branched around: a divergent branch per store costs more than the store.
-    const int dump = sf_lds_bytes<NT, X3>() - 256;
+    const int dump = sf_lds_bytes<NT>() - 256;
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, gq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     {
-        if constexpr (!WSTREAM) mil_stage_filter(ldsW, a.w, KSTEPS * NT * 64 * FRAGB, tid, NTHR);
+        mil_stage_filter(ldsW, a.w, KSTEPS * NT * 64 * FRAGB, tid, NTHR);
         for (int i = tid * 16; i < SF_XBYTES; i += NTHR * 16)          // channels 12..15 of every s2d pixel stay zero
             *reinterpret_cast<uint4*>(ldsX + i) = make_uint4(0, 0, 0, 0);
     }
@@ -165,10 +146,6 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int i = 0; i < 4; ++i) bias_r[nt][i] = a.bias ? a.bias[nt * 16 + gq * 4 + i] : 0.f;
-    if constexpr (X3 && NT == 2 && MIL_STEM_FWD_LOOKAHEAD > 0) {      // folded column tile 1: rows 4-15 accumulate w_lo * x_hi of rows 0-3 — they
-#pragma unroll                                                       // start at zero whatever bias_pad[20..] holds (the public C ABI does not promise zeros there)
-        for (int i = 0; i < 4; ++i) bias_r[1][i] = gq == 0 ? bias_r[1][i] : 0.f;
-    }
 
     // ---- tile walk: XCD x (= blockIdx & 7) owns tiles [x*per, (x+1)*per) ---------------------------
     const int G8 = gridDim.x >> 3, per = (a.ntiles + 7) >> 3;
@@ -217,21 +194,12 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
         for (int i = 0; i < SF_NLOAD; ++i) {
             const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
             const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
-            bf16x4_t pa, pb, qa, qb;
-            if constexpr (X3) {
-                mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
-                mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
-            } else {
+            bf16x4_t pa, pb;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
-            }
+            for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
             char* dst = smem + (l_lds[i] & 0x3FFFF);
             *reinterpret_cast<bf16x4_t*>(dst) = pa;
             *reinterpret_cast<bf16x4_t*>(dst + SF_XPIX) = pb;
-            if constexpr (X3) {                                  // lo plane: 32 bytes behind the hi plane of the same pixel
-                *reinterpret_cast<bf16x4_t*>(dst + 32) = qa;
-                *reinterpret_cast<bf16x4_t*>(dst + SF_XPIX + 32) = qb;
-            }
         }
         MIL_STAMP_MARK(0)
         __syncthreads();
@@ -239,7 +207,7 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
         if (tile + G8 < t_end) fetch(tile + G8);
         MIL_STAMP_MARK(2)
         // ---- the tile's own 16x32 s2d pixels go to the xs tensor (when the caller keeps one) ------------
-        if (!X3 && !FROM_XS && a.xs) {
+        if (!FROM_XS && a.xs) {
             const int xbase = ((img * H2 + 16 * ty) * W2 + 32 * tx) * 32;
             const int ylim = H2 - 16 * ty, xlim = W2 - 32 * tx;
 #pragma unroll
@@ -256,39 +224,15 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
         for (int m = 0; m < SF_MT; ++m)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[m][nt] = bias_r[nt];
-#ifdef MIL_EXP_STEMF_NO_CONV
-#elif MIL_STEM_FWD_LOOKAHEAD > 0
         {
             // The (k-step, row tile) loop flattened into one software pipeline: the pixel fragment of step j+LA is read
             // LA steps before the two MFMAs that consume it (a ring of LA+1 fragments), the filter fragments one k-step
             // ahead, and scheduling fences keep that order.  Left alone, hipcc reads each fragment right in front of its
             // MFMA pair behind an lgkmcnt(0): 72 LDS round trips per tile and wave, two thirds of this kernel's time.
-            constexpr int TOT = KSTEPS * SF_MT, LA = MIL_STEM_FWD_LOOKAHEAD, R = LA + 1;
-            constexpr int WD = WSTREAM ? 2 : 1, WR = WD + 1;      // filter fragments: k-steps ahead (streamed: an L2 round trip against 25 MFMAs per k-step) / ring slots
+            constexpr int TOT = KSTEPS * SF_MT, LA = 2, R = LA + 1;
+            constexpr int WD = 1, WR = WD + 1;                    // filter fragments: k-steps ahead / ring slots
             Frag8<T> ring[R], wq[WR][NT];
-            // X3, 20 channels: column tile 1 has four real rows (channels 16-19), so its rows 4-7 carry the LO halves of the same
-            // channels (lanes r = 4..7 read lane r-4's lo half): [wh ; wl] x xh, then wh x xl — two MFMAs instead of three; the
-            // epilogue adds rows 4-7 onto rows 0-3
-            constexpr bool FOLD = X3 && NT == 2;
-            const int w1h = (FOLD && r >= 4 && r < 8) ? (64 + lane - 4) * FRAGB + 16 : (64 + lane) * FRAGB;
-            const __amdgpu_buffer_rsrc_t rs_w = mil_rsrc(a.w, KSTEPS * NT * 64 * FRAGB);
-            auto wfrag = [&](int sl, int nt) {
-                if constexpr (WSTREAM) {             // (FOLD form only) 16 bytes per lane and half, the k-step in the scalar offset
-                    Frag8<T> f;
-                    f.h = __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)(nt == 1 ? w1h : lane * FRAGB), sl * NT * 64 * FRAGB, 0));
-                    f.l = __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)(nt == 1 ? (64 + lane) * FRAGB : lane * FRAGB + 16), sl * NT * 64 * FRAGB, 0));
-                    return f;
-                } else
-                if constexpr (FOLD) {
-                    if (nt == 1) {
-                        Frag8<T> f;
-                        f.h = *reinterpret_cast<const bf16x8_t*>(ldsW + sl * NT * 64 * FRAGB + w1h);
-                        f.l = *reinterpret_cast<const bf16x8_t*>(ldsW + ((sl * NT + 1) * 64 + lane) * FRAGB);      // the hi half: rows 4-15 are zero weights
-                        return f;
-                    }
-                }
-                return lds_frag<T>(ldsW + ((sl * NT + nt) * 64 + lane) * FRAGB);
-            };
+            auto wfrag = [&](int sl, int nt) { return lds_frag<T>(ldsW + ((sl * NT + nt) * 64 + lane) * FRAGB); };
 #pragma unroll
             for (int k = 0; k < WD; ++k)
 #pragma unroll
@@ -308,31 +252,11 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
                     for (int nt = 0; nt < NT; ++nt) wq[(sl + WD) % WR][nt] = wfrag(sl + WD, nt);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (FOLD) {
-                    acc[m][0] = mma8(wq[sl % WR][0], ring[j % R], acc[m][0]);
-                    acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[sl % WR][1].h, ring[j % R].h, acc[m][1], 0, 0, 0);      // [wh ; wl] x xh
-                    acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[sl % WR][1].l, ring[j % R].l, acc[m][1], 0, 0, 0);      // wh x xl
-                } else {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mma8(wq[sl % WR][nt], ring[j % R], acc[m][nt]);
-                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#else
-#pragma unroll
-        for (int sl = 0; sl < KSTEPS; ++sl) {
-            Frag8<T> wf[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wf[nt] = lds_frag<T>(ldsW + ((sl * NT + nt) * 64 + lane) * FRAGB);
-#pragma unroll
-            for (int m = 0; m < SF_MT; ++m) {
-                const Frag8<T> xf = lds_pix_frag<T, 32>(ldsX + pixbase[m] + ((sl >> 1) * SF_XW + 2 * (sl & 1)) * SF_XPIX);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mma8(wf[nt], xf, acc[m][nt]);
-            }
-        }
-#endif
         MIL_STAMP_MARK(3)
         // Stem pixels outside the image are the pool's -inf padding: written as such, so that the pool phase below
         // needs no per-tap bounds tests (only tiles on the image border have any).
@@ -345,42 +269,21 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
                 const int tp = (wave + NW * m) * 16 + r, sy = (tp * 1986) >> 16, sx = tp - sy * SF_SW;      // tp / 33 for tp < 1024
                 inside = (unsigned)(sy0 + sy) < (unsigned)H2 && (unsigned)(sx0 + sx) < (unsigned)W2;
             }
-            if constexpr (X3 && NT == 2 && MIL_STEM_FWD_LOOKAHEAD > 0) {      // column tile 1: rows 4-7 (lane group gq == 1) hold wl*xh of rows 0-3
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float t0 = acc[m][1][i], t1 = t0;
-                    if (i == 0) mil_swap16<true>(t0, t1); else mil_swap16<false>(t0, t1);      // t1 of lane group 0 = group 1's value
-                    acc[m][1][i] = gq == 0 ? acc[m][1][i] + t1 : 0.f;        // channels 20-23 are padding: exact zeros
-                }
-            }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (LAST_PARTIAL && nt == NT - 1 && gq >= 2) continue;        // channels COUTP.. do not exist
-                if constexpr (X3) {
-                    f32x4_t o;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { const float v = acc[m][nt][i]; o[i] = fmaxf(v, v * a.slope); }
-                    u32x4_t ou = __builtin_bit_cast(u32x4_t, o);
-                    if (border) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) ou[i] = inside ? ou[i] : 0xFF800000u;      // -inf
-                    }
-                    *reinterpret_cast<u32x4_t*>(smem + sdst[m] + nt * 64) = ou;
-                } else {
                 bf16x4_t o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { const float v = acc[m][nt][i]; o[i] = (__bf16)fmaxf(v, v * a.slope); }
                 u32x2_t ou = __builtin_bit_cast(u32x2_t, o);
                 if (border) { ou[0] = inside ? ou[0] : 0xFF80FF80u; ou[1] = inside ? ou[1] : 0xFF80FF80u; }
                 *reinterpret_cast<u32x2_t*>(smem + sdst[m] + nt * 32) = ou;
-                }
             }
         }
         MIL_STAMP_MARK(4)
         __syncthreads();
         MIL_STAMP_MARK(5)
         // ---- 3x3 s2 max-pool of the stem tile: first maximum in (ky,kx) scan order wins ---------------------
-#ifndef MIL_EXP_STEMF_NO_POOL
         {
             const int obase = ((img * Ho + PH * ty) * Wo + 16 * tx) * COUTP;
             const int ylim = Ho - PH * ty, xlim = Wo - 16 * tx;
@@ -393,18 +296,6 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
                 unsigned bi[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { best[j] = -INFINITY; bi[j] = 0; }
-                if constexpr (X3) {
-                    f32x4_t t[9];
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) t[k] = *reinterpret_cast<const f32x4_t*>(src + ((k / 3) * SF_SW + (k % 3)) * SPIX);
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (t[k][j] > best[j]) { best[j] = t[k][j]; bi[j] = k; }
-                        }
-                    }
-                } else {
                 u32x2_t t[9];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) t[k] = *reinterpret_cast<const u32x2_t*>(src + ((k / 3) * SF_SW + (k % 3)) * SPIX);
@@ -417,25 +308,18 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
                         if (v > best[j]) { best[j] = v; bi[j] = k; }
                     }
                 }
-                }
                 const bool ok = py < ylim && px < xlim;                 // py 15 (unused slot) is never inside: ylim <= 8
                 const unsigned eoff = (unsigned)(obase + p_rel[it]);
-                if constexpr (X3) {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4_t{best[0], best[1], best[2], best[3]}), rs_p,
-                                                           ok ? eoff * 4u : MIL_OOB, 0, 0);
-                } else {
-                    u32x2_t ov;
-                    ov[0] = (__float_as_uint(best[0]) >> 16) | (__float_as_uint(best[1]) & 0xFFFF0000u);
-                    ov[1] = (__float_as_uint(best[2]) >> 16) | (__float_as_uint(best[3]) & 0xFFFF0000u);
-                    __builtin_amdgcn_raw_buffer_store_b64(ov, rs_p, ok ? eoff * 2u : MIL_OOB, 0, 0);
-                }
+                u32x2_t ov;
+                ov[0] = (__float_as_uint(best[0]) >> 16) | (__float_as_uint(best[1]) & 0xFFFF0000u);
+                ov[1] = (__float_as_uint(best[2]) >> 16) | (__float_as_uint(best[3]) & 0xFFFF0000u);
+                __builtin_amdgcn_raw_buffer_store_b64(ov, rs_p, ok ? eoff * 2u : MIL_OOB, 0, 0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) bi[j] |= (best[j] > 0.f) ? 0u : 16u;
                 const unsigned rec = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
                 __builtin_amdgcn_raw_buffer_store_b32(rec, rs_i, ok ? eoff : MIL_OOB, 0, 0);
             }
         }
-#endif
         MIL_STAMP_MARK(6)
     }
     MIL_STAMP_STORE(a.stamp, NW)
@@ -477,13 +361,10 @@ __global__ __launch_bounds__(64 * NW, X3 ? 2 : (NT <= 2 ? (NW == 8 ? 4 : (NW == 
 // bf16 (one barrier per tile), single in split precision (hi + lo planes: 61 KB; two barriers).
 constexpr int SP_XH = 20;                                   // s2d rows of an 8x16-pooled-pixel tile
 template <bool X3> __host__ __device__ constexpr int sp_xbytes() { return SP_XH * SF_XW * sf_xpix(X3); }      // 36480 / 60800
-#ifndef MIL_SP_PRIO
-#define MIL_SP_PRIO 0                 // >0: the vector-instruction phases (maxima, decode, convert) at this priority (measured round 5 at equal repetition counts: no difference beyond the 3 % run-to-run spread)
-#endif
-#ifndef MIL_SP_WLDS
-#define MIL_SP_WLDS 1                 // bf16: filter fragments staged in LDS (16 KB) and ONE s2d buffer; 0: streamed from L1/L2, two buffers
-#endif
-template <bool X3> __host__ __device__ constexpr bool sp_wlds() { return !X3 && MIL_SP_WLDS; }
+// bf16: filter fragments staged in LDS (16 KB) and ONE s2d buffer; split precision: streamed from L1/L2, one buffer.
+// (Raising the priority of the vector-instruction phases — maxima, decode, convert — measured round 5 at equal repetition
+// counts: no difference beyond the 3 % run-to-run spread.)
+template <bool X3> __host__ __device__ constexpr bool sp_wlds() { return !X3; }
 template <bool X3> __host__ __device__ constexpr int sp_nbuf() { return (X3 || sp_wlds<X3>()) ? 1 : 2; }
 template <bool X3> __host__ __device__ constexpr int sp_lds_bytes() { return 64 + sp_nbuf<X3>() * (sp_xbytes<X3>() + 256) + 160 + (sp_wlds<X3>() ? MIL_SK6_STEPS * 2 * 64 * 16 : 0); }      // spare + tiles + the bias vector (+ the filter)
 
@@ -719,7 +600,6 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
         MIL_STAMP_MARK(0)
         __syncthreads();
         MIL_STAMP_MARK(1)
-        if (MIL_SP_PRIO) __builtin_amdgcn_s_setprio(0);
         const bool has_next = tile + G8 < t_end;
         if (!X3 && !FROM_XS && a.xs) {       // the tile's own 16x32 s2d pixels go to the xs tensor (when the caller keeps one)
             const int xbase = ((img * H2 + 16 * ty) * W2 + 32 * tx) * 32;
@@ -740,25 +620,15 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[m][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         {
-            #ifndef MIL_SP_WD
-#define MIL_SP_WD 2
-#endif
-#ifndef MIL_SP_LA
-#define MIL_SP_LA 2
-#endif
-#ifndef MIL_SP_EXP
-#define MIL_SP_EXP 0                  // ablations (development): 1 = no MFMA loop, 2 = no horizontal maxima, 4 = no decode / stores
-#endif
-            constexpr int MT = 11, TOT = (MIL_SP_EXP & 1) ? 0 : KSTEPS * MT, LA = X3 ? 1 : MIL_SP_LA, R = LA + 1;
-            constexpr int WD = X3 ? 1 : MIL_SP_WD, WR = WD + 1;           // filter fragments: k-steps ahead / ring slots
+            constexpr int MT = 11, TOT = KSTEPS * MT, LA = X3 ? 1 : 2, R = LA + 1;
+            constexpr int WD = X3 ? 1 : 2, WR = WD + 1;                    // filter fragments: k-steps ahead / ring slots
             // the step that issues the last filter loads: the next tile's input is requested behind them (vector loads return
             // in order).  Split precision has no registers for it inside the loop (two operand planes): requested behind the loop.
             constexpr int FETCH_AT = X3 ? -1 : (WLDS ? 0 : (KSTEPS - 1 - WD) * MT);
             Frag8<T> ring[R], wq[WR][NT];
-#ifndef MIL_SP_X3_FOLD
-#define MIL_SP_X3_FOLD 1              // split precision, column tile 1 (channels 16-19): [wh ; wl] x xh, then wh x xl (two MFMAs + a lane exchange in the
-#endif                                // epilogue) instead of three MFMAs; measured 1395 vs 1425 us per launch (round 5)
-            constexpr bool FOLD = X3 && MIL_SP_X3_FOLD;
+            // split precision, column tile 1 (channels 16-19): [wh ; wl] x xh, then wh x xl (two MFMAs + a lane exchange in the
+            // epilogue) instead of three MFMAs; measured 1395 vs 1425 us per launch (round 5)
+            constexpr bool FOLD = X3;
             const int w1h = (FOLD && r >= 4 && r < 8) ? (64 + lane - 4) * FRAGB + 16 : (64 + lane) * FRAGB;
             auto wfrag = [&](int sl, int nt) {
                 Frag8<T> f;
@@ -808,12 +678,11 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
         if constexpr (X3) {
             if (has_next) fetch(tile + G8);
         }
-        if (MIL_SP_PRIO) __builtin_amdgcn_s_setprio(MIL_SP_PRIO);
         // the hand-written vector instructions below read MFMA results: the compiler pads its own, not those inside asm
         asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         MIL_STAMP_MARK(2)
-        if constexpr (X3 && MIL_SP_X3_FOLD) {      // column tile 1: rows 4-7 (lane group 1) hold w_lo * x_hi of rows 0-3 — add them, zero the padding channels
+        if constexpr (X3) {      // column tile 1: rows 4-7 (lane group 1) hold w_lo * x_hi of rows 0-3 — add them, zero the padding channels
 #pragma unroll
             for (int m = 0; m < 11; ++m) {
 #pragma unroll
@@ -846,8 +715,8 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) { h[rho][q] = ev_in ? h[rho][q] : sentv; o[q] = od_in ? o[q] : sentv; }
             }
-            if (!(MIL_SP_EXP & 2)) sp_hmax8(h[rho], o);
-            if (tx > 0 && !(MIL_SP_EXP & 2)) {                   // column -1 of the image is padding: nothing to add
+            sp_hmax8(h[rho], o);
+            if (tx > 0) {                   // column -1 of the image is padding: nothing to add
                 constexpr unsigned long long mask = rho == 0 ? 0x0001000100010001ull : 0x1111111111111111ull << (rho & 3);
                 sp_edge8<rho>(h[rho], ek, sentv, mask);
             }
@@ -862,7 +731,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
         // ---- winner decode, + bias, LeakyReLU, store ------------------------------------------------------------------------
         const f32x4_t bias0 = *reinterpret_cast<const f32x4_t*>(ldsB + gq * 16), bias1 = *reinterpret_cast<const f32x4_t*>(ldsB + 64 + gq * 16);
 #pragma unroll
-        for (int p = 0; p < ((MIL_SP_EXP & 4) ? 0 : 2); ++p) {
+        for (int p = 0; p < 2; ++p) {
             const int py = PH * ty + 2 * wave + p, px = 16 * tx + r;
             const bool ok = py < Ho && px < Wo;
             const unsigned pix = (unsigned)((img * Ho + py) * Wo + px);
@@ -899,14 +768,6 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
             __builtin_amdgcn_raw_buffer_store_b32(rec[0], rs_i, ok ? pix * 24u + (unsigned)gq * 4u : MIL_OOB, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(rec[1], rs_i, ok1 ? pix * 24u + 16u + (unsigned)gq * 4u : MIL_OOB, 0, 0);
         }
-        if (MIL_SP_EXP & 4) {                                    // ablation: keep the maxima alive without the decode / stores
-            float sacc = 0.f;
-#pragma unroll
-            for (int rho = 0; rho < 5; ++rho)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) sacc += h[rho][q];
-            if (sacc == 1234.5f) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sacc), rs_i, 0, 0, 0);
-        }
         MIL_STAMP_MARK(4)
         if constexpr (NBUF == 1) __syncthreads();                // every wave is done reading the s2d tile
         else buf ^= 1;
@@ -938,9 +799,7 @@ static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
         b.widx = a.widx + (size_t)i0 * a.Ho * a.Wo * COUTP;
         b.ntiles = b.n_img * a.tiles_y * a.tiles_x;
         int grid = (b.ntiles + 7) & ~7;
-        int per_cu = mil_resident_per_cu(kern, lds, 2);
-        if (const char* e = mil_ab_env("MIL_STEM_WGS")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;      // development builds only
-        const int cap = mil_num_cus() * per_cu;
+        const int cap = mil_num_cus() * mil_resident_per_cu(kern, lds, 2);
         if (grid > cap) grid = cap;
 #ifdef MIL_STAMP
         static MilStampBuf sb;
@@ -958,25 +817,19 @@ static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
 
 #include "stem_walk.cuh"
 
-template <int NT, bool X3 = false, bool FROM_XS = false>
+template <int NT, bool FROM_XS = false>
 static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
     constexpr int COUTP = mil_nt_to_cp(NT);
-    constexpr int OESZ = X3 ? 4 : 2;
-    const int lds = sf_lds_bytes<NT, X3>();
-    // measured (24 channels, bf16): 1120 us with 4 waves per workgroup at 238 VGPRs, 1428 us with 8 waves squeezed into 128
-    // VGPRs (15 spilled): the 8-wave form serves the split-precision kernel, whose 156 KB of LDS leave one workgroup per CU
-    // (two waves per SIMD at up to 256 VGPRs)
-#ifndef MIL_STEM_FWD_WAVES
-#define MIL_STEM_FWD_WAVES 4
-#endif
-    constexpr int NW = X3 ? (sf_wstream(true) ? 4 : 8) : (NT <= 2 ? MIL_STEM_FWD_WAVES : 4);
-    a.tiles_y = (a.Ho + sf_ph(X3) - 1) / sf_ph(X3);
-    auto kern = stem_fwd_fused_kernel<NT, NW, X3, FROM_XS>;
+    constexpr int OESZ = 2;
+    const int lds = sf_lds_bytes<NT>();
+    constexpr int NW = 4;
+    a.tiles_y = (a.Ho + SF_PH - 1) / SF_PH;
+    auto kern = stem_fwd_fused_kernel<NT, NW, false, FROM_XS>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
     // every tensor is addressed with 32-bit offsets below 2 GiB: split the launch by images
     size_t per_img = FROM_XS ? 0 : (size_t)3 * a.H * a.W * 4;
-    const size_t xs_img = X3 ? 0 : (size_t)a.H2 * a.W2 * 32, p_img = (size_t)a.Ho * a.Wo * COUTP * OESZ;
+    const size_t xs_img = (size_t)a.H2 * a.W2 * 32, p_img = (size_t)a.Ho * a.Wo * COUTP * OESZ;
     if (xs_img > per_img) per_img = xs_img;
     if (p_img > per_img) per_img = p_img;
     const int chunk = mil_imgs_under_2g(per_img);
@@ -991,7 +844,7 @@ static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
         b.widx = a.widx + (size_t)i0 * a.Ho * a.Wo * COUTP;
         b.ntiles = b.n_img * a.tiles_y * a.tiles_x;
         int grid = (b.ntiles + 7) & ~7;
-        const int cap = mil_num_cus() * ((NT <= 2 && (!X3 || sf_wstream(true))) ? 2 : 1);
+        const int cap = mil_num_cus() * (NT <= 2 ? 2 : 1);
         if (grid > cap) grid = cap;
 #ifdef MIL_STAMP
         static MilStampBuf sb;
@@ -1001,7 +854,7 @@ static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
         MIL_CHECK_LAUNCH();
 #ifdef MIL_STAMP
         static const char* const ph[7] = {"convert", "barrier-x", "fetch-issue", "gemm", "stem-store", "barrier-s", "pool"};
-        sb.report(X3 ? "stem_fwd_fused_kernel<x3>" : "stem_fwd_fused_kernel", grid, NW, 7, ph, st);
+        sb.report("stem_fwd_fused_kernel", grid, NW, 7, ph, st);
 #endif
     }
     return MIL_OK;
@@ -1026,16 +879,12 @@ extern "C" int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const 
     a.tiles_y = (a.Ho + 7) / 8; a.tiles_x = (a.Wo + 15) / 16;
     a.slope = slope;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#ifndef MIL_STEM_FWD_POOL
-#define MIL_STEM_FWD_POOL 1           // 0: the round-2..4 kernel (stem tile through LDS, bf16-rounded activations pooled)
-#endif
-    if (MIL_STEM_FWD_POOL && cout_p == 24) {
+    if (cout_p == 24) {
         if (mil_stem_walk_wanted(a, mil_num_cus() * 2))
             return dtype == MIL_DT_F32S ? launch_stem_fwd_walk<true>(a, st) : launch_stem_fwd_walk<false>(a, st);
         return dtype == MIL_DT_F32S ? launch_stem_fwd_pool<true, false>(a, st) : launch_stem_fwd_pool<false, false>(a, st);
     }
-    if (dtype == MIL_DT_F32S) return launch_stem_fwd<2, true>(a, st);
-    return cout_p == 24 ? launch_stem_fwd<2>(a, st) : launch_stem_fwd<4>(a, st);
+    return launch_stem_fwd<4>(a, st);
 }
 
 // The same pass fed by the bf16 space-to-depth tensor xs [n,H2,W2,16] (mil_tile_preprocess_s2d's output, or mil_stem_s2d's):
@@ -1053,6 +902,6 @@ extern "C" int mil_stem_fwd_fused_xs(const void* xs, const void* wpack, const fl
     a.tiles_y = (a.Ho + 7) / 8; a.tiles_x = (a.Wo + 15) / 16;
     a.slope = slope;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (MIL_STEM_FWD_POOL && cout_p == 24) return launch_stem_fwd_pool<false, true>(a, st);
-    return cout_p == 24 ? launch_stem_fwd<2, false, true>(a, st) : launch_stem_fwd<4, false, true>(a, st);
+    if (cout_p == 24) return launch_stem_fwd_pool<false, true>(a, st);
+    return launch_stem_fwd<4, true>(a, st);
 }

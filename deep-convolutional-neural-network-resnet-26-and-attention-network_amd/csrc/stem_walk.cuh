@@ -193,11 +193,11 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[m][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
             {
-                constexpr int TOT = KSTEPS * MT, LA = X3 ? 1 : MIL_SP_LA, R = LA + 1;
-                constexpr int WD = X3 ? 1 : MIL_SP_WD, WR = WD + 1;
+                constexpr int TOT = KSTEPS * MT, LA = X3 ? 1 : 2, R = LA + 1;
+                constexpr int WD = X3 ? 1 : 2, WR = WD + 1;
                 constexpr int FETCH_AT = X3 ? -1 : 0;
                 Frag8<T> ring[R], wq[WR][NT];
-                constexpr bool FOLD = X3 && MIL_SP_X3_FOLD;
+                constexpr bool FOLD = X3;
                 const int w1h = (FOLD && r >= 4 && r < 8) ? (64 + lane - 4) * FRAGB + 16 : (64 + lane) * FRAGB;
                 auto wfrag = [&](int sl, int nt) {
                     Frag8<T> f;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
             asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
             MIL_STAMP_MARK(2)
-            if constexpr (X3 && MIL_SP_X3_FOLD) {      // column tile 1: rows 4-7 (lane group 1) hold w_lo * x_hi of rows 0-3 — add them, zero the padding channels
+            if constexpr (X3) {      // column tile 1: rows 4-7 (lane group 1) hold w_lo * x_hi of rows 0-3 — add them, zero the padding channels
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -342,11 +342,11 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
 }
 
 // Row walk when the tile is 256 pixels wide, no space-to-depth copy is kept, and whole images fill the resident workgroups
-// evenly enough (cost: rounds x steps x time per step against rounds x tiles x time per tile).  MIL_STEM_WALK = 0 / 1 (read per call) is a
+// evenly enough (cost: rounds x steps x time per step against rounds x tiles x time per tile).  MIL_STEM_WALK = 0 / 1 is a
 // TEST knob that forces either form.
 static bool mil_stem_walk_wanted(const StemFwdArgs& a, int grid_cap) {
     if (a.W != 256 || a.xs || a.xs_in || (a.H & 1) || a.Wo != 64) return false;
-    const char* e = getenv("MIL_STEM_WALK");
+    const char* e = mil_test_knob("MIL_STEM_WALK");
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
     const long tiles = (long)a.n_img * ((a.Ho + 7) / 8) * 4;
     const long cost_tile = (tiles + grid_cap - 1) / grid_cap * 6;           // measured: 6.5 / 11.0 us per tile, 5.4 / 9.0 us per step (bf16 / split)

@@ -358,16 +358,13 @@ def conv_s2_entry(x, wpack3, bias_pad, wpack1, cout_p, *, slope=LEAK):
     return y1, y2
 
 
-WGRAD_PAIR = True      # False (set from Python): the two stage-entry weight gradients as separate launches (A/B runs)
-
-
 def conv_wgrad_pair(x, dz1, dz2, cin, cout, *, workspace=None, out=None):
     """(dW3, db3, dW1) of a stage-entry block's 3x3/s2 conv and 1x1/s2 projection from one pass over x (see
     mil_conv_wgrad_pair), or None when the shape/dtype has no such kernel.  out = (dw3, db3, dw1) accumulates in place."""
     n, h, w, _ = x.shape
     _, ho, wo, _ = dz1.shape
     code = L.dt_code(x.dtype, mma=True)
-    if code not in (L.MIL_DT_BF16, L.MIL_DT_F32S) or not WGRAD_PAIR:
+    if code not in (L.MIL_DT_BF16, L.MIL_DT_F32S):
         return None
     _need(x, (n, h, w, cpad(cin)), x.dtype, "x")
     _need(dz1, (n, ho, wo, cpad(cout)), x.dtype, "dz1")

@@ -11,6 +11,8 @@
  *   - plain C: raw device pointers, ints, floats; `stream` is a hipStream_t passed as void*.
  *   - every function returns MIL_OK (0) or an error code; nothing allocates, nothing synchronises,
  *     no global state: work is enqueued on `stream`, buffers are caller-owned.
+ *   - the only environment read: five test knobs, on every call (MIL_PF_MIN_TILES, MIL_BUFFER_LIMIT_BYTES,
+ *     MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK), with which tests drive small inputs through the large-launch paths.
  *   - activations are NHWC with channels padded to a multiple of 8 (20->24, 40, 60->64, 80; padded
  *     channels hold zeros); `dtype` selects the activation/weight-operand type:
  *         MIL_DT_F32  (0): exact-fp32 MFMA (v_mfma_f32_16x16x4_f32)  — the parity gate, bit-level
@@ -215,7 +217,7 @@ int mil_conv_chain(const void* x, const MilChainConv* convs, int nconv, int n_im
  * Two kernels per precision, same arithmetic per output element (bit-identical, tested): tiles of one image (16x16 / 16x8
  * pixels, input halo staged per tile), or — maps 64 pixels wide (bf16: also 128) and enough images to fill the resident
  * workgroups evenly, about 512 — a row walk: one workgroup per image, input and mid activation in LDS rings, every input
- * pixel fetched once.  The environment variable MIL_BLOCK_STRIP=0/1 (a test knob, read per call) forces either form. */
+ * pixel fetched once.  MIL_BLOCK_STRIP=0/1 (a test knob) forces either form. */
 int mil_conv_block_fwd(const void* x, const void* wpack1, const float* bias1, const void* wpack2, const float* bias2,
                        void* o1, void* y, int n_img, int H, int W, int cp, float slope, int dtype, void* stream);
 
@@ -263,7 +265,7 @@ int mil_conv_dgrad_s2(const void* dz1, const void* dz2, const void* wpack, const
  * MIL_ERR_UNSUPPORTED (the caller then uses the three calls).
  * Two kernels for the 20-channel stem, bit-identical pool / widx: 8x16-pooled-pixel tiles, or — W == 256, xs == NULL and enough
  * images to fill the resident workgroups evenly, about 512 — a row walk (one workgroup per image, the space-to-depth rows in an
- * LDS ring, every input byte fetched once).  MIL_STEM_WALK=0/1 (a test knob, read per call) forces either form. */
+ * LDS ring, every input byte fetched once).  MIL_STEM_WALK=0/1 (a test knob) forces either form. */
 int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const float* bias_pad, void* xs, void* pool,
                        uint8_t* widx, int n_img, int H, int W, int cout_p, float slope, int dtype, void* stream);
 /* The same pass fed by the bf16 space-to-depth tensor xs [n,H2,W2,16] itself (mil_tile_preprocess_s2d's output): a
@@ -288,7 +290,7 @@ int mil_stem_bwd_fused(const void* xs, const void* g_pool, const uint8_t* widx, 
  * backward per 2048 tiles of 256x256.
  * bf16, W == 256 and enough images to fill the resident workgroups evenly (about 512): a row walk (one workgroup per image,
  * s2d rows and pooling windows in LDS rings) instead of 16x16 tiles; dW / db agree between the two forms to fp32 summation
- * order (a workgroup's partial sums cover other pixels).  MIL_STEM_WALK=0/1 (a test knob, read per call) forces either form. */
+ * order (a workgroup's partial sums cover other pixels).  MIL_STEM_WALK=0/1 (a test knob) forces either form. */
 int mil_stem_bwd_fused_nchw_workspace(size_t* bytes, int n, int H, int W, int dtype);
 int mil_stem_bwd_fused_nchw(const float* x_nchw, const void* g_pool, const uint8_t* widx, float* dw, float* db,
                             void* workspace, size_t workspace_bytes, int n, int H, int W, float slope, int accumulate,

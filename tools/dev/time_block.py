@@ -18,7 +18,7 @@ x[..., :20] = torch.randn((n, h, 64, 20), generator=g, device="cuda")
 w1 = torch.randn((20, 20, 3, 3), generator=g, device="cuda") / 13.4
 w2 = torch.randn((20, 20, 3, 3), generator=g, device="cuda") / 13.4
 b = torch.randn((20,), generator=g, device="cuda") * 0.1
-reps = 3 if "stamp" in os.environ.get("MIL_LIB_PATH", "") else 20
+reps = 20
 for mode, dt, code in (("x3", torch.float32, L.MIL_DT_F32S), ("bf16", torch.bfloat16, L.MIL_DT_F32)):
     with L.f32_mma(code):
         xx = x.to(dt)
