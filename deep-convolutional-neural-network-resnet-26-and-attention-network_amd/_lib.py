@@ -44,6 +44,8 @@ _SIGS = {
     "mil_stream_copy": ([_vp, _vp, _sz, _vp], _i),
     "mil_split_probe": ([_vp, _vp, _vp, _i, _vp], _i),
     "mil_stem_s2d": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_u8_decode_table": ([_vp], _i),
+    "mil_stem_s2d_u8": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_packed_weight_elems": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_pack_conv_weights": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_conv_igemm": ([_vp] * 6 + [_i] * 12 + [_f, _i, _vp], _i),
@@ -61,7 +63,9 @@ _SIGS = {
     "mil_resize_coeffs": ([_i, _i, _vp, _vp], _i),
     "mil_tile_preprocess": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_tile_preprocess_s2d": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_tile_preprocess_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_stem_fwd_fused_xs": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
+    "mil_stem_fwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_block_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_chain": ([_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_pair": ([_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
@@ -74,6 +78,8 @@ _SIGS = {
     "mil_stem_bwd_fused": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
     "mil_stem_bwd_fused_nchw_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_stem_bwd_fused_nchw": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
+    "mil_stem_bwd_fused_u8_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
+    "mil_stem_bwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_wide_packed_elems": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),

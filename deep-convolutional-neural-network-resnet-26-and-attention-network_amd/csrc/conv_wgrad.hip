@@ -13,6 +13,7 @@
 #include "pf_common.cuh"
 #include "reduce.cuh"
 #include "stamp.cuh"
+#include "u8_feed.cuh"
 
 template <typename T>
 struct WgradArgs {
@@ -679,6 +680,7 @@ static int wgrad_entry(const void* x, const void* dz, float* dw, float* db, void
 struct StemBwdArgs {
     const __bf16* xs;        // [n,H2,W2,16] space-to-depth input (FROM_X = false)
     const float* x;          // [n,3,H,W] the fp32 tiles themselves (FROM_X = true: the s2d tile is rebuilt in LDS, no copy kept)
+    const uint8_t* x8;       // [n,3,H,W] the tiles as planar bytes (U8, with FROM_X: u8_feed.cuh)
     int H, W;                // input dims (FROM_X)
     unsigned x_bytes;
     int lds_dump_off;
@@ -703,11 +705,14 @@ constexpr int MIL_STEM_BWD_WAVES = 2;  // measured (us per launch, 2048 tiles): 
 // windows = 243 pieces — every map of at least 9 pixels), else 2.  An unused second slot is three more loads per thread and tile
 // with an out-of-range offset: no memory traffic, but a quarter of this kernel's load instructions, and issuing them is what
 // its "fetch issue" phase (23 % of a tile) pays for.
-template <bool FROM_X, bool X3 = false, int NPW = 2>
-__global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel(StemBwdArgs a) {
+// The body is shared by stem_bwd_fused_kernel and the uint8 feed (stem_bwd_fused_u8_kernel, U8: FROM_X with two 4-byte loads per
+// item, decoded at the commit by mil_u8_item of u8_feed.cuh).
+template <bool FROM_X, bool X3, int NPW, bool U8>
+__device__ __forceinline__ void stem_bwd_fused_body(const StemBwdArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MIL_POISON(smem);
     static_assert(!X3 || FROM_X, "the split-precision form reads the fp32 tiles");
+    static_assert(!U8 || FROM_X, "the uint8 feed rebuilds its s2d tiles");
     constexpr int CINP = 16, NT = 2, KS = 4, COUTP = 24;
     constexpr int PIXB = mil_pix_pitch(CINP, X3 ? 4 : 2);   // 48; X3: 80 = [hi 32 B][lo 32 B] + pad
     constexpr int PIXZ = mil_pix_pitch(COUTP, X3 ? 4 : 2);  // dz tile: 48; X3: 112 = [hi 48 B][lo 48 B] + pad
@@ -728,7 +733,7 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
     const int WH = TH / 2 + 1, WW = TW / 2 + 1;             // pooling windows per image of the tile
     const int nwin = (WH * WW) << g.ti_log2;
 
-    const __amdgpu_buffer_rsrc_t rs_x = FROM_X ? mil_rsrc(a.x, a.x_bytes) : mil_rsrc(a.xs, a.xs_bytes);
+    const __amdgpu_buffer_rsrc_t rs_x = U8 ? mil_rsrc(a.x8, a.x_bytes) : FROM_X ? mil_rsrc(a.x, a.x_bytes) : mil_rsrc(a.xs, a.xs_bytes);
     const __amdgpu_buffer_rsrc_t rs_g = mil_rsrc(a.gp, a.gp_bytes);
     const __amdgpu_buffer_rsrc_t rs_i = mil_rsrc(a.widx, a.wi_bytes);
     HaloTables<NPX> ht;
@@ -750,37 +755,49 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
                 const int ti = row / g.hh, hy = row - ti * g.hh;
                 l_pos[i] = (ti << 20) | (hy << 10) | pair;
                 l_lds[i] = ((row * g.hw + 2 * pair) * PIXB + c * 8) | ((2 * pair + 1 >= g.hw) ? 1 << 20 : 0);
-                l_rel[i] = (((ti * 3 + c) * a.H + 2 * hy) * a.W + 4 * pair) * 4;
+                l_rel[i] = (((ti * 3 + c) * a.H + 2 * hy) * a.W + 4 * pair) * (U8 ? 1 : 4);
             }
         }
     }
-    u32x4_t lr0[NL], lr1[NL];
-    auto fetch_x = [&](const TileOrigin& o) {
+    using LoadT = typename std::conditional<U8, unsigned, u32x4_t>::type;
+    LoadT lr0[NL], lr1[NL];
+    auto item_ok = [&](const TileOrigin& o, int p) {
         const int y0 = o.oy0 - g.pad, c0 = 2 * (o.ox0 - g.pad);          // first s2d row / first input column of the halo tile
-        const int base = (((o.img0 * 3) * a.H + 2 * y0) * a.W + c0) * 4;       // may be negative; valid lanes are not
-        const int ilim = g.n_img - o.img0;
+        return (p >= 0) & ((p >> 20) < g.n_img - o.img0) & ((unsigned)(y0 + ((p >> 10) & 1023)) < (unsigned)g.H) &
+               ((unsigned)(c0 + 4 * (p & 1023)) < (unsigned)a.W);
+    };
+    auto fetch_x = [&](const TileOrigin& o) {
+        const int y0 = o.oy0 - g.pad, c0 = 2 * (o.ox0 - g.pad);
+        const int base = (((o.img0 * 3) * a.H + 2 * y0) * a.W + c0) * (U8 ? 1 : 4);       // may be negative; valid lanes are not
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
-            const int p = l_pos[i];
-            const bool ok = (p >= 0) & ((p >> 20) < ilim) & ((unsigned)(y0 + ((p >> 10) & 1023)) < (unsigned)g.H) &
-                            ((unsigned)(c0 + 4 * (p & 1023)) < (unsigned)a.W);
+            const bool ok = item_ok(o, l_pos[i]);
             const unsigned off = ok ? (unsigned)(base + l_rel[i]) : MIL_OOB;
-            lr0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
-            lr1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(a.W * 4), 0, 0);
+            if constexpr (U8) {
+                lr0[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off, 0, 0);
+                lr1[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off + (unsigned)a.W, 0, 0);
+            } else {
+                lr0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
+                lr1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(a.W * 4), 0, 0);
+            }
         }
     };
-    auto commit_x = [&]() {
+    auto commit_x = [&](const TileOrigin& o) {      // o: the tile these registers were fetched for
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
-            const f32x4_t v0 = __builtin_bit_cast(f32x4_t, lr0[i]), v1 = __builtin_bit_cast(f32x4_t, lr1[i]);
-            const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
             bf16x4_t pa, pb, qa, qb;
-            if constexpr (X3) {
-                mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
-                mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+            if constexpr (U8) {      // out-of-image items commit zeros (the conv's padding), not decode(0) = -1
+                mil_u8_item<X3>(lr0[i], lr1[i], item_ok(o, l_pos[i]), pa, pb, qa, qb);
             } else {
+                const f32x4_t v0 = __builtin_bit_cast(f32x4_t, lr0[i]), v1 = __builtin_bit_cast(f32x4_t, lr1[i]);
+                const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
+                if constexpr (X3) {
+                    mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
+                    mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                    for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                }
             }
             const int d0 = l_lds[i] & 0xFFFFF;
             const int d1 = (l_lds[i] >> 20) ? a.lds_dump_off : d0 + PIXB;
@@ -872,7 +889,7 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
         MIL_STAMP_BEGIN()
         __syncthreads();                         // previous tile's MFMA loop is done with ldsX / ldsZ
         MIL_STAMP_MARK(0)
-        if constexpr (FROM_X) commit_x(); else mil_commit_halo<NPX>(rx, ldsX, ht);
+        if constexpr (FROM_X) commit_x(cur.origin(g)); else mil_commit_halo<NPX>(rx, ldsX, ht);
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
             if (w_pos[i] >= 0) {
@@ -1058,12 +1075,19 @@ __global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel
     }
 }
 
+template <bool FROM_X, bool X3 = false, int NPW = 2>
+__global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_kernel(StemBwdArgs a) { stem_bwd_fused_body<FROM_X, X3, NPW, false>(a); }
+template <bool X3, int NPW>
+__global__ __launch_bounds__(256, MIL_STEM_BWD_WAVES) void stem_bwd_fused_u8_kernel(StemBwdArgs a) { stem_bwd_fused_body<true, X3, NPW, true>(a); }
+
 #include "stem_bwd_walk.cuh"
 
 // xs != null: the bf16 space-to-depth copy [n,H2,W2,16] is the conv input; else x = the fp32 tiles [n,3,H,W] (H = 2*H2,
 // W = 2*W2, W % 4 == 0) and the kernel rebuilds its s2d tiles itself.  Inputs beyond the 2 GiB reach of a buffer
 // descriptor are walked in image chunks, later chunks accumulating into dW/db.
-static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const uint8_t* widx, float* dw, float* db, void* ws,
+// x8 != null (with from_x): the uint8 feed — the tiled kernel at every size (the bf16 row-walk backward reads fp32 tiles only), on
+// the grid the fp32 feed would take, so that the slabs, and with them the fp32 sums, are those of mil_stem_bwd_fused_nchw.
+static int stem_bwd_entry(const void* xs, const float* x, const uint8_t* x8, const void* gp, const uint8_t* widx, float* dw, float* db, void* ws,
                           size_t ws_bytes, int n, int H2, int W2, float slope, int accumulate, int dtype, bool from_x, bool query,
                           size_t* need, void* stream) {
     const bool x3 = dtype == MIL_DT_F32S || dtype == MIL_DT_F32S_DGRAD;      // fp32 g_pool, split-precision products: from the fp32 tiles only
@@ -1086,6 +1110,8 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
     if (halo_px > 400 || nwin * 3 > 512 || g.hh >= 1024 || g.hw >= 1024) return MIL_ERR_UNSUPPORTED;
     if (from_x && ((g.hh << g.ti_log2) * ((g.hw + 1) >> 1) * 3 > 3 * 256)) return MIL_ERR_UNSUPPORTED;
     // images per launch: every tensor of a launch must stay under 2 GiB; whole tiles of images per chunk
+    // (the uint8 feed's images are 3*H*W bytes; it is chunked like the fp32 feed all the same, so that a split launch accumulates
+    // the same images per chunk and the workspace query of the fp32 feed holds for both)
     const size_t in_img = from_x ? (size_t)12 * a.H * a.W : (size_t)H2 * W2 * 32, gp_img = (size_t)a.Hp * a.Wp * gpx;
     a.gpx = gpx;
     int chunk = mil_imgs_under_2g(in_img > gp_img ? in_img : gp_img);
@@ -1093,12 +1119,15 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
     if (chunk > n) chunk = n;
     const int xb = (halo_px * PIXB + 15) & ~15, zb = 256 * PIXZ, gb = (nwin * PIXG + 15) & ~15, ib = (nwin * 24 + 15) & ~15;
     const int lds = xb + zb + gb + ib + 48;                 // + dump slot (FROM_X: second pixel of a pair behind an odd-width halo; hi + lo)
+    const bool u8 = x8 != nullptr;
     const int groups = (chunk + (1 << g.ti_log2) - 1) >> g.ti_log2;
     const int ntiles_max = groups * g.tiles_y * g.tiles_x;
     const bool one = nwin * 3 <= 256;                       // one window piece per thread
     auto kern = x3 ? (one ? stem_bwd_fused_kernel<true, true, 1> : stem_bwd_fused_kernel<true, true, 2>)
               : from_x ? (one ? stem_bwd_fused_kernel<true, false, 1> : stem_bwd_fused_kernel<true, false, 2>)
                        : (one ? stem_bwd_fused_kernel<false, false, 1> : stem_bwd_fused_kernel<false, false, 2>);
+    auto kern8 = x3 ? (one ? stem_bwd_fused_u8_kernel<true, 1> : stem_bwd_fused_u8_kernel<true, 2>)
+                    : (one ? stem_bwd_fused_u8_kernel<false, 1> : stem_bwd_fused_u8_kernel<false, 2>);
     int grid = mil_num_cus() * mil_resident_per_cu(kern, lds, 4) * 2;          // two rounds of the resident set
     if (grid > ntiles_max) grid = ntiles_max;
     const size_t slab_elems = (size_t)(MT + 1) * 16 * 32;
@@ -1109,7 +1138,7 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
     a.lds_z_off = xb; a.lds_g_off = xb + zb; a.lds_i_off = xb + zb + gb; a.lds_dump_off = xb + zb + gb + ib; a.slope = slope;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // the row-walk form (stem_bwd_walk.cuh): one workgroup per image, no more slabs than the tiled form's workspace holds
-    const bool walk = mil_stem_walk_wanted_bwd(n, H2, W2, from_x, !x3, g.tiles_y * g.tiles_x, mil_num_cus() * 2);
+    const bool walk = !u8 && mil_stem_walk_wanted_bwd(n, H2, W2, from_x, !x3, g.tiles_y * g.tiles_x, mil_num_cus() * 2);
     int walk_grid = 0;
     if (walk) {
         auto wk = stem_bwd_walk_kernel;
@@ -1126,7 +1155,8 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
         StemBwdArgs c = a;
         c.g.n_img = nc; c.g.n_groups = (nc + (1 << g.ti_log2) - 1) >> g.ti_log2;
         c.ntiles = c.g.n_groups * g.tiles_y * g.tiles_x;
-        if (from_x) { c.x = x + (size_t)i0 * 3 * a.H * a.W; c.x_bytes = (unsigned)((size_t)nc * 12 * a.H * a.W); }
+        if (u8) { c.x8 = x8 + (size_t)i0 * 3 * a.H * a.W; c.x_bytes = (unsigned)((size_t)nc * 3 * a.H * a.W); }
+        else if (from_x) { c.x = x + (size_t)i0 * 3 * a.H * a.W; c.x_bytes = (unsigned)((size_t)nc * 12 * a.H * a.W); }
         else { c.xs = (const __bf16*)xs + (size_t)i0 * H2 * W2 * 16; c.xs_bytes = (unsigned)((size_t)nc * H2 * W2 * 32); }
         c.gp = (const __bf16*)gp + (size_t)i0 * a.Hp * a.Wp * (gpx / 2); c.gp_bytes = (unsigned)((size_t)nc * gp_img);
         c.widx = widx + (size_t)i0 * a.Hp * a.Wp * 24; c.wi_bytes = (unsigned)((size_t)nc * a.Hp * a.Wp * 24);
@@ -1136,11 +1166,12 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
         c.stamp = sb.get((size_t)gr * 4 * 9);
 #endif
         if (walk) hipLaunchKernelGGL(stem_bwd_walk_kernel, dim3(gr), dim3(256), SBW_LDS, st, c);
+        else if (u8) hipLaunchKernelGGL(kern8, dim3(gr), dim3(256), lds, st, c);
         else hipLaunchKernelGGL(kern, dim3(gr), dim3(256), lds, st, c);
         MIL_CHECK_LAUNCH();
 #ifdef MIL_STAMP
         static const char* const ph[7] = {"barrier-top", "commit", "barrier-x", "fetch-issue", "gather", "barrier-z", "gemm"};
-        sb.report(walk ? "stem_bwd_walk_kernel" : x3 ? "stem_bwd_fused_kernel<x3>" : "stem_bwd_fused_kernel", gr, 4, 7, ph, st);
+        sb.report(walk ? "stem_bwd_walk_kernel" : u8 ? (x3 ? "stem_bwd_fused_u8_kernel<x3>" : "stem_bwd_fused_u8_kernel") : x3 ? "stem_bwd_fused_kernel<x3>" : "stem_bwd_fused_kernel", gr, 4, 7, ph, st);
 #endif
         MilReduceJob j{};
         j.slab = (const float*)ws; j.nslab = gr; j.slab_elems = slab_elems; j.slab_cols = 32; j.n_rows = 16 * 12;
@@ -1155,7 +1186,7 @@ static int stem_bwd_entry(const void* xs, const float* x, const void* gp, const 
 
 extern "C" int mil_stem_bwd_fused_workspace(size_t* bytes, int n, int H2, int W2, int dtype) {
     if (!bytes) return MIL_ERR_ARG;
-    return stem_bwd_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, H2, W2, 0.1f, 0, dtype, false, true, bytes, nullptr);
+    return stem_bwd_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, H2, W2, 0.1f, 0, dtype, false, true, bytes, nullptr);
 }
 
 extern "C" int mil_stem_bwd_fused(const void* xs, const void* g_pool, const uint8_t* widx, float* dw, float* db,
@@ -1163,14 +1194,14 @@ extern "C" int mil_stem_bwd_fused(const void* xs, const void* g_pool, const uint
                                   int accumulate, int dtype, void* stream) {
     if (!xs || !g_pool || !widx || !dw || !db) return MIL_ERR_ARG;
     size_t need = 0;
-    return stem_bwd_entry(xs, nullptr, g_pool, widx, dw, db, workspace, workspace_bytes, n, H2, W2, slope, accumulate, dtype, false, false,
+    return stem_bwd_entry(xs, nullptr, nullptr, g_pool, widx, dw, db, workspace, workspace_bytes, n, H2, W2, slope, accumulate, dtype, false, false,
                           &need, stream);
 }
 
 extern "C" int mil_stem_bwd_fused_nchw_workspace(size_t* bytes, int n, int H, int W, int dtype) {
     if (!bytes) return MIL_ERR_ARG;
     if (H <= 0 || W <= 0 || (H & 1) || (W & 3)) return MIL_ERR_UNSUPPORTED;
-    return stem_bwd_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, H / 2, W / 2, 0.1f, 0, dtype, true, true, bytes, nullptr);
+    return stem_bwd_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n, H / 2, W / 2, 0.1f, 0, dtype, true, true, bytes, nullptr);
 }
 
 extern "C" int mil_stem_bwd_fused_nchw(const float* x, const void* g_pool, const uint8_t* widx, float* dw, float* db,
@@ -1179,8 +1210,25 @@ extern "C" int mil_stem_bwd_fused_nchw(const float* x, const void* g_pool, const
     if (!x || !g_pool || !widx || !dw || !db) return MIL_ERR_ARG;
     if (H <= 0 || W <= 0 || (H & 1) || (W & 3) || (reinterpret_cast<uintptr_t>(x) & 15)) return MIL_ERR_UNSUPPORTED;
     size_t need = 0;
-    return stem_bwd_entry(nullptr, x, g_pool, widx, dw, db, workspace, workspace_bytes, n, H / 2, W / 2, slope, accumulate, dtype, true, false,
+    return stem_bwd_entry(nullptr, x, nullptr, g_pool, widx, dw, db, workspace, workspace_bytes, n, H / 2, W / 2, slope, accumulate, dtype, true, false,
                           &need, stream);
+}
+
+// The same backward reading uint8 tiles x [n,3,H,W] (u8_feed.cuh): dw / db are bit-identical to mil_stem_bwd_fused_nchw on the
+// decoded tiles in its tiled form (the bf16 row-walk form reads fp32 tiles only: this feed runs the tiled kernel at every size).
+// H even, W % 4 == 0, x 4-byte aligned, else MIL_ERR_UNSUPPORTED; the workspace is that of mil_stem_bwd_fused_nchw.
+extern "C" int mil_stem_bwd_fused_u8_workspace(size_t* bytes, int n, int H, int W, int dtype) {
+    return mil_stem_bwd_fused_nchw_workspace(bytes, n, H, W, dtype);
+}
+
+extern "C" int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, const uint8_t* widx, float* dw, float* db,
+                                     void* workspace, size_t workspace_bytes, int n, int H, int W, float slope,
+                                     int accumulate, int dtype, void* stream) {
+    if (!x_u8 || !g_pool || !widx || !dw || !db) return MIL_ERR_ARG;
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 3) || (reinterpret_cast<uintptr_t>(x_u8) & 3)) return MIL_ERR_UNSUPPORTED;
+    size_t need = 0;
+    return stem_bwd_entry(nullptr, nullptr, x_u8, g_pool, widx, dw, db, workspace, workspace_bytes, n, H / 2, W / 2, slope, accumulate, dtype,
+                          true, false, &need, stream);
 }
 
 static int wgrad_pair_entry(const void* x, const void* dz1, const void* dz2, float* dw3, float* db3, float* dw1, void* ws,

@@ -5,6 +5,7 @@
 #include "geom.cuh"
 #include "pack.cuh"
 #include "pf_common.cuh"
+#include "u8_feed.cuh"
 
 // ---------------------------------------------------------------------------------------------
 // fp32 NCHW [n,3,H,W]  ->  NHWC space-to-depth [n, ceil(H/2), ceil(W/2), 16]; channel = c*4 + dy*2 + dx
@@ -46,6 +47,55 @@ extern "C" int mil_stem_s2d(const float* x_nchw, void* out, int n, int H, int W,
     else if (dtype == MIL_DT_F32) hipLaunchKernelGGL(stem_s2d_kernel<F32>, dim3(grid), dim3(256), 0, st, x_nchw, (float*)out, n, H, W, H2, W2);
     else return MIL_ERR_ARG;
     MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The same packing from uint8 tiles [n,3,H,W] (u8_feed.cuh): out = mil_stem_s2d of the decoded tiles, bit for bit.  Pixels
+// beyond an odd H / W are the zero padding (0.0, not decode(0)).
+template <typename T>
+__global__ void stem_s2d_u8_kernel(const uint8_t* __restrict__ x, typename T::elem* __restrict__ out, int n, int H, int W,
+                                   int H2, int W2) {
+    const size_t total = (size_t)n * H2 * W2;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int x2 = (int)(idx % W2);
+        const size_t r = idx / W2;
+        const int y2 = (int)(r % H2);
+        const int img = (int)(r / H2);
+        float v0[8], v1[8];
+#pragma unroll
+        for (int ch = 0; ch < 16; ++ch) {
+            float val = 0.f;
+            if (ch < 12) {
+                const int c = ch >> 2, dy = (ch >> 1) & 1, dx = ch & 1;
+                const int iy = 2 * y2 + dy, ix = 2 * x2 + dx;
+                if (iy < H && ix < W) val = mil_u8_decode(x[(((size_t)img * 3 + c) * H + iy) * W + ix]);
+            }
+            if (ch < 8) v0[ch] = val; else v1[ch - 8] = val;
+        }
+        store8<T>(out + idx * 16, v0);
+        store8<T>(out + idx * 16 + 8, v1);
+    }
+}
+
+extern "C" int mil_stem_s2d_u8(const uint8_t* x_u8, void* out, int n, int H, int W, int dtype, void* stream) {
+    if (!x_u8 || !out || n < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
+    const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
+    const size_t total = (size_t)n * H2 * W2;
+    if (total == 0) return MIL_OK;
+    int grid = (int)((total + 255) / 256);
+    if (grid > 65536) grid = 65536;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MIL_DT_BF16) hipLaunchKernelGGL(stem_s2d_u8_kernel<BF16>, dim3(grid), dim3(256), 0, st, x_u8, (__bf16*)out, n, H, W, H2, W2);
+    else if (dtype == MIL_DT_F32) hipLaunchKernelGGL(stem_s2d_u8_kernel<F32>, dim3(grid), dim3(256), 0, st, x_u8, (float*)out, n, H, W, H2, W2);
+    else return MIL_ERR_ARG;
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The 256 fp32 values the uint8 feed decodes to: mil_u8_decode — the expression every kernel of that feed evaluates — on the host.
+extern "C" int mil_u8_decode_table(float* out256) {
+    if (!out256) return MIL_ERR_ARG;
+    for (int u = 0; u < 256; ++u) out256[u] = mil_u8_decode((unsigned)u);
     return MIL_OK;
 }
 

@@ -25,6 +25,7 @@ struct PrepArgs {
     const int* kk;              // [R,ksize]
     float* out;                 // [T,3,R,R] fp32 NCHW, or null when xs is given
     __bf16* xs;                 // [T,R/2,R/2,16] bf16 space-to-depth NHWC (channel = c*4 + dy*2 + dx, 12 real), or null
+    uint8_t* out_u8;            // [T,3,R,R] the resized bytes themselves, planar (the uint8 feed: u8_feed.cuh), or null
     int T, S, pad, R, ksize;
     int margin, row_pitch;      // bytes: zero margin in front of a staged row (>= 3*pad, 4-aligned); pitch of a staged row
     int lds_h_off, lds_k_off, lds_b_off;
@@ -189,8 +190,13 @@ __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
             s0 += (int)p[k * R * 3] * wk; s1 += (int)p[k * R * 3 + 1] * wk; s2 += (int)p[k * R * 3 + 2] * wk;
         }
         const int yo = vflip ? R - 1 - yr : yr, xo = hflip ? R - 1 - xr : xr;
-        float* o = a.out + ((size_t)t * 3 * R + yo) * R + xo;
         const size_t plane = (size_t)R * R;
+        if (a.out_u8) {             // Pillow's own bytes: ToTensor + Normalize is left to the stem kernels' decode table
+            uint8_t* o8 = a.out_u8 + ((size_t)t * 3 * R + yo) * R + xo;
+            o8[0] = (uint8_t)prep_clip8(s0); o8[plane] = (uint8_t)prep_clip8(s1); o8[2 * plane] = (uint8_t)prep_clip8(s2);
+            continue;
+        }
+        float* o = a.out + ((size_t)t * 3 * R + yo) * R + xo;
         o[0] = ((float)prep_clip8(s0) / 255.0f - 0.5f) / 0.5f;
         o[plane] = ((float)prep_clip8(s1) / 255.0f - 0.5f) / 0.5f;
         o[2 * plane] = ((float)prep_clip8(s2) / 255.0f - 0.5f) / 0.5f;
@@ -247,12 +253,12 @@ extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
 // [0, 2*pad]) selects the train chain, null the flat chain.  bounds_host is the host copy of the table (the launcher
 // sizes the LDS strip from it); bounds_dev / kk_dev are its device copies (mil_resize_coeffs(S, R)).
 static int prep_entry(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
-                      const int32_t* kk_dev, float* out, void* xs, int T, int S, int pad, int R, void* stream) {
-    if (!rois || !bounds_host || !bounds_dev || !kk_dev || (!out && !xs) || T < 0 || S <= 0 || R <= 0 || pad < 0) return MIL_ERR_ARG;
+                      const int32_t* kk_dev, float* out, void* xs, uint8_t* out_u8, int T, int S, int pad, int R, void* stream) {
+    if (!rois || !bounds_host || !bounds_dev || !kk_dev || (!out && !xs && !out_u8) || T < 0 || S <= 0 || R <= 0 || pad < 0) return MIL_ERR_ARG;
     if (xs && ((R & 1) || (reinterpret_cast<uintptr_t>(xs) & 15))) return MIL_ERR_UNSUPPORTED;      // 2x2 blocks, 16-byte records
     if (T == 0) return MIL_OK;
     PrepArgs a{};
-    a.rois = rois; a.params = params; a.bounds = bounds_dev; a.kk = kk_dev; a.out = out; a.xs = static_cast<__bf16*>(xs);
+    a.rois = rois; a.params = params; a.bounds = bounds_dev; a.kk = kk_dev; a.out = out; a.xs = static_cast<__bf16*>(xs); a.out_u8 = out_u8;
     a.T = T; a.S = S; a.pad = params ? pad : 0; a.R = R; a.ksize = prep_ksize(S, R);
     int nri_max = 0;
     for (int r0 = 0; r0 < R; r0 += PREP_BAND) {
@@ -279,7 +285,16 @@ static int prep_entry(const uint8_t* rois, const int32_t* params, const int32_t*
 extern "C" int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                                    const int32_t* kk_dev, float* out, int T, int S, int pad, int R, void* stream) {
     if (!out) return MIL_ERR_ARG;
-    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, out, nullptr, T, S, pad, R, stream);
+    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, out, nullptr, nullptr, T, S, pad, R, stream);
+}
+
+// The same chain with the output left as bytes: out [T,3,R,R] uint8, planar — what Pillow's resize returns, before ToTensor +
+// Normalize (RoiBuilder.py:193-210).  The uint8 feed of the stem kernels (mil_stem_fwd_fused_u8 / mil_stem_bwd_fused_u8 /
+// mil_stem_s2d_u8) decodes it to exactly mil_tile_preprocess's fp32 values, in every compute mode.  Any R.
+extern "C" int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                                      const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream) {
+    if (!out) return MIL_ERR_ARG;
+    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, nullptr, nullptr, out, T, S, pad, R, stream);
 }
 
 // The same chain with the output written as the bf16 space-to-depth NHWC tensor xs [T,R/2,R/2,16] the stem kernels read
@@ -288,5 +303,5 @@ extern "C" int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, c
 extern "C" int mil_tile_preprocess_s2d(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                                        const int32_t* kk_dev, void* xs, int T, int S, int pad, int R, void* stream) {
     if (!xs) return MIL_ERR_ARG;
-    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, nullptr, xs, T, S, pad, R, stream);
+    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, nullptr, xs, nullptr, T, S, pad, R, stream);
 }

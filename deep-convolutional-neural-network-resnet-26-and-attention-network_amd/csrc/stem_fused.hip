@@ -14,10 +14,12 @@
 // are in flight on the same L2.
 #include "pf_common.cuh"
 #include "stamp.cuh"
+#include "u8_feed.cuh"
 #include <type_traits>
 
 struct StemFwdArgs {
-    const float* x;            // [n,3,H,W] (FROM_XS: null)
+    const float* x;            // [n,3,H,W] (FROM_XS, U8: null)
+    const uint8_t* x8;         // U8: the tiles as planar bytes [n,3,H,W] (u8_feed.cuh)
     const __bf16* xs_in;       // FROM_XS: the input already as bf16 space-to-depth NHWC [n,H2,W2,16] (mil_tile_preprocess_s2d)
     const void* w;             // MIL_PACK_STEM fragments [8][NT][64][8] (bf16; MIL_DT_F32S: [hi | lo] pairs)
     const float* bias;         // [NT*16]
@@ -421,9 +423,12 @@ __device__ __forceinline__ float sp_lrelu(float v, float slope) {            // 
     return d;
 }
 
-template <bool X3, bool FROM_XS>
-__global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
+// The body is shared by the fp32 / s2d feeds (stem_fwd_pool_kernel) and the uint8 feed (stem_fwd_pool_u8_kernel, U8): the feeds
+// differ in the fetch (two 4-byte loads per item instead of two 16-byte loads) and in the commit (mil_u8_item, u8_feed.cuh).
+template <bool X3, bool FROM_XS, bool U8>
+__device__ __forceinline__ void stem_fwd_pool_body(const StemFwdArgs& a) {
     static_assert(!(X3 && FROM_XS), "the space-to-depth feed is bf16");
+    static_assert(!(U8 && FROM_XS), "one feed at a time");
     using T = typename std::conditional<X3, F32S, BF16>::type;
     constexpr int NT = 2, COUTP = 24, NTHR = 256, KSTEPS = MIL_SK6_STEPS, KSTEPS_STD = 8, PH = 8;      // the SK6 order of geom.cuh: 6 k-steps
     constexpr int XPIX = sf_xpix(X3), XBYTES = sp_xbytes<X3>(), NBUF = sp_nbuf<X3>(), BUFSTRIDE = XBYTES + 256;
@@ -444,7 +449,8 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
     smem += SPARE;
     const int H = a.H, W = a.W, H2 = a.H2, W2 = a.W2, Ho = a.Ho, Wo = a.Wo;
     const __amdgpu_buffer_rsrc_t rs_x = FROM_XS ? mil_rsrc(a.xs_in, (unsigned)((size_t)a.n_img * H2 * W2 * 32))
-                                                : mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
+                                      : U8 ? mil_rsrc(a.x8, (unsigned)((size_t)a.n_img * 3 * H * W))
+                                           : mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
     const __amdgpu_buffer_rsrc_t rs_xs = mil_rsrc(a.xs, (unsigned)((size_t)a.n_img * H2 * W2 * 32));
     const __amdgpu_buffer_rsrc_t rs_p = mil_rsrc(a.pool, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP * OESZ));
     const __amdgpu_buffer_rsrc_t rs_i = mil_rsrc(a.widx, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP));
@@ -468,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
             const int pair = idx % SF_NPAIR, t = idx / SF_NPAIR;
             const int c = t % 3, row = t / 3;
             l_lds[i] = ((row * SF_XW + 2 * pair) * XPIX + c * 8) | ((c == 2 ? 1 : 0) << 16) | (row << 18) | (pair << 24);
-            l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * 4;
+            l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * (U8 ? 1 : 4);
         }
     }
     const int x_row0 = tid >> 6, x_col = (tid >> 1) & 31;
@@ -519,7 +525,8 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
     const int t_end = min(t_begin + per, a.ntiles);
     int tile = t_begin + (blockIdx.x >> 3);
 
-    u32x4_t r0[NLOAD], r1[FROM_XS ? 1 : NLOAD];
+    using LoadT = typename std::conditional<U8, unsigned, u32x4_t>::type;
+    LoadT r0[NLOAD], r1[FROM_XS ? 1 : NLOAD];
     auto fetch = [&](int t) {
         const int tx = t % a.tiles_x, q = t / a.tiles_x, ty = q % a.tiles_y, img = q / a.tiles_y;
         const int y0 = 2 * PH * ty - 3, c0 = 64 * tx - 8;
@@ -534,14 +541,19 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
             }
             return;
         }
-        const int base = (((img * 3) * H + 2 * y0) * W + c0) * 4;
+        const int base = (((img * 3) * H + 2 * y0) * W + c0) * (U8 ? 1 : 4);
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
             const int row = (l_lds[i] >> 18) & 31, pair = l_lds[i] >> 24;
             const bool ok = (unsigned)(y0 + row) < (unsigned)H2 && (unsigned)(c0 + 4 * pair) < (unsigned)W;
             const unsigned off = ok ? (unsigned)(base + l_rel[i]) : MIL_OOB;
-            r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
-            r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(W * 4), 0, 0);
+            if constexpr (U8) {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off + (unsigned)W, 0, 0);
+            } else {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(W * 4), 0, 0);
+            }
         }
     };
     if (tile < t_end) fetch(tile);
@@ -571,15 +583,21 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
         } else
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
-            const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
-            const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
             bf16x4_t pa, pb, qa, qb;
-            if constexpr (X3) {
-                mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
-                mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+            if constexpr (U8) {      // out-of-image items commit zeros (the conv's padding), not decode(0) = -1
+                const int row = (l_lds[i] >> 18) & 31, pair = l_lds[i] >> 24;
+                const bool ok = (unsigned)(2 * PH * ty - 3 + row) < (unsigned)H2 && (unsigned)(64 * tx - 8 + 4 * pair) < (unsigned)W;
+                mil_u8_item<X3>(r0[i], r1[i], ok, pa, pb, qa, qb);
             } else {
+                const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
+                const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
+                if constexpr (X3) {
+                    mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
+                    mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                    for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                }
             }
             char* dst = ldsX + (l_lds[i] & 0xFFFF);
             *reinterpret_cast<bf16x4_t*>(dst) = pa;
@@ -776,14 +794,20 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) {
 }
 
 template <bool X3, bool FROM_XS>
+__global__ __launch_bounds__(256, 2) void stem_fwd_pool_kernel(StemFwdArgs a) { stem_fwd_pool_body<X3, FROM_XS, false>(a); }
+template <bool X3>
+__global__ __launch_bounds__(256, 2) void stem_fwd_pool_u8_kernel(StemFwdArgs a) { stem_fwd_pool_body<X3, false, true>(a); }
+
+template <bool X3, bool FROM_XS, bool U8 = false>
 static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
     constexpr int COUTP = 24, OESZ = X3 ? 4 : 2;
     const int lds = sp_lds_bytes<X3>();
     a.tiles_y = (a.Ho + 7) / 8;
-    auto kern = stem_fwd_pool_kernel<X3, FROM_XS>;
+    void (*kern)(StemFwdArgs);
+    if constexpr (U8) kern = stem_fwd_pool_u8_kernel<X3>; else kern = stem_fwd_pool_kernel<X3, FROM_XS>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
-    size_t per_img = FROM_XS ? 0 : (size_t)3 * a.H * a.W * 4;
+    size_t per_img = FROM_XS ? 0 : (size_t)3 * a.H * a.W * (U8 ? 1 : 4);
     const size_t xs_img = X3 ? 0 : (size_t)a.H2 * a.W2 * 32, p_img = (size_t)a.Ho * a.Wo * COUTP * OESZ;
     if (xs_img > per_img) per_img = xs_img;
     if (p_img > per_img) per_img = p_img;
@@ -793,6 +817,7 @@ static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
         StemFwdArgs b = a;
         b.n_img = n_total - i0 < chunk ? n_total - i0 : chunk;
         b.x = a.x ? a.x + (size_t)i0 * 3 * a.H * a.W : nullptr;
+        b.x8 = a.x8 ? a.x8 + (size_t)i0 * 3 * a.H * a.W : nullptr;
         b.xs_in = a.xs_in ? a.xs_in + (size_t)i0 * a.H2 * a.W2 * 16 : nullptr;
         b.xs = a.xs ? a.xs + (size_t)i0 * a.H2 * a.W2 * 16 : nullptr;
         b.pool = static_cast<char*>(a.pool) + (size_t)i0 * a.Ho * a.Wo * COUTP * OESZ;
@@ -809,7 +834,7 @@ static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
         MIL_CHECK_LAUNCH();
 #ifdef MIL_STAMP
         static const char* const ph[5] = {"convert", "barrier-x", "gemm", "maxima", "decode-store"};
-        sb.report(X3 ? "stem_fwd_pool_kernel<x3>" : "stem_fwd_pool_kernel", grid, 4, 5, ph, st);
+        sb.report(U8 ? (X3 ? "stem_fwd_pool_u8_kernel<x3>" : "stem_fwd_pool_u8_kernel") : X3 ? "stem_fwd_pool_kernel<x3>" : "stem_fwd_pool_kernel", grid, 4, 5, ph, st);
 #endif
     }
     return MIL_OK;
@@ -885,6 +910,28 @@ extern "C" int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const 
         return dtype == MIL_DT_F32S ? launch_stem_fwd_pool<true, false>(a, st) : launch_stem_fwd_pool<false, false>(a, st);
     }
     return launch_stem_fwd<4>(a, st);
+}
+
+// The same pass fed by uint8 tiles x [n,3,H,W] (planar bytes standing for ((u / 255) - 0.5) / 0.5, u8_feed.cuh): pool / widx are
+// bit-identical to mil_stem_fwd_fused(decoded tiles, xs = NULL).  20-channel stem (cout_p 24), bf16 or split precision; no
+// space-to-depth copy (the backward is mil_stem_bwd_fused_u8).  H even, W % 4 == 0, x 4-byte aligned, else MIL_ERR_UNSUPPORTED.
+extern "C" int mil_stem_fwd_fused_u8(const uint8_t* x_u8, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx,
+                                     int n_img, int H, int W, int cout_p, float slope, int dtype, void* stream) {
+    if (!x_u8 || !wpack || !pool || !widx || n_img < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
+    if ((dtype != MIL_DT_BF16 && dtype != MIL_DT_F32S) || (H & 1) || (W & 3) || (reinterpret_cast<uintptr_t>(x_u8) & 3) || slope < 0.f || slope >= 1.f)
+        return MIL_ERR_UNSUPPORTED;
+    if (cout_p != 24) return MIL_ERR_UNSUPPORTED;
+    if (n_img == 0) return MIL_OK;
+    StemFwdArgs a{};
+    a.x8 = x_u8; a.w = wpack; a.bias = bias_pad; a.pool = pool; a.widx = widx;
+    a.n_img = n_img; a.H = H; a.W = W; a.H2 = H / 2; a.W2 = W / 2;
+    a.Ho = (a.H2 - 1) / 2 + 1; a.Wo = (a.W2 - 1) / 2 + 1;
+    a.tiles_y = (a.Ho + 7) / 8; a.tiles_x = (a.Wo + 15) / 16;
+    a.slope = slope;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (mil_stem_walk_wanted(a, mil_num_cus() * 2))
+        return dtype == MIL_DT_F32S ? launch_stem_fwd_walk<true, true>(a, st) : launch_stem_fwd_walk<false, true>(a, st);
+    return dtype == MIL_DT_F32S ? launch_stem_fwd_pool<true, false, true>(a, st) : launch_stem_fwd_pool<false, false, true>(a, st);
 }
 
 // The same pass fed by the bf16 space-to-depth tensor xs [n,H2,W2,16] (mil_tile_preprocess_s2d's output, or mil_stem_s2d's):

@@ -25,8 +25,10 @@ template <bool X3> __host__ __device__ constexpr int swk_lds_bytes() {
     return 64 + swk_nring<X3>() * swk_rowb<X3>() + 256 + 160 + (X3 ? 0 : MIL_SK6_STEPS * 2 * 64 * 16);     // 64224 / 75520
 }
 
-template <bool X3>
-__global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
+// The body is shared by the fp32 feed (stem_fwd_walk_kernel) and the uint8 feed (stem_fwd_walk_u8_kernel, U8: two 4-byte loads
+// per item, decoded at the commit — mil_u8_item, u8_feed.cuh; same LDS as the fp32 feed).
+template <bool X3, bool U8>
+__device__ __forceinline__ void stem_fwd_walk_body(const StemFwdArgs& a) {
     using T = typename std::conditional<X3, F32S, BF16>::type;
     constexpr int NT = 2, COUTP = 24, NTHR = 256, KSTEPS = MIL_SK6_STEPS, KSTEPS_STD = 8;
     constexpr int XPIX = sf_xpix(X3), ROWB = swk_rowb<X3>(), NRING = swk_nring<X3>(), XBYTES = NRING * ROWB;
@@ -44,7 +46,8 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
         *reinterpret_cast<uint4*>(smem + i) = make_uint4(0, 0, 0, 0);
     smem += SPARE;
     const int H = a.H, W = a.W, H2 = a.H2, Ho = a.Ho, Wo = a.Wo;
-    const __amdgpu_buffer_rsrc_t rs_x = mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
+    const __amdgpu_buffer_rsrc_t rs_x = U8 ? mil_rsrc(a.x8, (unsigned)((size_t)a.n_img * 3 * H * W))
+                                           : mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
     const __amdgpu_buffer_rsrc_t rs_p = mil_rsrc(a.pool, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP * OESZ));
     const __amdgpu_buffer_rsrc_t rs_i = mil_rsrc(a.widx, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP));
     constexpr int W_OFF = KSTEPS_STD * NT * 64 * FRAGB;       // the SK6 k-steps sit behind the eight standard ones
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
         const int idx = tid + NTHR * i;
         const int pair = idx & 63, t = idx >> 6, c = t % 3, row = t / 3;
         l_col[i] = (4 + 2 * pair) * XPIX + c * 8;
-        l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * 4;
+        l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * (U8 ? 1 : 4);
         l_row[i] = row;
         l_c2[i] = c == 2;
     }
@@ -97,17 +100,23 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
     const float slope = a.slope;
     const int S = (Ho + 1) / 2 + 1;                             // steps per image
 
-    u32x4_t r0[NLOAD], r1[NLOAD];
+    using LoadT = typename std::conditional<U8, unsigned, u32x4_t>::type;
+    LoadT r0[NLOAD], r1[NLOAD];
     // s2d rows 4s-3 .. 4s of image img (rows outside the image: zeros)
     auto fetch = [&](int img, int s) {
         const int y0 = 4 * s - 3;
-        const int base = ((img * 3) * H + 2 * y0) * W * 4;       // negative for s = 0: its valid rows' sums are not
+        const int base = ((img * 3) * H + 2 * y0) * W * (U8 ? 1 : 4);       // negative for s = 0: its valid rows' sums are not
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
             const bool ok = (unsigned)(y0 + l_row[i]) < (unsigned)H2;
             const unsigned off = ok ? (unsigned)(base + l_rel[i]) : MIL_OOB;
-            r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
-            r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? off + (unsigned)(W * 4) : MIL_OOB, 0, 0);
+            if constexpr (U8) {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, ok ? off + (unsigned)W : MIL_OOB, 0, 0);
+            } else {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? off + (unsigned)(W * 4) : MIL_OOB, 0, 0);
+            }
         }
     };
     float h0[8];                                                // horizontal maxima of the previous step's last stem row
@@ -125,15 +134,20 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) {
         // ---- the four new s2d rows: fp32 -> bf16 (hi / lo halves in split precision), channel = c*4 + dy*2 + dx ----------------
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i) {
-            const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
-            const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
             bf16x4_t pa, pb, qa, qb;
-            if constexpr (X3) {
-                mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
-                mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+            if constexpr (U8) {      // s2d rows above / below the image commit zeros (the conv's padding), not decode(0) = -1
+                const bool ok = (unsigned)(4 * s - 3 + l_row[i]) < (unsigned)H2;
+                mil_u8_item<X3>(r0[i], r1[i], ok, pa, pb, qa, qb);
             } else {
+                const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
+                const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
+                if constexpr (X3) {
+                    mil_split4(f32x4_t{fa[0], fa[1], fa[2], fa[3]}, pa, qa);
+                    mil_split4(f32x4_t{fb[0], fb[1], fb[2], fb[3]}, pb, qb);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                    for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                }
             }
             int rr = base4 + l_row[i];
             rr = rr >= NRING ? rr - NRING : rr;
@@ -355,13 +369,19 @@ static bool mil_stem_walk_wanted(const StemFwdArgs& a, int grid_cap) {
 }
 
 template <bool X3>
+__global__ __launch_bounds__(256, 2) void stem_fwd_walk_kernel(StemFwdArgs a) { stem_fwd_walk_body<X3, false>(a); }
+template <bool X3>
+__global__ __launch_bounds__(256, 2) void stem_fwd_walk_u8_kernel(StemFwdArgs a) { stem_fwd_walk_body<X3, true>(a); }
+
+template <bool X3, bool U8 = false>
 static int launch_stem_fwd_walk(StemFwdArgs a, hipStream_t st) {
     constexpr int COUTP = 24, OESZ = X3 ? 4 : 2;
     const int lds = swk_lds_bytes<X3>();
-    auto kern = stem_fwd_walk_kernel<X3>;
+    void (*kern)(StemFwdArgs);
+    if constexpr (U8) kern = stem_fwd_walk_u8_kernel<X3>; else kern = stem_fwd_walk_kernel<X3>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
-    size_t per_img = (size_t)3 * a.H * a.W * 4;
+    size_t per_img = (size_t)3 * a.H * a.W * (U8 ? 1 : 4);
     const size_t p_img = (size_t)a.Ho * a.Wo * COUTP * OESZ;
     if (p_img > per_img) per_img = p_img;
     const int chunk = mil_imgs_under_2g(per_img);
@@ -369,7 +389,8 @@ static int launch_stem_fwd_walk(StemFwdArgs a, hipStream_t st) {
     for (int i0 = 0; i0 < n_total; i0 += chunk) {
         StemFwdArgs b = a;
         b.n_img = n_total - i0 < chunk ? n_total - i0 : chunk;
-        b.x = a.x + (size_t)i0 * 3 * a.H * a.W;
+        b.x = a.x ? a.x + (size_t)i0 * 3 * a.H * a.W : nullptr;
+        b.x8 = a.x8 ? a.x8 + (size_t)i0 * 3 * a.H * a.W : nullptr;
         b.pool = static_cast<char*>(a.pool) + (size_t)i0 * a.Ho * a.Wo * COUTP * OESZ;
         b.widx = a.widx + (size_t)i0 * a.Ho * a.Wo * COUTP;
         int grid = mil_num_cus() * mil_resident_per_cu(kern, lds, 2);
@@ -382,7 +403,7 @@ static int launch_stem_fwd_walk(StemFwdArgs a, hipStream_t st) {
         MIL_CHECK_LAUNCH();
 #ifdef MIL_STAMP
         static const char* const ph[5] = {"convert", "barrier-x", "gemm", "maxima", "decode-store"};
-        sb.report(X3 ? "stem_fwd_walk_kernel<x3>" : "stem_fwd_walk_kernel", grid, 4, 5, ph, st);
+        sb.report(U8 ? (X3 ? "stem_fwd_walk_u8_kernel<x3>" : "stem_fwd_walk_u8_kernel") : X3 ? "stem_fwd_walk_kernel<x3>" : "stem_fwd_walk_kernel", grid, 4, 5, ph, st);
 #endif
     }
     return MIL_OK;

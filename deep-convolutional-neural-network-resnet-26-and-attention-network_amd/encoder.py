@@ -204,10 +204,13 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         """x: fp32 [T,3,H,W] tiles (the reference's tensor), or `preprocess.S2dTiles` — the same tiles as the bf16
-        space-to-depth tensor the stem kernels read (bf16 compute mode only)."""
-        from .preprocess import S2dTiles
+        space-to-depth tensor the stem kernels read (bf16 compute mode only) — or `preprocess.U8Tiles`, the same tiles as
+        the uint8 images they are (every compute mode; a CPU handle is moved to the module's device as uint8)."""
+        from .preprocess import S2dTiles, U8Tiles
         if isinstance(x, S2dTiles):
             x = x.xs
+        elif isinstance(x, U8Tiles):
+            x = x.u8.to(self.conv1.weight.device)
         return _EncoderFn.apply(self, x, *self.encoder_params())
 
 
@@ -224,7 +227,43 @@ def encoder_forward(net, x, dtype):
         if dtype != torch.bfloat16:
             raise ValueError("space-to-depth bf16 tiles feed the bf16 compute mode only (the fp32 modes take fp32 [T,3,H,W] tiles)")
         return _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in=x)
+    if x.dtype == torch.uint8:          # the tiles arrive as the uint8 images they are (preprocess.U8Tiles): every compute mode
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"a uint8 input must be the planar tile stack [T,3,H,W], got {tuple(x.shape)}")
+        return _encoder_forward_from_u8(net, x, dtype, hk, stem_hooked, wp, bp)
     return _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in=None)
+
+
+def _encoder_forward_from_u8(net, x, dtype, hk, stem_hooked, wp, bp):
+    """The stem of `_encoder_forward_from` for uint8 tiles: the decisions the fp32 input takes (fused forward or the three-call
+    chain, what the backward re-reads), the uint8 tensor saved in place of the fp32 one.  Nothing converts the stack to fp32
+    (a hooked stem is handed `U8Tiles(x).float()`, as the reference's hook would see)."""
+    if net.keep_s2d:
+        x = x.clone()                   # `keep_s2d`: a library-owned copy for the backward — here the uint8 tensor itself
+    fused = ops.stem_fwd_fused_u8(x, wp, bp, ops.cpad(STEM_WIDTH), dtype=dtype) if (net.fuse_stem_forward and not stem_hooked) else None
+    split = dtype == torch.float32 and L.dt_code(dtype, mma=True) == L.MIL_DT_F32S
+    xs = None
+    if fused is not None:
+        pool, widx = fused
+        stem_hw = (x.shape[2] // 2, x.shape[3] // 2)
+        if not net.fuse_backward and not split:      # the un-fused backward wants the s2d tensor anyway (as keep_s2d of the fp32 feed)
+            xs = ops.stem_s2d_u8(x, dtype)
+    else:
+        xs = ops.stem_s2d_u8(x, dtype)
+        stem = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=True)
+        pool, widx = ops.maxpool_fwd(stem)
+        stem_hw = tuple(stem.shape[1:3])
+        if stem_hooked:                 # the hooked children see what the reference's would (NCHW fp32, 20 channels)
+            if hooks.hooked(net.conv1):
+                from .preprocess import U8Tiles
+                pre = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=False)
+                hooks.fire(net.conv1, U8Tiles(x).float(), hooks.nchw(pre, STEM_WIDTH))
+            stem_v = hooks.nchw(stem, STEM_WIDTH)
+            hooks.fire(net.relu, stem_v, stem_v)
+            hooks.fire(net.maxpool, stem_v, hooks.nchw(pool, STEM_WIDTH))
+    saved = {"xs": xs, "x": x if xs is None else None, "x_src": x if xs is None else None,
+             "x_version": x._version, "stem_hw": stem_hw, "widx": widx, "blocks": []}
+    return _encoder_forward_body(net, pool, saved, dtype, hk)
 
 
 def _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in):
@@ -262,6 +301,11 @@ def _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in):
     src = xs_in if xs_in is not None else x             # the caller's tensor the backward re-reads
     saved = {"xs": xs, "x": x if xs is None else None, "x_src": src if (xs is None or xs_in is not None) else None,
              "x_version": src._version, "stem_hw": stem_hw, "widx": widx, "blocks": []}
+    return _encoder_forward_body(net, pool, saved, dtype, hk)
+
+
+def _encoder_forward_body(net, pool, saved, dtype, hk):
+    """Everything behind the stem: the residual stages, the average pool and the fc layer."""
     t = pool
     stage_in = pool
     all_blocks = list(net.blocks())
@@ -559,8 +603,8 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         if net.fuse_backward:               # pool backward + lrelu backward + stem wgrad in one pass (bf16 path)
             stem_ws = (lambda nb: batch.workspace(("s", 0), nb)) if batch is not None else None
             if saved["xs"] is None:
-                fused_stem = ops.stem_bwd_fused_nchw(saved["x"], dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias),
-                                                     ws_alloc=stem_ws)
+                stem_bwd = ops.stem_bwd_fused_u8 if saved["x"].dtype == torch.uint8 else ops.stem_bwd_fused_nchw
+                fused_stem = stem_bwd(saved["x"], dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias), ws_alloc=stem_ws)
             else:
                 fused_stem = ops.stem_bwd_fused(saved["xs"], dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias),
                                                 ws_alloc=stem_ws)
@@ -571,7 +615,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         else:
             dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
             if saved["xs"] is None:
-                saved["xs"] = ops.stem_s2d(saved["x"], dz.dtype)
+                saved["xs"] = (ops.stem_s2d_u8 if saved["x"].dtype == torch.uint8 else ops.stem_s2d)(saved["x"], dz.dtype)
             grads["stem"] = wgrad(saved["xs"], dstem, 3, STEM_WIDTH, key=("stem", 0), ks=4, stride=1, pad=2, stem=True,
                                   out=gout(net.conv1.weight, net.conv1.bias))
 

@@ -16,7 +16,9 @@ from . import ops
 from ._lib import BF16X3
 from .encoder import BasicResBlock, ResNet
 from .head import DROP_P, SMOOTHING, BagLayout, head_apply
-from .preprocess import S2dTiles
+from .preprocess import S2dTiles, U8Tiles
+
+_HANDLES = (S2dTiles, U8Tiles)        # tile stacks handed over in a form the stem kernels read directly
 
 SUBSAMPLE = 0.2     # gbm/model.py:193
 
@@ -178,7 +180,8 @@ class Attention(nn.Module):
     # ---- a batch of bags: one encoder pass over all tiles, segmented head --------------------------
     def forward_bags(self, bags, labels):
         """bags: list of [N_b,3,H,W] fp32 tensors (same H,W), or (x_all [sum N_b,3,H,W], [N_b...]) when the
-        tiles already sit back to back in one tensor; labels: [n_bags].  Returns one output dict per bag
+        tiles already sit back to back in one tensor; labels: [n_bags].  In place of an fp32 tensor: `U8Tiles` (the uint8
+        images, every compute mode) or `S2dTiles` (bf16 mode), one kind per call.  Returns one output dict per bag
         (keys/shapes/grad flags of gbm/model.py:249-264); each `loss` back-propagates."""
         dev = self.weight_mask.device
         if dev.type != "cuda":
@@ -190,6 +193,8 @@ class Attention(nn.Module):
             if self.training:      # per-bag subsampling needs the bags separately
                 if isinstance(x_cat, S2dTiles):
                     bags = [S2dTiles(t) for t in torch.split(x_cat.xs, list(cat_sizes), dim=0)]
+                elif isinstance(x_cat, U8Tiles):
+                    bags = [U8Tiles(t) for t in torch.split(x_cat.u8, list(cat_sizes), dim=0)]
                 else:
                     bags = list(torch.split(x_cat, list(cat_sizes), dim=0))
             else:
@@ -198,7 +203,7 @@ class Attention(nn.Module):
         if bags is None:
             if x_cat.dim() != 4 or x_cat.shape[1] != 3:
                 raise ValueError(f"expected [N,3,H,W], got {tuple(x_cat.shape)}")
-            tiles, sizes, bags = [x_cat.detach() if isinstance(x_cat, S2dTiles) else x_cat.detach().to(dev, torch.float32)], list(cat_sizes), []
+            tiles, sizes, bags = [x_cat.detach() if isinstance(x_cat, _HANDLES) else x_cat.detach().to(dev, torch.float32)], list(cat_sizes), []
         for b, x in enumerate(bags):
             x = x.detach()
             if x.dim() != 4 or x.shape[1] != 3:
@@ -209,15 +214,18 @@ class Attention(nn.Module):
                 else:
                     idx = torch.randperm(x.shape[0])[: int(x.shape[0] * SUBSAMPLE)]
                 x = x[idx.to(x.device)]
-            tiles.append(x if isinstance(x, S2dTiles) else x.to(dev, torch.float32))
+            tiles.append(x if isinstance(x, _HANDLES) else x.to(dev, torch.float32))
             sizes.append(x.shape[0])
         layout = BagLayout.cached(sizes, dev)
-        if any(isinstance(t, S2dTiles) for t in tiles):
-            if not all(isinstance(t, S2dTiles) for t in tiles):
-                raise ValueError("bags of one call must all be fp32 tile stacks or all S2dTiles")
-            if any(t.device != dev for t in tiles):
+        if any(isinstance(t, _HANDLES) for t in tiles):
+            kind = type(next(t for t in tiles if isinstance(t, _HANDLES)))
+            if not all(type(t) is kind for t in tiles):
+                raise ValueError("bags of one call must all be fp32 tile stacks, all S2dTiles or all U8Tiles")
+            if kind is U8Tiles:
+                tiles = [t.to(dev) for t in tiles]          # a CPU handle moves as uint8: a quarter of the fp32 stack's bytes
+            elif any(t.device != dev for t in tiles):
                 raise ValueError("S2dTiles must live on the module's device")
-            x_all = tiles[0] if len(tiles) == 1 else S2dTiles.cat(tiles)
+            x_all = tiles[0] if len(tiles) == 1 else kind.cat(tiles)
         else:
             x_all = tiles[0] if len(tiles) == 1 else torch.cat(tiles, dim=0)
         if self.training:
@@ -286,7 +294,7 @@ class Attention(nn.Module):
         if Y is None:
             Y = torch.tensor([1])
         with torch.no_grad():
-            h_local = self.cnn(x_slice.detach().to(dev, torch.float32))
+            h_local = self.cnn(x_slice.detach().to(dev) if isinstance(x_slice, U8Tiles) else x_slice.detach().to(dev, torch.float32))
             H = gather_features(h_local, group)
             layout = BagLayout.cached([H.shape[0]], dev)
             y = Y.to(dev).long().reshape(-1)[:1].contiguous()

@@ -106,6 +106,20 @@ def stem_s2d(x, dtype):
     return out
 
 
+def _need_u8_tiles(x):
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"expected a contiguous CUDA uint8 [N,3,H,W] tile stack, got {tuple(x.shape)} {x.dtype} on {x.device}")
+
+
+def stem_s2d_u8(x, dtype):
+    """stem_s2d from uint8 tiles [n,3,H,W] (the uint8 feed, see mil_stem_s2d_u8): bit for bit stem_s2d of the decoded tensor."""
+    _need_u8_tiles(x)
+    n, _, h, w = x.shape
+    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 16), dtype=dtype, device=x.device)
+    L.check(L.lib().mil_stem_s2d_u8(x.data_ptr(), out.data_ptr(), n, h, w, L.dt_code(dtype), L.stream_ptr()), "mil_stem_s2d_u8")
+    return out
+
+
 def pack_weights(w, bias, mode, dtype):
     """fp32 [Cout,Cin,k,k] -> (packed MFMA-fragment weights, zero-padded fp32 bias)."""
     w = w.detach()
@@ -450,6 +464,32 @@ def stem_fwd_fused(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat
     return xs, pool, widx
 
 
+def stem_fwd_fused_u8(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat16):
+    """(pool, widx) of the whole stem in one pass over uint8 tiles x [n,3,H,W] (see mil_stem_fwd_fused_u8): bit for bit
+    stem_fwd_fused(decoded tiles, keep_s2d=False).  None when the shape / dtype has no fused kernel (the caller then runs
+    stem_s2d_u8 / conv / maxpool_fwd)."""
+    _need_u8_tiles(x)
+    n, c, h, w = x.shape
+    code = L.dt_code(dtype, mma=True)
+    if code != L.MIL_DT_F32S and dtype != torch.bfloat16:
+        return None
+    if h % 2 or w % 4 or cout_p != 24 or x.data_ptr() % 4:
+        return None
+    h2, w2 = h // 2, w // 2
+    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+    pool = torch.empty((n, hp, wp, cout_p), dtype=dtype, device=x.device)
+    widx = torch.empty((n, hp, wp, cout_p), dtype=torch.uint8, device=x.device)
+    end = TIMER.bracket(("stem_fwd_u8", cout_p, n, h, w)) if TIMER else None
+    rc = L.lib().mil_stem_fwd_fused_u8(x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), pool.data_ptr(), widx.data_ptr(), n, h, w,
+                                       cout_p, slope, code, L.stream_ptr())
+    if rc == 2:
+        return None
+    L.check(rc, "mil_stem_fwd_fused_u8")
+    if end is not None:
+        end.record()
+    return pool, widx
+
+
 def stem_fwd_fused_xs(xs, wpack, bias_pad, cout_p, *, slope=LEAK):
     """(pool, widx) of the whole stem in one pass over the bf16 space-to-depth tiles xs [n,H2,W2,16] (see
     mil_stem_fwd_fused_xs), or None when the shape has no fused kernel."""
@@ -546,16 +586,62 @@ def stem_bwd_fused_nchw(x, g_pool, widx, *, workspace=None, out=None, slope=LEAK
     return dw, db
 
 
-def stem_bwd_dense_ok(src, dtype):
-    """True when the fused stem backward for this saved input (the fp32 tiles [n,3,H,W] or the s2d copy [n,H2,W2,16])
-    exists with the dense pooled-gradient layout."""
+def stem_bwd_fused_u8(x, g_pool, widx, *, workspace=None, out=None, slope=LEAK, ws_alloc=None):
+    """stem_bwd_fused_nchw reading uint8 tiles x [n,3,H,W] (see mil_stem_bwd_fused_u8); None when the shape / dtype / alignment
+    has no such kernel."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8 or not x.is_cuda or not x.is_contiguous():
+        return None
+    n, _, h, w = x.shape
+    dense = g_pool.shape[-1] == 20            # dense gradient layout (MIL_DT_BF16_DGRAD / MIL_DT_F32S_DGRAD)
     need = ctypes.c_size_t(0)
+    rc = L.lib().mil_stem_bwd_fused_u8_workspace(ctypes.byref(need), n, h, w, L.dt_code(g_pool.dtype, dense, mma=True))
+    if rc == 2 or x.data_ptr() % 4:
+        return None
+    L.check(rc, "mil_stem_bwd_fused_u8_workspace")
+    h2, w2 = h // 2, w // 2
+    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+    _need(g_pool, (n, hp, wp, 20 if dense else 24), g_pool.dtype, "g_pool")
+    _need(widx, (n, hp, wp, 24), torch.uint8, "widx")
+    if ws_alloc is not None:                 # deferred reductions: the slab buffer must outlive this call
+        workspace = ws_alloc(need.value)
+    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
+        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
+    if out is None:
+        dw = torch.empty((20, 3, 7, 7), dtype=torch.float32, device=x.device)
+        db = torch.empty(20, dtype=torch.float32, device=x.device)
+    else:
+        dw, db = out
+        _need(dw, (20, 3, 7, 7), torch.float32, "dw")
+        _need(db, (20,), torch.float32, "db")
+    end = TIMER.bracket(("stem_bwd_u8", n, h, w)) if TIMER else None
+    rc = L.lib().mil_stem_bwd_fused_u8(x.data_ptr(), g_pool.data_ptr(), widx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h, w,
+                                       slope, 0 if out is None else 1, L.dt_code(g_pool.dtype, dense, mma=True), L.stream_ptr())
+    if rc == 2:
+        return None
+    L.check(rc, "mil_stem_bwd_fused_u8")
+    if end is not None:
+        end.record()
+    return dw, db
+
+
+def stem_bwd_dense_ok(src, dtype):
+    """True when the fused stem backward for this saved input (the fp32 or uint8 tiles [n,3,H,W], or the s2d copy
+    [n,H2,W2,16]) exists with the dense pooled-gradient layout."""
+    need = ctypes.c_size_t(0)
+    if src.dim() == 4 and src.shape[1] == 3 and src.dtype == torch.uint8:
+        n, _, h, w = src.shape
+        if not src.is_contiguous() or src.data_ptr() % 4:
+            return False
+        return L.lib().mil_stem_bwd_fused_u8_workspace(ctypes.byref(need), n, h, w, L.dt_code(dtype, True, mma=True)) == 0
     if src.dim() == 4 and src.shape[1] == 3 and src.dtype == torch.float32:
         n, _, h, w = src.shape
         if not src.is_contiguous() or src.data_ptr() % 16:
             return False
         return L.lib().mil_stem_bwd_fused_nchw_workspace(ctypes.byref(need), n, h, w, L.dt_code(dtype, True, mma=True)) == 0
     n, h2, w2, _ = src.shape
+    if dtype != torch.bfloat16:         # an fp32 s2d copy (hooked or un-fused stem of the fp32 modes): no fused backward reads it
+        return False
     return L.lib().mil_stem_bwd_fused_workspace(ctypes.byref(need), n, h2, w2, L.dt_code(dtype, True)) == 0
 
 

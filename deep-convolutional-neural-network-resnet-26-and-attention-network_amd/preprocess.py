@@ -49,6 +49,64 @@ class S2dTiles:
         return S2dTiles(torch.cat([p.xs for p in parts], dim=0))
 
 
+class U8Tiles:
+    """A stack of tiles held as the 8-bit images they are: `u8 [T,3,H,W]` uint8, planar (the fp32 tensor's own indexing, one
+    byte per element), standing for the fp32 stack `((u8.float() / 255) - 0.5) / 0.5` that ToTensor + Normalize(.5,.5) makes of
+    them (RoiBuilder.py:193-210).  What `TilePreprocessor(..., out="u8")` returns and what `Attention.forward` / `forward_bags` /
+    `forward_tile_parallel` / `ResNet.forward` accept in place of the fp32 stack in EVERY compute mode: the decode is lossless,
+    so outputs and gradients are bit for bit those of the fp32 tensor, at a quarter of its bytes.  A handle on the CPU is
+    moved to the module's device as uint8.  Same surface as `S2dTiles`, plus `.float()`."""
+
+    def __init__(self, u8):
+        if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8:
+            raise ValueError(f"expected a uint8 [T,3,H,W] tensor, got {getattr(u8, 'dtype', type(u8))}")
+        if u8.dim() != 4 or u8.shape[1] != 3:
+            raise ValueError(f"expected a uint8 [T,3,H,W] tensor, got {tuple(u8.shape)}")
+        self.u8 = u8.contiguous()
+
+    @property
+    def shape(self):
+        return self.u8.shape
+
+    @property
+    def device(self):
+        return self.u8.device
+
+    def dim(self):
+        return 4
+
+    def detach(self):
+        return U8Tiles(self.u8.detach())
+
+    def to(self, device):
+        return U8Tiles(self.u8.to(device))
+
+    _decode_tables = {}
+
+    def float(self):
+        """The fp32 [T,3,H,W] tensor the handle stands for: `((u8.float() / 255) - 0.5) / 0.5` as the CPU computes it (IEEE
+        division — the definition of the decode).  The 256 values are computed once, on the host, and looked up on the
+        handle's device: a GPU's own elementwise division need not round as the host's does."""
+        dev = self.u8.device
+        tab = U8Tiles._decode_tables.get(dev)
+        if tab is None:
+            tab = (((torch.arange(256, dtype=torch.uint8).float() / 255) - 0.5) / 0.5).to(dev)
+            U8Tiles._decode_tables[dev] = tab
+        return tab[self.u8.to(torch.int32)]
+
+    def __len__(self):
+        return self.u8.shape[0]
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, (torch.Tensor, slice)):
+            raise TypeError("U8Tiles are indexed with a tensor or a slice (a selection of tiles)")
+        return U8Tiles(self.u8[idx])
+
+    @staticmethod
+    def cat(parts):
+        return U8Tiles(torch.cat([p.u8 for p in parts], dim=0))
+
+
 class TilePreprocessor:
     """`update_resolution_and_buffer(resolution)` + the two transform chains for ROIs of `roi_size` pixels."""
 
@@ -85,10 +143,11 @@ class TilePreprocessor:
     def __call__(self, rois, params=None, out="nchw"):
         """rois: uint8 [T,S,S,3] on the GPU (the cached `data_cache` array).  params: int32 [T,4] from `draw_params`
         (train chain) or None (validation chain).  Returns fp32 [T,3,R,R] in [-1,1] (out="nchw": the reference's tensor), or
-        — out="s2d" — the same tiles as `S2dTiles` (bf16 space-to-depth, what the stem kernels read: the fp32 stack is never
-        materialised)."""
-        if out not in ("nchw", "s2d"):
-            raise ValueError("out must be 'nchw' or 's2d'")
+        — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
+        — out="s2d" — as `S2dTiles` (bf16 space-to-depth: the bf16 compute mode only).  With either handle the fp32 stack is
+        never materialised."""
+        if out not in ("nchw", "s2d", "u8"):
+            raise ValueError("out must be 'nchw', 's2d' or 'u8'")
         if out == "s2d" and self.resolution % 2:
             raise ValueError("the space-to-depth output needs an even resolution")
         if rois.dtype != torch.uint8 or rois.dim() != 4 or rois.shape[3] != 3 or rois.shape[1] != rois.shape[2]:
@@ -111,6 +170,9 @@ class TilePreprocessor:
         if out == "s2d":
             res = torch.empty((t, r // 2, r // 2, 16), dtype=torch.bfloat16, device=rois.device)
             fn, what = L.lib().mil_tile_preprocess_s2d, "mil_tile_preprocess_s2d"
+        elif out == "u8":
+            res = torch.empty((t, 3, r, r), dtype=torch.uint8, device=rois.device)
+            fn, what = L.lib().mil_tile_preprocess_u8, "mil_tile_preprocess_u8"
         else:
             res = torch.empty((t, 3, r, r), dtype=torch.float32, device=rois.device)
             fn, what = L.lib().mil_tile_preprocess, "mil_tile_preprocess"
@@ -121,4 +183,4 @@ class TilePreprocessor:
                        self.bounds_host.ctypes.data, b.data_ptr(), k.data_ptr(), res[done:].data_ptr(),
                        n, self.roi_size, self.pad, r, L.stream_ptr()), what)
             done += n
-        return S2dTiles(res) if out == "s2d" else res
+        return S2dTiles(res) if out == "s2d" else U8Tiles(res) if out == "u8" else res

@@ -30,8 +30,9 @@
  *                          40 -> 60 and 60 -> 80 channels, i.e. padded 24 -> 40, 40 -> 64, 64 -> 80), mil_conv_wgrad_pair
  *                          (20 -> 40 channels), mil_conv_dgrad_s2 (all three entries: 40 -> 20, 60 -> 40 and 80 -> 60
  *                          channels; the dense-output code MIL_DT_F32S_DGRAD only for the 40 -> 20 entry, cz_p == 40),
- *                          mil_stem_fwd_fused (xs must be null: no space-to-depth copy) and
- *                          mil_stem_bwd_fused_nchw(_workspace); every pointwise entry point takes MIL_DT_F32 for the same tensors.
+ *                          mil_stem_fwd_fused (xs must be null: no space-to-depth copy),
+ *                          mil_stem_bwd_fused_nchw(_workspace) and their uint8-feed forms mil_stem_fwd_fused_u8 and
+ *                          mil_stem_bwd_fused_u8(_workspace); every pointwise entry point takes MIL_DT_F32 for the same tensors.
  *   - master weights, biases, all gradients of parameters, and the whole MIL head are fp32.
  */
 #ifndef MIL_HIP_H
@@ -88,6 +89,19 @@ int mil_split_probe(const float* v, uint16_t* hi, uint16_t* lo, int n, void* str
  * NHWC space-to-depth [n, ceil(H/2), ceil(W/2), 16] of `dtype` (channel = c*4+dy*2+dx, 12 real).
  * Lets the 7x7 stride-2 stem conv (gbm/model.py:24) run as a 4x4 stride-1 implicit GEMM. */
 int mil_stem_s2d(const float* x_nchw, void* out, int n, int H, int W, int dtype, void* stream);
+
+/* ---- the uint8 tile feed ------------------------------------------------------------------
+ * Every tile the reference's model sees is an 8-bit image behind ToTensor + Normalize(.5,.5) (RoiBuilder.py:193-210): each
+ * element of the fp32 [n,3,H,W] tensor is one of 256 values, v = ((u / 255) - 0.5) / 0.5.  The *_u8 entry points take the bytes
+ * themselves, x_u8 [n,3,H,W] planar (the fp32 tensor's own indexing, a quarter of its size), and decode them on their way into
+ * LDS (reciprocal product + one Newton step = the correctly rounded u / 255 for all 256 codes, then one fma): results are bit
+ * for bit those of the fp32 entry point on the decoded tensor, in every compute mode.  Conv zero padding stays 0.0 (code 0
+ * decodes to -1: out-of-image loads are committed as zeros).
+ * mil_u8_decode_table (HOST): out256[u] = the fp32 value code u decodes to — the kernels' own expression, compiled for the host. */
+int mil_u8_decode_table(float* out256);
+/* mil_stem_s2d from uint8 tiles: out is bit-identical to mil_stem_s2d of the decoded tensor (MIL_DT_F32 / MIL_DT_BF16).  The
+ * feed of the exact-fp32 mode, and of the other two wherever the fused kernels below answer MIL_ERR_UNSUPPORTED. */
+int mil_stem_s2d_u8(const uint8_t* x_u8, void* out, int n, int H, int W, int dtype, void* stream);
 
 /* ---- weight packing -----------------------------------------------------------------------
  * fp32 master weights in the reference state-dict layout [Cout][Cin][k][k] ->
@@ -173,6 +187,11 @@ int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, const int32_
  * that mil_stem_fwd_fused_xs / mil_stem_bwd_fused read: values = the bf16 roundings of mil_tile_preprocess's.  R even. */
 int mil_tile_preprocess_s2d(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                             const int32_t* kk_dev, void* xs, int T, int S, int pad, int R, void* stream);
+/* Same chain, output left as bytes: out [T,3,R,R] uint8 planar = Pillow's resized (cropped, flipped) image before ToTensor +
+ * Normalize (RoiBuilder.py:203-204 are the stem kernels' decode table).  Lossless: the uint8 feed decodes it to exactly
+ * mil_tile_preprocess's values, so it serves all three compute modes.  Any R. */
+int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                           const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream);
 
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
@@ -275,6 +294,13 @@ int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const float* bias
  * channels 12-15 of its LDS copy of a record; the tensor's own padding channels are not read and need not be zero.) */
 int mil_stem_fwd_fused_xs(const void* xs, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx, int n_img,
                           int H2, int W2, int cout_p, float slope, int dtype, void* stream);
+/* The same pass fed by uint8 tiles x_u8 [n,3,H,W] (the uint8 feed above; RoiBuilder.py:203-204 -> gbm/model.py:24-26,51-53 without
+ * the fp32 stack in between): mil_stem_fwd_fused with xs == NULL, cout_p == 24, dtype MIL_DT_BF16 or MIL_DT_F32S.  pool / widx are
+ * bit-identical to mil_stem_fwd_fused on the decoded tiles; the tiled and the row-walk kernel are chosen by the same rule
+ * (MIL_STEM_WALK included).  H even, W % 4 == 0, x_u8 4-byte aligned, else MIL_ERR_UNSUPPORTED (the caller then runs
+ * mil_stem_s2d_u8 / mil_conv_igemm / mil_maxpool_fwd).  The backward is mil_stem_bwd_fused_u8. */
+int mil_stem_fwd_fused_u8(const uint8_t* x_u8, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx, int n_img,
+                          int H, int W, int cout_p, float slope, int dtype, void* stream);
 
 /* Fused backward of the whole stem (bf16 path): max-pool backward + LeakyReLU backward + the 7x7 conv's weight
  * and bias gradient in one pass over xs [n,H2,W2,16] (mil_stem_s2d output), g_pool [n,Hp,Wp,24] (gradient of
@@ -295,6 +321,16 @@ int mil_stem_bwd_fused_nchw_workspace(size_t* bytes, int n, int H, int W, int dt
 int mil_stem_bwd_fused_nchw(const float* x_nchw, const void* g_pool, const uint8_t* widx, float* dw, float* db,
                             void* workspace, size_t workspace_bytes, int n, int H, int W, float slope, int accumulate,
                             int dtype, void* stream);
+/* mil_stem_bwd_fused_nchw reading uint8 tiles x_u8 [n,3,H,W] (the uint8 feed above), for the same four dtype codes (MIL_DT_BF16,
+ * MIL_DT_BF16_DGRAD, MIL_DT_F32S, MIL_DT_F32S_DGRAD).  dW / db are bit-identical to the TILED form of mil_stem_bwd_fused_nchw on
+ * the decoded tiles (same tiles, same slabs, same reduction).  The bf16 row-walk backward reads fp32 tiles only: this feed runs
+ * the tiled kernel at every size, so against a row-walk run of the fp32 feed dW / db agree to fp32 summation order.  H even,
+ * W % 4 == 0, x_u8 4-byte aligned, else MIL_ERR_UNSUPPORTED (the caller then runs mil_maxpool_bwd + mil_stem_s2d_u8 +
+ * mil_conv_wgrad). */
+int mil_stem_bwd_fused_u8_workspace(size_t* bytes, int n, int H, int W, int dtype);
+int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, const uint8_t* widx, float* dw, float* db,
+                          void* workspace, size_t workspace_bytes, int n, int H, int W, float slope, int accumulate,
+                          int dtype, void* stream);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten + Linear(80,L,bias=False) (gbm/model.py:31-32,58-60).
  * x [n,hw,cp] -> pooled [n,c] fp32 (kept for backward), feats [n,nf] fp32 = pooled @ wfc^T (+ bias when given:
