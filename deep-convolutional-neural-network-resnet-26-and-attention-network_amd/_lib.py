@@ -11,8 +11,11 @@ import threading
 import torch  # noqa: F401  (must be imported first: the HIP runtime torch loaded is the one we bind to)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MIL_LIB_PATH selects another build of the same library (the NaN-poisoned diagnostic build, `make -C csrc POISON=1`)
+# MIL_LIB_PATH selects another build of the same library.  build() also makes POISON_LIB_PATH, the diagnostic build whose
+# kernels NaN-fill their dynamic and static LDS at entry; tests/test_gpu_poison.py runs the GPU suites on it in a child process
+# (nothing else loads it)
 LIB_PATH = os.environ.get("MIL_LIB_PATH") or os.path.join(_HERE, "libmil_hip.so")
+POISON_LIB_PATH = os.path.join(_HERE, "libmil_hip_poison.so")
 
 MIL_DT_F32, MIL_DT_BF16, MIL_DT_BF16_DGRAD, MIL_DT_F32S, MIL_DT_F32S_DGRAD = 0, 1, 2, 3, 4
 # compute_dtype value of the split-precision path: fp32 tensors (every pointwise kernel of the fp32 path), convolutions
@@ -26,15 +29,17 @@ class MilLibraryError(RuntimeError):
     pass
 
 
-def build_library(verbose=False):
-    """Compile every HIP source for gfx950 into libmil_hip.so (hipcc cross-compiles without a GPU)."""
-    cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j", str(min(8, os.cpu_count() or 1))]
+def build_library(verbose=False, poison=False):
+    """Compile every HIP source for gfx950 into libmil_hip.so (hipcc cross-compiles without a GPU); poison=True: into
+    libmil_hip_poison.so with -DMIL_POISON_LDS (objects of its own under csrc/build_poison)."""
+    cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j", str(min(8, os.cpu_count() or 1))] + (["POISON=1"] if poison else [])
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    out = POISON_LIB_PATH if poison else os.path.join(_HERE, "libmil_hip.so")
     if verbose or res.returncode != 0:
         print(res.stdout)
     if res.returncode != 0:
-        raise MilLibraryError("building libmil_hip.so failed")
-    return LIB_PATH
+        raise MilLibraryError(f"building {os.path.basename(out)} failed")
+    return out
 
 
 _c = ctypes

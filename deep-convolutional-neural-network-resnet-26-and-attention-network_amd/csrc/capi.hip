@@ -61,4 +61,20 @@ extern "C" int mil_poison_probe(unsigned* out, int lds_bytes, void* stream) {
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
+// The same for MIL_POISON_STATIC: a two-dimensional static array and a static scalar, as the kernels declare them.
+// out[0 .. PROBE_STATIC_WORDS) = the array's words, out[PROBE_STATIC_WORDS] = the scalar.
+#define PROBE_STATIC_WORDS (13 * 83)
+__global__ void poison_static_probe_kernel(unsigned* out) {
+    __shared__ float arr[13][83];
+    __shared__ int one;
+    MIL_POISON_STATIC(arr); MIL_POISON_STATIC(one);
+    for (int i = threadIdx.x; i < PROBE_STATIC_WORDS; i += blockDim.x) out[i] = reinterpret_cast<const unsigned*>(&arr)[i];
+    if (threadIdx.x == 0) out[PROBE_STATIC_WORDS] = (unsigned)one;
+}
+extern "C" int mil_poison_static_probe(unsigned* out, int words, int threads, void* stream) {
+    if (!out || words != PROBE_STATIC_WORDS + 1 || threads < 1 || threads > 1024) return MIL_ERR_ARG;
+    hipLaunchKernelGGL(poison_static_probe_kernel, dim3(1), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), out);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
 #endif

@@ -216,8 +216,18 @@ __device__ __forceinline__ void mil_poison_lds(void* base) {
     __syncthreads();
 }
 #define MIL_POISON(base) mil_poison_lds(base)
+// The same for a STATIC `__shared__` object (the implicit argument above counts the dynamic segment only): the named array
+// (or scalar) is filled word by word by the whole workgroup, at kernel entry, before the first LDS access.  Every static
+// array gets one, also where the kernel provably writes all of it first (tests/test_cpu_poison.py audits the sources).
+__device__ __forceinline__ void mil_poison_static(unsigned* w, unsigned words) {
+    for (unsigned i = threadIdx.x; i < words; i += blockDim.x) w[i] = 0x7FC07FC0u;
+    __syncthreads();
+}
+#define MIL_POISON_STATIC(arr) do { static_assert(sizeof(arr) % 4 == 0, "whole words"); \
+                                    mil_poison_static(reinterpret_cast<unsigned*>(&(arr)), sizeof(arr) / 4); } while (0)
 #else
 #define MIL_POISON(base) ((void)0)
+#define MIL_POISON_STATIC(arr) ((void)0)
 #endif
 
 // The only environment the library reads: five TEST knobs that drive small inputs through the large-launch paths, read on

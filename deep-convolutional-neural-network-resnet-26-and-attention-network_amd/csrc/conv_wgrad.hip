@@ -401,6 +401,7 @@ MilDeferState& mil_defer_state() { return g_defer; }
 
 __global__ __launch_bounds__(32 * MIL_RED_GROUPS) void wgrad_reduce_job_kernel(MilReduceJob j) {
     __shared__ f32x4_t part[MIL_RED_GROUPS][32];
+    MIL_POISON_STATIC(part);
     mil_reduce_job_block(j, blockIdx.x, part);
 }
 
@@ -409,6 +410,7 @@ __global__ __launch_bounds__(32 * MIL_RED_GROUPS) void wgrad_reduce_job_kernel(M
 __global__ __launch_bounds__(32 * MIL_RED_GROUPS) void wgrad_reduce_all_kernel(const MilReduceJob* __restrict__ jobs, int njobs) {
     __shared__ f32x4_t part[MIL_RED_GROUPS][32];
     __shared__ int which;
+    MIL_POISON_STATIC(part); MIL_POISON_STATIC(which);
     const int b = blockIdx.x;
     if (threadIdx.x < 64) {
         bool mine = false;

@@ -44,6 +44,7 @@ __global__ __launch_bounds__(1024) void head_colstats_kernel(const float* __rest
     __shared__ float part[HP][HL];
     __shared__ float mu_s[HL];
     __shared__ float red[16];
+    MIL_POISON_STATIC(part); MIL_POISON_STATIC(mu_s); MIL_POISON_STATIC(red);
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n0 = off[b], n1 = off[b + 1], N = n1 - n0;
     const int i = tid % HL, p = tid / HL;
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(256) void head_inst_fwd_kernel(const float* __restr
                                                             float slope, float keep_scale) {
     __shared__ __attribute__((aligned(16))) float strip[4][2 * HL + 2 * HD];      // per wave: z[80] m[80] t[40] lv[40]
     __shared__ float w2[HK * HD], wc[HD];
+    MIL_POISON_STATIC(strip); MIL_POISON_STATIC(w2); MIL_POISON_STATIC(wc);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < HK * HD; i += 256) w2[i] = w.a_w2[i];
     if (tid < HD) wc[tid] = w.b_wc[tid];
@@ -174,6 +176,7 @@ __global__ __launch_bounds__(256) void head_bag_fwd_kernel(const float* __restri
                                                            float* __restrict__ a1, float* __restrict__ wrois,
                                                            float* __restrict__ rec) {
     __shared__ float red[16];
+    MIL_POISON_STATIC(red);
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n0 = off[b], n1 = off[b + 1], N = n1 - n0;
     float s0[HK], s1[HK];
@@ -264,6 +267,7 @@ __global__ __launch_bounds__(256) void head_inst_bwd_kernel(const float* __restr
                                                             float* __restrict__ db_out, float* __restrict__ dhz_out,
                                                             float* __restrict__ dH, int ntot, float slope, float keep_scale) {
     __shared__ __attribute__((aligned(16))) float strip[4][2 * HD];      // per wave: du[40] dv[40]
+    MIL_POISON_STATIC(strip);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane < HD ? lane : 0;
     const float w2j[HK] = {w.a_w2[j], w.a_w2[HD + j], w.a_w2[2 * HD + j]};
@@ -468,6 +472,7 @@ __global__ __launch_bounds__(256) void head_wgrad_reduce_kernel(const float* __r
 // l2 = 0.5*(||Wl||_F + ||Wc||_F) contributes gl2 * 0.5 * W/||W|| to the two buffer weights.
 __global__ __launch_bounds__(256) void head_l2_grad_kernel(HeadWeights w, const float* __restrict__ gl2, float* __restrict__ grads) {
     __shared__ float red[16];
+    MIL_POISON_STATIC(red);
     const int tid = threadIdx.x;
     float q1 = 0.f, q2 = 0.f;
     for (int i = tid; i < HD * HL; i += 256) { const float v = w.b_w1[i]; q1 += v * v; }
@@ -485,6 +490,7 @@ __global__ __launch_bounds__(1024) void head_bn_bwd_kernel(const float* __restri
                                                            const float* __restrict__ stats, HeadWeights w,
                                                            const float* __restrict__ dhz, float* __restrict__ dH) {
     __shared__ float p1[HP][HL], p2[HP][HL];
+    MIL_POISON_STATIC(p1); MIL_POISON_STATIC(p2);
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n0 = off[b], n1 = off[b + 1], N = n1 - n0;
     const int i = tid % HL, p = tid / HL;

@@ -295,6 +295,7 @@ __global__ void avgpool_fc_fwd_kernel(const typename T::elem* __restrict__ x, co
                                       float* __restrict__ feats, int hw, int CP, int C, int NF) {
     __shared__ float stage[4096];                            // [pixels of a chunk][CP]
     __shared__ float sp[POOL_MAXC];
+    MIL_POISON_STATIC(stage); MIL_POISON_STATIC(sp);
     const int t = blockIdx.x, tid = threadIdx.x;
     const int NG = CP >> 3, PCH = 4096 / CP;
     float s0 = 0.f, s1 = 0.f;                                // channels tid and tid + blockDim (CP <= 2 * blockDim)
@@ -335,6 +336,7 @@ __global__ void avgpool_fc_bwd_kernel(const float* __restrict__ dfeats, const fl
                                       const typename T::elem* __restrict__ act, typename T::elem* __restrict__ dz, int hw,
                                       int CP, int C, int NF, float slope) {
     __shared__ float sd[POOL_MAXC], sg[POOL_MAXC];
+    MIL_POISON_STATIC(sd); MIL_POISON_STATIC(sg);
     const int t = blockIdx.x, tid = threadIdx.x;
     for (int c = tid; c < POOL_MAXC; c += blockDim.x) sd[c] = (c < NF) ? dfeats[(size_t)t * NF + c] : 0.f;
     __syncthreads();

@@ -1258,16 +1258,23 @@ def test_launches_chunked_under_the_buffer_limit(ops, dtype, monkeypatch):
     assert rel_err(dw_cut.cpu(), dw_one.cpu()) < 1e-5
 
 
-def test_poisoned_lds_build_really_poisons():
-    """Only under MIL_LIB_PATH=<libmil_hip_poison.so> (`make -C csrc POISON=1`: every kernel fills its dynamic LDS with NaNs at
-    entry, so that a read of never-written LDS shows up as a NaN deterministically): the probe kernel must see the pattern in
-    every word of a 100 KB segment.  The whole kernel suite is then run once on that build."""
+def _poison_build():
+    """The poisoned diagnostic library (libmil_hip_poison.so, made by build() beside the shipped one) when this process runs
+    on it — tests/test_gpu_poison.py starts such a process for every GPU suite in each `-m gpu` run and requires the two
+    probe tests below to have PASSED there; in the ordinary process they have nothing to probe."""
     import ctypes
     import os
     path = os.environ.get("MIL_LIB_PATH", "")
     if "poison" not in os.path.basename(path):
         pytest.skip("runs on the poisoned diagnostic build only")
-    lib = ctypes.CDLL(path)
+    return ctypes.CDLL(path)
+
+
+def test_poisoned_lds_build_really_poisons():
+    """-DMIL_POISON_LDS: every kernel fills its dynamic LDS with NaNs at entry (MIL_POISON), so that a read of never-written
+    LDS shows up as a NaN deterministically.  The probe kernel must see the pattern in every word of a 100 KB segment."""
+    import ctypes
+    lib = _poison_build()
     lib.mil_poison_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mil_poison_probe.restype = ctypes.c_int
     nbytes = 100 * 1024
@@ -1275,6 +1282,23 @@ def test_poisoned_lds_build_really_poisons():
     assert lib.mil_poison_probe(out.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream) == 0
     torch.cuda.synchronize()
     assert bool((out == 0x7FC07FC0).all())
+
+
+def test_poisoned_static_lds_build_really_poisons():
+    """The same for static `__shared__` objects (MIL_POISON_STATIC): a [13][83] float array and an int scalar, declared as the
+    kernels declare theirs, must hold the pattern in every word — with fewer threads than words (one wave), with a block
+    that is no divisor of the word count, and with more threads than words would need."""
+    import ctypes
+    lib = _poison_build()
+    lib.mil_poison_static_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.mil_poison_static_probe.restype = ctypes.c_int
+    words = 13 * 83 + 1
+    for threads in (64, 192, 1024):
+        out = torch.zeros(words, dtype=torch.int32, device="cuda")
+        assert lib.mil_poison_static_probe(out.data_ptr(), words, threads, torch.cuda.current_stream().cuda_stream) == 0
+        torch.cuda.synchronize()
+        assert bool((out == 0x7FC07FC0).all()), threads
+    assert lib.mil_poison_static_probe(out.data_ptr(), words - 1, 64, None) == 1          # wrong size: refused, nothing launched
 
 
 def test_split_precision_operand_split_is_the_plain_subtraction():
