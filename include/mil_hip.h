@@ -193,6 +193,21 @@ int mil_tile_preprocess_s2d(const uint8_t* rois, const int32_t* params, const in
 int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                            const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream);
 
+/* Tissue selection (RoiBuilder.py:156-169, the loop body of RoiBuilder.build()): per roi_size window of a whole-slide image the
+ * integers from which the reference's two tests are decided — ImageStat.Stat(roi).stddev[0] > 5 (from sum R, sum R^2 and the
+ * pixel count) and more than 1000 pixels with h > 120, 50 < v < 210 in roi.convert('HSV').
+ *     out[t] = (sum R, sum R^2, #{pixels with h > hue_min and v_min < v < v_max}, S*S)          int64 [n,4], device
+ * Window t is the S x S interleaved-RGB uint8 image whose row y starts at byte base + win_off[t] + y * row_pitch, at any byte
+ * alignment: a slide [H,W,3] has row_pitch = 3W and win_off = (row*W + col)*3, a contiguous ROI stack [n,S,S,3] has row_pitch =
+ * 3S and win_off = t*3*S*S.  win_off is a DEVICE array [n].  base_bytes is the size of the source: loads go through buffer
+ * descriptors that end with it, a window (or part of one) outside the source reads as zeros and touches nothing else.
+ * The hue test is Pillow's rgb2hsv_row restated in integers (csrc/roi_select.hip), exact for hue_min = 120 on all 2^24 colours.
+ * 1 <= S <= 4096 (above: MIL_ERR_UNSUPPORTED, as a row_pitch so large that one row of a window leaves 31-bit offsets); null
+ * pointers, S < 1, row_pitch < 3S, n < 0, base_bytes < 0, hue_min outside [0,255]: MIL_ERR_ARG; n == 0: MIL_OK, no launch —
+ * all decided on the host before any GPU call.  Any n (launches of 65535 windows).  out is zeroed by the call (same stream). */
+int mil_roi_stats(const uint8_t* base, int64_t base_bytes, const int64_t* win_off, int64_t row_pitch, int n, int S,
+                  int hue_min, int v_min, int v_max, int64_t* out, void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
