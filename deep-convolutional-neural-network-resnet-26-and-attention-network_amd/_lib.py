@@ -69,6 +69,9 @@ _SIGS = {
     "mil_tile_preprocess": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_tile_preprocess_s2d": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_tile_preprocess_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_tile_preprocess_win": ([_vp, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_tile_preprocess_win_s2d": ([_vp, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_tile_preprocess_win_u8": ([_vp, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_roi_stats": ([_vp, _c.c_int64, _vp, _c.c_int64, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "mil_stem_fwd_fused_xs": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_stem_fwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -11,7 +11,23 @@
 //
 // One workgroup = 8 output rows of one tile: their ~8*scale + 2*support source rows are staged four at a time with
 // aligned 4-byte loads, filtered horizontally into an LDS strip [rows][res][3], then the strip is filtered vertically.
-#include "common.cuh"
+//
+// Windows of a slide (WIN = true, mil_tile_preprocess_win*): the ROI is not a tile of a contiguous stack but a window of a
+// larger image that stays where it is — row y of window t starts at byte win_off[t] + y * row_pitch of the source, at ANY byte
+// alignment, and the phase (win_off + y * pitch) & 15 changes from row to row whenever the pitch is no multiple of 16.  A
+// row is staged as the 16-byte granules of the SOURCE's own grid that hold its bytes, each fetched with one aligned load
+// and stored, unshifted, at the same granule of the LDS row: the row's first byte then sits at margin + phase instead of
+// margin, and the horizontal pass — which funnel-shifts its taps to the window start anyway — adds the row's phase to the
+// shift.  Masking: left and right of a window the slide has real pixels, and Pad() pads with zeros; every granule is ANDed
+// with the mask of its bytes that belong to the row (all ones except in the first and the last granules), so the bytes in
+// front of and behind a staged row are zero in LDS exactly as they are for a stack, and rows of the padded image outside
+// the window are stored as zeros whatever the source holds there.  Bounds: every load goes through a buffer descriptor from
+// the grid point below the workgroup's first row to the end of the source rounded up to the grid (roi_select.hip), so an
+// over-fetch in front of the first or behind the last window returns zeros; its 32-bit offsets are relative to that row
+// (host: rows of a band * pitch < 2 GiB) while win_off and y * pitch are 64-bit.  A source whose rows all start on the
+// grid — a contiguous stack with 3S % 16 == 0, a slide with base, 3W and 3 * col multiples of 16 — needs no extra granule
+// per row and stages exactly the pieces the stack kernel's fast path does.
+#include "pf_common.cuh"
 #include <cmath>
 
 #define PREP_BITS 22
@@ -29,11 +45,24 @@ struct PrepArgs {
     int T, S, pad, R, ksize;
     int margin, row_pitch;      // bytes: zero margin in front of a staged row (>= 3*pad, 4-aligned); pitch of a staged row
     int lds_h_off, lds_k_off, lds_b_off;
+    // WIN only: the source as mil_roi_stats takes it
+    const uint8_t* base_al;     // source pointer rounded down to the 16-byte grid
+    const long long* win_off;   // [T] byte offset of each window's first pixel from the (unrounded) source pointer
+    long long total;            // bytes from base_al to the grid point at or behind the end of the source
+    long long src_pitch;        // bytes between two rows of a window
+    int delta;                  // source pointer - base_al (0..15)
 };
 
 __device__ __forceinline__ unsigned prep_clip8(int v) { v >>= PREP_BITS; return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-template <int KS>
+// all ones in the bytes b of a dword with lo <= b < hi (byte 0 = the lowest address), zero elsewhere
+__device__ __forceinline__ unsigned prep_keep(int lo, int hi) {
+    lo = min(max(lo, 0), 4); hi = min(max(hi, 0), 4);
+    const unsigned mh = hi == 4 ? ~0u : (1u << (8 * hi)) - 1u, ml = lo == 4 ? ~0u : (1u << (8 * lo)) - 1u;
+    return mh & ~ml;
+}
+
+template <int KS, bool WIN>
 __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
     MIL_POISON(psm);
@@ -52,23 +81,54 @@ __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
     const int r0 = blockIdx.x * PREP_BAND, r1 = min(r0 + PREP_BAND, R);
     const int y_lo = bds[2 * r0], y_hi = bds[2 * (r1 - 1)] + bds[2 * (r1 - 1) + 1];
     const int nri = y_hi - y_lo;
-    const unsigned char* src_tile = a.rois + (size_t)t * S * S * 3;
+    const unsigned char* src_tile = WIN ? nullptr : a.rois + (size_t)t * S * S * 3;
     const int row_bytes = S * 3;
-    const bool wide = (row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(src_tile) & 3) == 0;
+    const bool wide = !WIN && (row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(src_tile) & 3) == 0;
+
+    // WIN: descriptor of this workgroup, from the grid point below the first source row it reads to the end of the source
+    // (no row: range 0).  rel0 = that row's first byte inside the descriptor; phase of source row ys = (rel0 + (ys - ys0) * pitch) & 15.
+    const long long woff = WIN ? a.win_off[t] : 0;
+    const int ys0 = WIN ? max(top + y_lo - pad, 0) : 0;
+    const long long fb = (long long)a.delta + woff + (long long)ys0 * a.src_pitch;
+    const long long B = fb & ~15ll, room = a.total - B;
+    const unsigned range = (!WIN || woff < 0 || ys0 >= S || room <= 0) ? 0u : (room > 0x80000000ll ? 0x80000000u : (unsigned)room);
+    const __amdgpu_buffer_rsrc_t rs = mil_rsrc(WIN ? a.base_al + B : nullptr, range);
+    const unsigned rel0 = (unsigned)(fb - B), spitch = (unsigned)a.src_pitch;
+    const bool grid_rows = (fb & 15) == 0 && (a.src_pitch & 15) == 0;         // every row of the window starts on the 16-byte grid
 
     // Fast path (16-byte aligned rows, <= 4 KB each): the next four source rows are fetched into registers while the
     // current four are filtered, so the global-load latency is paid once per band instead of once per row group.
     typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
-    const int ppr = row_bytes >> 4;                                   // 16-byte pieces per source row
-    const bool fast = (row_bytes & 15) == 0 && (a.margin & 15) == 0 && (reinterpret_cast<uintptr_t>(src_tile) & 15) == 0 && ppr <= 256;
+    // (WIN: granules of the source grid per row — one more than the row's own when rows may start anywhere in a granule)
+    const int ppr = WIN ? (row_bytes + (grid_rows ? 15 : 30)) >> 4 : row_bytes >> 4;      // 16-byte pieces per source row
+    const bool fast = WIN ? ppr <= 256
+                          : (row_bytes & 15) == 0 && (a.margin & 15) == 0 && (reinterpret_cast<uintptr_t>(src_tile) & 15) == 0 && ppr <= 256;
+    // WIN: granule `piece` of row j of the band (row ys of the window), masked to the bytes that are the row's
+    auto win_piece = [&](int j, int piece) -> u4_t {
+        const int ys = top + y_lo + j - pad;
+        const bool ok = j < nri && ys >= 0 && ys < S;
+        const unsigned r = rel0 + (unsigned)(ys - ys0) * spitch;
+        const u32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (r & ~15u) + 16u * (unsigned)piece : MIL_OOB, 0, 0);
+        const int lo = ok ? (int)(r & 15u) - 16 * piece : 0, hi = ok ? lo + row_bytes : 0;
+        u4_t v = q;
+        if (lo > 0 || hi < 16) {                                      // a row's first and last granules only (and rows that are not there)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) v[d] = q[d] & prep_keep(lo - 4 * d, hi - 4 * d);
+        }
+        return v;
+    };
     u4_t pre[PREP_ROWS];
     auto fetch_rows = [&](int j0) {
 #pragma unroll
         for (int i = 0; i < PREP_ROWS; ++i) {
             const int id = tid + 256 * i, jj = id / ppr, piece = id - jj * ppr;
-            const int ys = top + y_lo + j0 + jj - pad;
-            const bool ok = jj < PREP_ROWS && j0 + jj < nri && ys >= 0 && ys < S;
-            pre[i] = ok ? *reinterpret_cast<const u4_t*>(src_tile + (size_t)ys * row_bytes + piece * 16) : u4_t{0u, 0u, 0u, 0u};
+            if constexpr (WIN) {
+                pre[i] = win_piece(jj < PREP_ROWS ? j0 + jj : nri, piece);
+            } else {
+                const int ys = top + y_lo + j0 + jj - pad;
+                const bool ok = jj < PREP_ROWS && j0 + jj < nri && ys >= 0 && ys < S;
+                pre[i] = ok ? *reinterpret_cast<const u4_t*>(src_tile + (size_t)ys * row_bytes + piece * 16) : u4_t{0u, 0u, 0u, 0u};
+            }
         }
     };
     if (fast) fetch_rows(0);
@@ -83,6 +143,12 @@ __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
             }
             __syncthreads();
             if (j0 + PREP_ROWS < nri) fetch_rows(j0 + PREP_ROWS);
+        } else if constexpr (WIN) {                                   // rows of more than 4 KB: granule by granule, no prefetch
+            for (int id = tid; id < PREP_ROWS * ppr; id += 256) {
+                const int jj = id / ppr, piece = id - jj * ppr;
+                *reinterpret_cast<u4_t*>(rows + jj * a.row_pitch + a.margin + piece * 16) = win_piece(j0 + jj, piece);
+            }
+            __syncthreads();
         } else {
             for (int jj = 0; jj < PREP_ROWS; ++jj) {
                 if (j0 + jj >= nri) break;
@@ -109,11 +175,13 @@ __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
             int w[KS];
 #pragma unroll
             for (int k = 0; k < KS; ++k) w[k] = k < ksize ? kks[xr * ksize + k] : 0;
-            const int b0 = a.margin + (left - pad + xmin) * 3;
-            const int al = b0 & ~3;
-            const unsigned sh = (unsigned)(b0 & 3);
+            const int bx = a.margin + (left - pad + xmin) * 3;
             for (int jj = 0; jj < PREP_ROWS; ++jj) {
                 if (j0 + jj >= nri) break;
+                // WIN: the staged row starts its phase behind the margin (a row outside the window is all zeros: any phase does)
+                const int b0 = WIN ? bx + (int)((rel0 + (unsigned)(top + y_lo + j0 + jj - pad - ys0) * spitch) & 15u) : bx;
+                const int al = b0 & ~3;
+                const unsigned sh = (unsigned)(b0 & 3);
                 const unsigned* q = reinterpret_cast<const unsigned*>(rows + jj * a.row_pitch + al);
                 unsigned d[ND + 1], e[ND];
 #pragma unroll
@@ -249,12 +317,17 @@ extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
     return MIL_OK;
 }
 
+// Windows of a larger source (mil_tile_preprocess_win*): the source convention of mil_roi_stats.
+struct PrepWin { const uint8_t* base; int64_t base_bytes; const int64_t* win_off; int64_t row_pitch; };
+
 // out [T,3,R,R] fp32 in [-1,1] from uint8 ROIs [T,S,S,3].  params [T,4] (top, left, hflip, vflip with top/left in
 // [0, 2*pad]) selects the train chain, null the flat chain.  bounds_host is the host copy of the table (the launcher
-// sizes the LDS strip from it); bounds_dev / kk_dev are its device copies (mil_resize_coeffs(S, R)).
-static int prep_entry(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+// sizes the LDS strip from it); bounds_dev / kk_dev are its device copies (mil_resize_coeffs(S, R)).  `win` instead of `rois`:
+// the ROIs are windows of a larger source (the WIN kernels).
+static int prep_entry(const uint8_t* rois, const PrepWin* win, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                       const int32_t* kk_dev, float* out, void* xs, uint8_t* out_u8, int T, int S, int pad, int R, void* stream) {
-    if (!rois || !bounds_host || !bounds_dev || !kk_dev || (!out && !xs && !out_u8) || T < 0 || S <= 0 || R <= 0 || pad < 0) return MIL_ERR_ARG;
+    if (win && (!win->base || !win->win_off || win->base_bytes < 0 || S <= 0 || win->row_pitch < 3 * (int64_t)S)) return MIL_ERR_ARG;
+    if ((!win && !rois) || !bounds_host || !bounds_dev || !kk_dev || (!out && !xs && !out_u8) || T < 0 || S <= 0 || R <= 0 || pad < 0) return MIL_ERR_ARG;
     if (xs && ((R & 1) || (reinterpret_cast<uintptr_t>(xs) & 15))) return MIL_ERR_UNSUPPORTED;      // 2x2 blocks, 16-byte records
     if (T == 0) return MIL_OK;
     PrepArgs a{};
@@ -267,14 +340,28 @@ static int prep_entry(const uint8_t* rois, const int32_t* params, const int32_t*
         if (n > nri_max) nri_max = n;
     }
     a.margin = (3 * a.pad + 15) & ~15;
-    a.row_pitch = (a.margin + S * 3 + 3 * a.pad + 3 * 32 + 8 + 15) & ~15;       // + slack read behind the last window
+    a.row_pitch = (a.margin + S * 3 + 3 * a.pad + 3 * 32 + 8 + (win ? 16 : 0) + 15) & ~15;       // + slack read behind the last window (+ a row's phase)
     a.lds_h_off = PREP_ROWS * a.row_pitch;
     a.lds_k_off = (a.lds_h_off + nri_max * R * 3 + 15) & ~15;
     a.lds_b_off = a.lds_k_off + R * a.ksize * 4;
     const int lds = a.lds_b_off + 2 * R * 4;
     if (lds > 160 * 1024 || T > 65535 || a.ksize > 32) return MIL_ERR_UNSUPPORTED;
-    auto kern = a.ksize <= 4 ? tile_preprocess_kernel<4> : a.ksize <= 8 ? tile_preprocess_kernel<8> : a.ksize <= 12 ? tile_preprocess_kernel<12>
-              : a.ksize <= 16 ? tile_preprocess_kernel<16> : a.ksize <= 24 ? tile_preprocess_kernel<24> : tile_preprocess_kernel<32>;
+    auto kern = a.ksize <= 4 ? tile_preprocess_kernel<4, false> : a.ksize <= 8 ? tile_preprocess_kernel<8, false>
+              : a.ksize <= 12 ? tile_preprocess_kernel<12, false> : a.ksize <= 16 ? tile_preprocess_kernel<16, false>
+              : a.ksize <= 24 ? tile_preprocess_kernel<24, false> : tile_preprocess_kernel<32, false>;
+    if (win) {
+        // 32-bit offsets inside a workgroup's descriptor: the rows of a band (+ the phase row) * pitch + one row below 2 GiB
+        if (((int64_t)nri_max + 1) * win->row_pitch + 3 * (int64_t)S + 64 > (int64_t)0x7fff0000) return MIL_ERR_UNSUPPORTED;
+        const uintptr_t bp = reinterpret_cast<uintptr_t>(win->base);
+        a.delta = (int)(bp & 15);
+        a.base_al = win->base - a.delta;
+        a.total = ((int64_t)a.delta + win->base_bytes + 15) & ~(int64_t)15;
+        a.src_pitch = win->row_pitch;
+        a.win_off = reinterpret_cast<const long long*>(win->win_off);
+        kern = a.ksize <= 4 ? tile_preprocess_kernel<4, true> : a.ksize <= 8 ? tile_preprocess_kernel<8, true>
+             : a.ksize <= 12 ? tile_preprocess_kernel<12, true> : a.ksize <= 16 ? tile_preprocess_kernel<16, true>
+             : a.ksize <= 24 ? tile_preprocess_kernel<24, true> : tile_preprocess_kernel<32, true>;
+    }
     if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((R + PREP_BAND - 1) / PREP_BAND, T), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
@@ -285,7 +372,7 @@ static int prep_entry(const uint8_t* rois, const int32_t* params, const int32_t*
 extern "C" int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                                    const int32_t* kk_dev, float* out, int T, int S, int pad, int R, void* stream) {
     if (!out) return MIL_ERR_ARG;
-    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, out, nullptr, nullptr, T, S, pad, R, stream);
+    return prep_entry(rois, nullptr, params, bounds_host, bounds_dev, kk_dev, out, nullptr, nullptr, T, S, pad, R, stream);
 }
 
 // The same chain with the output left as bytes: out [T,3,R,R] uint8, planar — what Pillow's resize returns, before ToTensor +
@@ -294,7 +381,7 @@ extern "C" int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, c
 extern "C" int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                                       const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream) {
     if (!out) return MIL_ERR_ARG;
-    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, nullptr, nullptr, out, T, S, pad, R, stream);
+    return prep_entry(rois, nullptr, params, bounds_host, bounds_dev, kk_dev, nullptr, nullptr, out, T, S, pad, R, stream);
 }
 
 // The same chain with the output written as the bf16 space-to-depth NHWC tensor xs [T,R/2,R/2,16] the stem kernels read
@@ -303,5 +390,33 @@ extern "C" int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params
 extern "C" int mil_tile_preprocess_s2d(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                                        const int32_t* kk_dev, void* xs, int T, int S, int pad, int R, void* stream) {
     if (!xs) return MIL_ERR_ARG;
-    return prep_entry(rois, params, bounds_host, bounds_dev, kk_dev, nullptr, xs, nullptr, T, S, pad, R, stream);
+    return prep_entry(rois, nullptr, params, bounds_host, bounds_dev, kk_dev, nullptr, xs, nullptr, T, S, pad, R, stream);
+}
+
+// The three entries again for ROIs that are windows of a larger image left where it is (array_read_region, RoiBuilder.py:117-124,
+// followed by the chains of :193-210): row y of window t starts at byte win_off_dev[t] + y * row_pitch of `base` (base_bytes
+// long), at any alignment — the source convention of mil_roi_stats; win_off_dev [T] int64 on the device.  Everything else
+// as above; a window's result is bit for bit the one the stack entry returns for the same pixels.
+extern "C" int mil_tile_preprocess_win(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                                       const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                                       const int32_t* kk_dev, float* out, int T, int S, int pad, int R, void* stream) {
+    if (!out) return MIL_ERR_ARG;
+    const PrepWin w{base, base_bytes, win_off_dev, row_pitch};
+    return prep_entry(nullptr, &w, params, bounds_host, bounds_dev, kk_dev, out, nullptr, nullptr, T, S, pad, R, stream);
+}
+
+extern "C" int mil_tile_preprocess_win_u8(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                                          const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                                          const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream) {
+    if (!out) return MIL_ERR_ARG;
+    const PrepWin w{base, base_bytes, win_off_dev, row_pitch};
+    return prep_entry(nullptr, &w, params, bounds_host, bounds_dev, kk_dev, nullptr, nullptr, out, T, S, pad, R, stream);
+}
+
+extern "C" int mil_tile_preprocess_win_s2d(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                                           const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                                           const int32_t* kk_dev, void* xs, int T, int S, int pad, int R, void* stream) {
+    if (!xs) return MIL_ERR_ARG;
+    const PrepWin w{base, base_bytes, win_off_dev, row_pitch};
+    return prep_entry(nullptr, &w, params, bounds_host, bounds_dev, kk_dev, nullptr, xs, nullptr, T, S, pad, R, stream);
 }

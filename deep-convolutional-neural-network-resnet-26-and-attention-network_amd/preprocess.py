@@ -146,10 +146,7 @@ class TilePreprocessor:
         — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
         — out="s2d" — as `S2dTiles` (bf16 space-to-depth: the bf16 compute mode only).  With either handle the fp32 stack is
         never materialised."""
-        if out not in ("nchw", "s2d", "u8"):
-            raise ValueError("out must be 'nchw', 's2d' or 'u8'")
-        if out == "s2d" and self.resolution % 2:
-            raise ValueError("the space-to-depth output needs an even resolution")
+        self._check_out(out)
         if rois.dtype != torch.uint8 or rois.dim() != 4 or rois.shape[3] != 3 or rois.shape[1] != rois.shape[2]:
             raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(rois.shape)} {rois.dtype}")
         if rois.shape[1] != self.roi_size:
@@ -159,28 +156,88 @@ class TilePreprocessor:
         rois = rois.contiguous()
         t = rois.shape[0]
         b, k = self._tables(rois.device)
-        if params is not None:
-            params = torch.as_tensor(params, dtype=torch.int32)
-            if tuple(params.shape) != (t, 4):
-                raise ValueError("params must be int32 [T,4]")
-            if int(params[:, :2].min()) < 0 or int(params[:, :2].max()) > 2 * self.pad:
-                raise ValueError("crop offsets must lie in [0, 2*pad]")
-            params = params.to(rois.device).contiguous()
-        r = self.resolution
-        if out == "s2d":
-            res = torch.empty((t, r // 2, r // 2, 16), dtype=torch.bfloat16, device=rois.device)
-            fn, what = L.lib().mil_tile_preprocess_s2d, "mil_tile_preprocess_s2d"
-        elif out == "u8":
-            res = torch.empty((t, 3, r, r), dtype=torch.uint8, device=rois.device)
-            fn, what = L.lib().mil_tile_preprocess_u8, "mil_tile_preprocess_u8"
-        else:
-            res = torch.empty((t, 3, r, r), dtype=torch.float32, device=rois.device)
-            fn, what = L.lib().mil_tile_preprocess, "mil_tile_preprocess"
+        params = self._params(params, t, rois.device)
+        res, what = self._result(out, t, rois.device)
+        fn = getattr(L.lib(), what)
         done = 0
         while done < t:                                      # grid.y limit: 65535 tiles per launch
             n = min(t - done, 65535)
             L.check(fn(rois[done:].data_ptr(), None if params is None else params[done:].data_ptr(),
                        self.bounds_host.ctypes.data, b.data_ptr(), k.data_ptr(), res[done:].data_ptr(),
-                       n, self.roi_size, self.pad, r, L.stream_ptr()), what)
+                       n, self.roi_size, self.pad, self.resolution, L.stream_ptr()), what)
             done += n
         return S2dTiles(res) if out == "s2d" else U8Tiles(res) if out == "u8" else res
+
+    def _check_out(self, out):
+        if out not in ("nchw", "s2d", "u8"):
+            raise ValueError("out must be 'nchw', 's2d' or 'u8'")
+        if out == "s2d" and self.resolution % 2:
+            raise ValueError("the space-to-depth output needs an even resolution")
+
+    def _params(self, params, t, dev):
+        if params is None:
+            return None
+        params = torch.as_tensor(params, dtype=torch.int32)
+        if tuple(params.shape) != (t, 4):
+            raise ValueError("params must be int32 [T,4]")
+        if t and (int(params[:, :2].min()) < 0 or int(params[:, :2].max()) > 2 * self.pad):
+            raise ValueError("crop offsets must lie in [0, 2*pad]")
+        return params.to(dev).contiguous()
+
+    def _result(self, out, t, dev):
+        """(the output tensor of `t` tiles, the name of the stack entry point that fills it)."""
+        r = self.resolution
+        if out == "s2d":
+            return torch.empty((t, r // 2, r // 2, 16), dtype=torch.bfloat16, device=dev), "mil_tile_preprocess_s2d"
+        if out == "u8":
+            return torch.empty((t, 3, r, r), dtype=torch.uint8, device=dev), "mil_tile_preprocess_u8"
+        return torch.empty((t, 3, r, r), dtype=torch.float32, device=dev), "mil_tile_preprocess"
+
+    def from_slide(self, slide, coords, params=None, out="nchw"):
+        """The same chains on windows of a slide that stays where it is (`array_read_region`, RoiBuilder.py:117-124, then
+        :193-210): slide uint8 [H,W,3] on the GPU (any contiguous view, whatever its alignment), coords int [T,2] of (row, col)
+        of `roi_size` windows.  No [T,S,S,3] stack is made: the kernel reads the windows in place (mil_tile_preprocess_win*).
+        params / out / the return value as in `__call__`, bit for bit what `__call__` returns for the same windows copied into a
+        stack.  A window outside the slide raises ValueError, a slide on the CPU RuntimeError, both before any launch.  With
+        coords=None `slide` is an ROI stack [n,S,S,3]: the same kernel at row pitch 3S."""
+        self._check_out(out)
+        src, off, pitch = source_windows(slide, coords, self.roi_size)
+        if not src.is_cuda:
+            raise RuntimeError("tile pre-processing runs on an AMD GPU only (no CPU fallback)")
+        t = int(off.numel())
+        b, k = self._tables(src.device)
+        params = self._params(params, t, src.device)
+        res, what = self._result(out, t, src.device)
+        what = what.replace("mil_tile_preprocess", "mil_tile_preprocess_win")
+        fn = getattr(L.lib(), what)
+        off_dev = off.to(src.device)
+        done = 0
+        while done < t:                                      # grid.y limit: 65535 windows per launch
+            n = min(t - done, 65535)
+            L.check(fn(src.data_ptr(), src.numel(), off_dev[done:].data_ptr(), pitch,
+                       None if params is None else params[done:].data_ptr(), self.bounds_host.ctypes.data, b.data_ptr(),
+                       k.data_ptr(), res[done:].data_ptr(), n, self.roi_size, self.pad, self.resolution, L.stream_ptr()), what)
+            done += n
+        return S2dTiles(res) if out == "s2d" else U8Tiles(res) if out == "u8" else res
+
+
+def source_windows(source, coords, s):
+    """The windows of `s` pixels of a source as mil_roi_stats / mil_tile_preprocess_win* address them: (contiguous source, int64
+    CPU byte offsets [n] of each window's first pixel, row pitch in bytes).  source: uint8, a slide [H,W,3] with coords (int
+    [n,2] of (row, col)) or an ROI stack [n,s,s,3] with coords=None.  Needs no device."""
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.uint8:
+        raise ValueError(f"expected a uint8 tensor, got {getattr(source, 'dtype', type(source))}")
+    if source.dim() == 3 and source.shape[2] == 3 and coords is not None:
+        h, w = int(source.shape[0]), int(source.shape[1])
+        c = coords.detach().cpu().numpy() if isinstance(coords, torch.Tensor) else np.asarray(coords)
+        if c.size and c.dtype.kind not in "iu":
+            raise ValueError("coords must be integers")
+        c = torch.as_tensor(c.astype(np.int64).reshape(-1, 2))
+        if c.numel() and (int(c.min()) < 0 or int(c[:, 0].max()) + s > h or int(c[:, 1].max()) + s > w):
+            raise ValueError(f"a {s} x {s} window does not lie inside the {h} x {w} slide")
+        return source.contiguous(), (c[:, 0] * w + c[:, 1]) * 3, 3 * w
+    if source.dim() == 4 and source.shape[3] == 3 and coords is None:
+        if source.shape[1] != s or source.shape[2] != s:
+            raise ValueError(f"expected [n,{s},{s},3] ROIs, got {tuple(source.shape)}")
+        return source.contiguous(), torch.arange(source.shape[0], dtype=torch.int64) * (3 * s * s), 3 * s
+    raise ValueError(f"expected a slide [H,W,3] (with coords) or an ROI stack [n,S,S,3] (without), got {tuple(source.shape)}")

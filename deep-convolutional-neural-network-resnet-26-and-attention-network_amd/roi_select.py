@@ -86,6 +86,14 @@ class RoiSelector:
             return False
         return math.sqrt(var) > self.min_stddev and n_pass > self.min_pass
 
+    def kept(self, source, coords=None):
+        """`select()`'s second item — the `coor_cache`, int64 [T,2] numpy (row, col) of the kept windows (for an ROI stack their
+        indices, [T]) — without building the ROI array: `TilePreprocessor.from_slide` reads the windows where they are."""
+        src, off, pitch, c = self._windows(source, coords)
+        st = self._stats(src, off, pitch)
+        kept = [i for i in range(st.shape[0]) if self.keep(st[i].tolist())]
+        return np.asarray(kept, dtype=np.int64) if c is None else c[kept].numpy().reshape(-1, 2)
+
     def select(self, source, coords=None):
         """(rois, kept_coords): the reference's `data_cache` array — uint8 [T,S,S,3] on the GPU, in raster order, ready for
         `TilePreprocessor.__call__` — and its `coor_cache`, int64 [T,2] numpy (row, col).  For an ROI stack the second item

@@ -1,0 +1,118 @@
+"""One slide's bag of tiles without a data cache: the device-side counterpart of the reference's `RoiBuilder` in state
+VALID-READY (RoiBuilder.py:128-284).  The reference keeps two caches per slide, the kept coordinates (`coor_cache`) and the kept
+ROIs themselves (`data_cache`, [T,1200,1200,3] uint8 — 10.8 GB at its 2500-tile cap), because every epoch re-reads the ROIs
+from disk.  Here the slide is resident in HBM, `TilePreprocessor.from_slide` reads each window where it lies, and the only
+thing a bag holds besides the slide is the coordinates: slide -> kept coordinates -> `U8Tiles` -> `Attention`, with nothing of
+size T*S*S in between.  Reading slide files and `.npy` caches stays with the caller.
+"""
+import numpy as np
+import torch
+
+from .preprocess import TilePreprocessor
+from .roi_select import RoiSelector
+
+
+class SlideBag:
+    """slide: uint8 [H,W,3] (on the GPU for everything but the host bookkeeping).  `roi_size`, `padding`: the reference's
+    `params['roi_size']` / `params['padding']`; `pad`: its Pad(100); `max_tiles`: the hard limit of `get_train_data`
+    (RoiBuilder.py:230).  `selector`: a `RoiSelector` of the same roi_size (default: the reference's constants).  `coords`:
+    a loaded `coor_cache`, int [T,2] of (row, col) — `build()` then has nothing to do.
+
+    Unlike the reference, a bag with no kept window returns an EMPTY stack [0,3,R,R] from the three `get_*` methods, not the
+    `torch.zeros(20,3,128,128)` placeholder of RoiBuilder.py:236,257 (which has neither the bag's resolution nor any tile of
+    it); the caller decides what to do with a slide without tissue."""
+
+    def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None):
+        if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
+            raise ValueError(f"expected a uint8 [H,W,3] slide, got {getattr(slide, 'dtype', type(slide))} "
+                             f"{tuple(getattr(slide, 'shape', ()))}")
+        self.roi_size, self.padding, self.pad, self.max_tiles = int(roi_size), int(padding), int(pad), int(max_tiles)
+        if self.roi_size < 1 or self.padding < 0 or self.pad < 0 or self.max_tiles < 1:
+            raise ValueError("roi_size and max_tiles must be positive, padding and pad non-negative")
+        self.selector = RoiSelector(self.roi_size, self.padding) if selector is None else selector
+        if self.selector.roi_size != self.roi_size:
+            raise ValueError(f"the selector cuts {self.selector.roi_size}-pixel windows, the bag {self.roi_size}-pixel ones")
+        self.slide = slide
+        self.coords = None                                   # coor_cache: int64 [T,2] numpy (row, col) once built
+        if coords is not None:
+            c = np.asarray(coords.cpu() if isinstance(coords, torch.Tensor) else coords)
+            if c.size and c.dtype.kind not in "iu":
+                raise ValueError("coords must be integers")
+            c = c.astype(np.int64).reshape(-1, 2)
+            s, (h, w) = self.roi_size, slide.shape[:2]
+            if c.size and (c.min() < 0 or c[:, 0].max() + s > h or c[:, 1].max() + s > w):
+                raise ValueError(f"a {s} x {s} window does not lie inside the {h} x {w} slide")
+            self.coords = c
+        self.resolution = self.prep = None
+        if resolution is not None:
+            self.update_resolution(resolution)
+
+    @property
+    def ntiles(self):
+        """The number of kept windows; -1 before `build()`, as the reference's `params['ntiles']`."""
+        return -1 if self.coords is None else len(self.coords)
+
+    def build(self):
+        """Runs the tissue selection over the slide's raster (RoiBuilder.py:153-169) unless `coords=` supplied its result."""
+        if self.coords is None:
+            self.coords = self.selector.kept(self.slide)
+        return True
+
+    def update_resolution(self, resolution):
+        """`update_resolution_and_buffer` (RoiBuilder.py:182-212): the size of the tiles the `get_*` methods return."""
+        self.resolution = int(resolution)
+        self.prep = TilePreprocessor(self.roi_size, self.resolution, pad=self.pad, device=self.slide.device)
+
+    def _ready(self):
+        if self.coords is None or self.prep is None:
+            raise RuntimeError("call build() and update_resolution() first "
+                               f"(ntiles = {self.ntiles}, resolution = {self.resolution})")
+
+    def choose(self, generator=None, choice=None):
+        """The windows a training draw uses, as indices into `coords` (RoiBuilder.py:230-231): all of them, in order, when at
+        most `max_tiles` were kept (returns None; `choice` is then not used); otherwise `max_tiles` distinct ones, drawn
+        without replacement from `generator` or — `choice` — injected by the caller, in the order given."""
+        n = self.ntiles
+        if n < 0:
+            raise RuntimeError("call build() first")
+        if n <= self.max_tiles:
+            return None
+        if choice is None:
+            return torch.randperm(n, generator=generator)[:self.max_tiles].numpy()
+        idx = np.asarray(choice.cpu() if isinstance(choice, torch.Tensor) else choice).astype(np.int64).reshape(-1)
+        if len(idx) != self.max_tiles or len(np.unique(idx)) != len(idx) or idx.min() < 0 or idx.max() >= n:
+            raise ValueError(f"choice must hold {self.max_tiles} distinct indices below {n}")
+        return idx
+
+    def get_train_data(self, generator=None, choice=None, params=None, out="u8"):
+        """`get_train_data` (RoiBuilder.py:215-238): the cap of `choose`, then the train chain on the chosen windows with
+        `draw_params(generator)` or the injected `params` [n,4]."""
+        self._ready()
+        idx = self.choose(generator, choice)
+        c = self.coords if idx is None else self.coords[idx]
+        if params is None:
+            params = self.prep.draw_params(len(c), generator)
+        return self.prep.from_slide(self.slide, c, params, out)
+
+    def get_validation_data(self, out="u8"):
+        """`get_validation_data` (RoiBuilder.py:240-259): the flat chain on every kept window."""
+        self._ready()
+        return self.prep.from_slide(self.slide, self.coords, None, out)
+
+    def get_inference_data(self, out="u8"):
+        """`get_inference_data` (RoiBuilder.py:261-284): (tiles of the flat chain, their coordinates).  The reference's third
+        item, the ROIs themselves (for `imshow` in its `visualize`), is `rois(indices)` for the ones that are drawn."""
+        self._ready()
+        return self.prep.from_slide(self.slide, self.coords, None, out), self.coords.copy()
+
+    def rois(self, indices):
+        """The chosen kept windows as pixels, uint8 [n,S,S,3] on the slide's device — materialised on request only."""
+        if self.coords is None:
+            raise RuntimeError("call build() first")
+        idx = np.asarray(indices.cpu() if isinstance(indices, torch.Tensor) else indices).astype(np.int64).reshape(-1)
+        s = self.roi_size
+        out = torch.empty((len(idx), s, s, 3), dtype=torch.uint8, device=self.slide.device)
+        for j, i in enumerate(idx):
+            r, q = (int(v) for v in self.coords[i])
+            out[j].copy_(self.slide[r:r + s, q:q + s])
+        return out

@@ -192,6 +192,26 @@ int mil_tile_preprocess_s2d(const uint8_t* rois, const int32_t* params, const in
  * mil_tile_preprocess's values, so it serves all three compute modes.  Any R. */
 int mil_tile_preprocess_u8(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                            const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream);
+/* The three entries above for ROIs that are WINDOWS of a larger image left in place (array_read_region followed by the
+ * chains, RoiBuilder.py:117-124,193-210) instead of tiles of a contiguous stack: row y of window t starts at byte
+ * base + win_off_dev[t] + y * row_pitch, at any byte alignment — mil_roi_stats' source convention (a slide [H,W,3]: row_pitch =
+ * 3W, win_off = (row*W + col)*3; a stack: 3S and t*3*S*S).  win_off_dev is a DEVICE array [T]; base_bytes is the size of the
+ * source: loads go through buffer descriptors that end with it, so no over-fetch leaves it.  Left and right of a window the
+ * source's own pixels are masked: Pad() pads with zeros.  params, tables, outputs, T <= 65535 per call and status codes as
+ * above, results bit for bit those of the stack entries for the same pixels; additionally null base / win_off_dev,
+ * base_bytes < 0 or row_pitch < 3S: MIL_ERR_ARG, and a row_pitch so large that the source rows of eight output rows leave
+ * 31-bit offsets: MIL_ERR_UNSUPPORTED — decided on the host before any GPU call. */
+int mil_tile_preprocess_win(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                            const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                            const int32_t* kk_dev, float* out, int T, int S, int pad, int R, void* stream);
+/* RoiBuilder.py:117-124,193-210 with mil_tile_preprocess_s2d's output (xs [T,R/2,R/2,16] bf16, R even). */
+int mil_tile_preprocess_win_s2d(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                                const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                                const int32_t* kk_dev, void* xs, int T, int S, int pad, int R, void* stream);
+/* RoiBuilder.py:117-124,193-210 with mil_tile_preprocess_u8's output (out [T,3,R,R] uint8 planar, any R). */
+int mil_tile_preprocess_win_u8(const uint8_t* base, int64_t base_bytes, const int64_t* win_off_dev, int64_t row_pitch,
+                               const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
+                               const int32_t* kk_dev, uint8_t* out, int T, int S, int pad, int R, void* stream);
 
 /* Tissue selection (RoiBuilder.py:156-169, the loop body of RoiBuilder.build()): per roi_size window of a whole-slide image the
  * integers from which the reference's two tests are decided — ImageStat.Stat(roi).stddev[0] > 5 (from sum R, sum R^2 and the
