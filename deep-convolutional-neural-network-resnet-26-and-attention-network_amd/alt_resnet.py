@@ -5,8 +5,9 @@ kernels: same module tree and state-dict keys (`conv1.weight`, `layerL.B.conv{1,
 `layerL.0.downsample.0.weight`, `fc.weight`, `fc.bias`), forward and hand-written backward.
 
 64-channel layers run on the resident-filter kernels of the 20–80-channel path; 128/256/512-channel layers run on
-the channel-blocked kernels of `csrc/conv_wide.hip`.  `pretrained=True` of the reference is a URL fetch and is not
-offered; its `zero_init_residual=True` branch raises in the reference (`alt_resnet.py:104` touches a `bn2` that no
+the channel-blocked kernels of `csrc/conv_wide.hip`.  `compute_dtype` is `torch.bfloat16` (the default), `torch.float32`
+(exact-f32 MFMA) or `mil_amd.BF16X3` (fp32 tensors, every convolution as three bf16 MFMAs on hi/lo-split operands).
+`pretrained=True` of the reference is a URL fetch and is not offered; its `zero_init_residual=True` branch raises in the reference (`alt_resnet.py:104` touches a `bn2` that no
 longer exists) and is rejected here as well.
 """
 import torch
@@ -16,6 +17,7 @@ from . import _lib as L
 from . import ops
 
 WIDTHS = (64, 128, 256, 512)          # alt_resnet.py:86-89
+MODES = (torch.bfloat16, torch.float32, L.BF16X3)
 GATHER_GEMM = [True]                  # A/B switch: False keeps every wide conv on the channel-blocked kernels of conv_wide.hip
 
 
@@ -42,7 +44,8 @@ class BasicBlock(nn.Module):
 class _Conv:
     """One convolution of the network: packed operands + the three kernel calls, narrow or wide path.  The packed
     (MFMA fragment order) copies are built once and re-used until the weight changes: `_packed_conv` keys them on
-    the parameter's storage, its version counter and the optimizer epoch, as `encoder.ResNet.refresh_packed` does."""
+    the parameter's storage, its version counter and the optimizer epoch, as `encoder.ResNet.refresh_packed` does.
+    `dtype` is the compute MODE (torch.bfloat16, torch.float32 or L.BF16X3: the packing differs between the last two)."""
 
     def __init__(self, conv, dtype):
         w = conv.weight
@@ -161,8 +164,10 @@ def _packed_stem(net, dtype):
     return hit[1]
 
 
-def _forward(net, x, dtype):
-    wp, bp = _packed_stem(net, dtype)
+def _forward(net, x, mode):
+    """`mode`: the compute mode the filters are packed for; the caller holds the matching `L.f32_mma`."""
+    dtype = L.storage_dtype(mode)
+    wp, bp = _packed_stem(net, mode)
     fused = ops.stem_fwd_fused(x, wp, bp, 64, slope=0.0, dtype=dtype)
     if fused is not None:
         xs, pool, widx = fused
@@ -175,8 +180,8 @@ def _forward(net, x, dtype):
     saved = {"xs": xs, "stem_hw": stem_hw, "widx": widx, "blocks": []}
     t = pool
     for blk in net.blocks():
-        c1, c2 = _packed_conv(net, blk.conv1, dtype), _packed_conv(net, blk.conv2, dtype)
-        ds = _packed_conv(net, blk.downsample[0], dtype) if blk.downsample is not None else None
+        c1, c2 = _packed_conv(net, blk.conv1, mode), _packed_conv(net, blk.conv2, mode)
+        ds = _packed_conv(net, blk.downsample[0], mode) if blk.downsample is not None else None
         o1 = c1.forward(t)
         short = ds.forward(t, relu=False) if ds is not None else t
         out = c2.forward(o1, res=short)
@@ -187,7 +192,7 @@ def _forward(net, x, dtype):
     return feats, saved
 
 
-def _backward(net, saved, dfeats, dtype):
+def _backward(net, saved, dfeats):
     blocks = saved["blocks"]
     last_out = blocks[-1][2]
     dz, dwfc, dbfc = ops.avgpool_fc_bwd(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], last_out, 512,
@@ -220,14 +225,18 @@ def _backward(net, saved, dfeats, dtype):
 class _AltFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, *params):
-        dtype = net.compute_dtype
-        feats, saved = _forward(net, x.detach(), dtype)
-        ctx.net, ctx.saved, ctx.dtype = net, saved, dtype
+        mode = net.compute_dtype            # torch.bfloat16, torch.float32 (exact-f32 MFMA) or L.BF16X3 (fp32 tensors, split products)
+        if mode not in MODES:
+            raise ValueError(f"compute dtype must be torch.float32, torch.bfloat16 or mil_amd.BF16X3, got {mode}")
+        with L.f32_mma(L.mma_code(mode)):
+            feats, saved = _forward(net, x.detach(), mode)
+        ctx.net, ctx.saved, ctx.mode = net, saved, mode
         return feats
 
     @staticmethod
     def backward(ctx, dfeats):
-        grads = _backward(ctx.net, ctx.saved, dfeats, ctx.dtype)
+        with L.f32_mma(L.mma_code(ctx.mode)):      # autograd's thread: the forward's setting does not reach it
+            grads = _backward(ctx.net, ctx.saved, dfeats)
         ctx.saved = None
         return (None, None, *grads)
 

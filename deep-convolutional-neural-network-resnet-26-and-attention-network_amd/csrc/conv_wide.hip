@@ -8,8 +8,9 @@
 //   k loop  = 32-wide INPUT-channel chunks; per chunk the halo tile slice [pixels][32] and the filter slice
 //             [taps][4][64 lanes][8] are staged in LDS and all taps run from them (one MFMA k-step = one tap
 //             of the chunk), accumulators persist across chunks.
-// Same operand conventions as conv_igemm.hip (NHWC, fragment-packed weights, fp32 accumulate; T = BF16 or the
-// exact-fp32 MFMA path), same fused epilogue (bias?/residual/ReLU-or-LeakyReLU/mask), dgrad = the same kernel
+// Same operand conventions as conv_igemm.hip (NHWC, fragment-packed weights, fp32 accumulate; T = BF16, the
+// exact-fp32 MFMA path, or F32S: fp32 tensors split on their way into LDS into [hi | lo] bf16 planes and contracted
+// as three bf16 MFMAs per k-step, MIL_DT_F32S), same fused epilogue (bias?/residual/ReLU-or-LeakyReLU/mask), dgrad = the same kernel
 // over dz with transposed+flipped packing, stride-2 dgrad through the zero-insert loader.
 // Weight gradient: wide_wgrad_kernel, one (output block, input chunk) pair per grid.y.
 #include "pf_common.cuh"
@@ -32,7 +33,9 @@ struct WideArgs {
     float slope;
 };
 
-// halo slice loader: channels [c0, c0+32) of a tensor with `ctot` channels per pixel
+// halo slice loader: channels [c0, c0+32) of a tensor with `ctot` channels per pixel.  F32S: a 16-byte piece is four fp32
+// channels and lands as 8 bytes of the record's hi plane + 8 bytes, 64 behind, of its lo plane ([hi: 32 bf16][lo: 32 bf16]
+// in the 128 bytes the fp32 record takes); pixels outside the image are zeros in both planes.
 template <typename T>
 __device__ __forceinline__ void wide_load_halo(char* lds, const typename T::elem* __restrict__ x, const ConvGeom& g,
                                                const TileOrigin& o, int tid, int ctot, int c0) {
@@ -54,7 +57,8 @@ __device__ __forceinline__ void wide_load_halo(char* lds, const typename T::elem
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (ok) v = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(x) +
                         ((((size_t)img * g.H + iy) * g.W + ix) * ctot + c0) * ESZ + j * 16);
-        *reinterpret_cast<uint4*>(lds + hp * PIXB + j * 16) = v;
+        if constexpr (T::SPLIT) mil_commit_piece<T, WIDE_CK * 2>(lds + hp * PIXB + j * 8, __builtin_bit_cast(u32x4_t, v));
+        else *reinterpret_cast<uint4*>(lds + hp * PIXB + j * 16) = v;
     }
 }
 
@@ -97,13 +101,13 @@ __global__ __launch_bounds__(256) void wide_conv_kernel(WideArgs<T> a, int lds_w
         __syncthreads();
         for (int tap = 0; tap < ntaps; ++tap) {
             const int ky = tap / g.ks, kx = tap - ky * g.ks;
-            const int toff = (ky * g.hw + kx) * PIXB + gq * FRAGB;
+            const int toff = (ky * g.hw + kx) * PIXB + gq * T::CGB;
             Frag8<T> bf[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) bf[j] = lds_frag<T>(ldsW + ((tap * WIDE_NT + wn * 2 + j) * 64 + lane) * FRAGB);
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const Frag8<T> af = lds_frag<T>(ldsA + pixbase[m] + toff);
+                const Frag8<T> af = lds_pix_frag<T, WIDE_CK * 2>(ldsA + pixbase[m] + toff);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[m][j] = mma8(af, bf[j], acc[m][j]);
             }
@@ -317,6 +321,171 @@ __global__ __launch_bounds__(256, 2) void wide_conv_pf_kernel(WideArgs<BF16> a, 
     }
 }
 
+// The fused epilogue of the wide conv kernels on the accumulators a workgroup has parked in LDS: epi = [128 px][64 ch] fp32.
+template <typename T>
+__device__ __forceinline__ void wide_epilogue(const WideArgs<T>& a, const TileOrigin& o, const float* epi, int cb, int tid) {
+    const ConvGeom& g = a.g;
+    const int tw_mask = (1 << g.tw_log2) - 1, th_mask = (1 << g.th_log2) - 1;
+    for (int idx = tid; idx < 128 * (WIDE_NB / 8); idx += 256) {
+        const int tp = idx >> 3, c8 = idx & 7;
+        const int ox = o.ox0 + (tp & tw_mask);
+        const int oy = o.oy0 + ((tp >> g.tw_log2) & th_mask);
+        const int img = o.img0 + (tp >> (g.tw_log2 + g.th_log2));
+        if (img >= g.n_img || oy >= g.Ho || ox >= g.Wo) continue;
+        float v[8];
+        {
+            const f32x4_t lo = *reinterpret_cast<const f32x4_t*>(epi + tp * WIDE_NB + c8 * 8);
+            const f32x4_t hi = *reinterpret_cast<const f32x4_t*>(epi + tp * WIDE_NB + c8 * 8 + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
+        }
+        const int c = cb * WIDE_NB + c8 * 8;
+        if (a.bias) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += a.bias[c + j];
+        }
+        const size_t off = (((size_t)img * g.Ho + oy) * g.Wo + ox) * a.cout + c;
+        if (a.res) {
+            float rv[8];
+            load8<T>(a.res + off, rv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += rv[j];
+        }
+        if (a.apply_relu) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = lrelu(v[j], a.slope);
+        }
+        if (a.act) {
+            float av[8];
+            load8<T>(a.act + off, av);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= lrelu_grad(av[j], a.slope);
+        }
+        store8<T>(a.y + off, v);
+    }
+}
+
+// Pipelined split-precision (MIL_DT_F32S) form of wide_conv_kernel<F32S> for the launches wide_conv_pf_kernel takes in bf16
+// (stride 1 or zero insertion, halo <= 256 pixels): the plain form spends four fifths of a chunk waiting — its halo loop is
+// six serial load -> wait -> LDS-store round trips and the 74 KB filter slice three more, all in front of 72 x 3 MFMAs per wave.
+// Here the NEXT chunk's halo pieces (fp32, 8 x 16 B per thread) and filter pieces (18 x 16 B) are requested into registers
+// before the current chunk's MFMA loop and split / written to LDS after it; piece addresses and predicates are computed once
+// per workgroup.  100 KB of LDS leave one workgroup per CU, so the registers are there (no occupancy bound in the launch bounds).
+// Accumulation order per output = (chunk, tap, lo*hi, hi*lo, hi*hi), that of the plain form: results are bit-identical.
+template <int KS>
+__global__ __launch_bounds__(256) void wide_conv_x3_pf_kernel(WideArgs<F32S> a, int lds_w_off, unsigned x_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    MIL_POISON(smem);
+    using T = F32S;
+    constexpr int PIXB = mil_pix_pitch(WIDE_CK, 4);
+    constexpr int LO = WIDE_CK * 2;                          // the lo plane of a pixel record starts 64 bytes behind its hi plane
+    constexpr int NTAP = KS * KS;
+    constexpr int NPH = 8;                                   // halo pieces per thread: <= 256 pixels x 8 pieces of four fp32 channels
+    constexpr int NPW = 2 * NTAP;                            // filter pieces per thread: NTAP * 4 * 64 fragments of 32 B / 256 / 16 B
+    // In LDS the filter slice is two planes, [fragment][hi: 16 B] and, WPL behind, [fragment][lo: 16 B]: read at the packed
+    // 32-byte pitch, lanes l and l + 8 of a 16-byte fragment read share their banks.  Piece tid + 256 i is half (tid & 1) of
+    // fragment (tid >> 1) + 128 i.
+    constexpr int WPL = NTAP * WIDE_NT * 64 * 16;
+    const ConvGeom& g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave & 1, wn = wave >> 1;              // wave grid: 2 (pixels) x 2 (channels)
+    const int r = lane & 15, gq = lane >> 4;
+    const int cb = blockIdx.y;
+    const TileOrigin o = mil_tile_origin(g, blockIdx.x);
+    char* ldsA = smem;
+    char* ldsW = smem + lds_w_off;
+    const int nchunks = a.cin / WIDE_CK;
+    const __amdgpu_buffer_rsrc_t rs_x = mil_rsrc(a.x, x_bytes);
+
+    unsigned h_off[NPH];
+    int h_lds[NPH];
+    {
+        const int npix = (g.hh * g.hw) << g.ti_log2;
+        const int iy0 = o.oy0 - g.pad, ix0 = o.ox0 - g.pad;
+#pragma unroll
+        for (int i = 0; i < NPH; ++i) {
+            const int idx = tid + 256 * i;
+            const int hp = idx >> 3, j = idx & 7;
+            const int ti = hp / (g.hh * g.hw), rem = hp - ti * (g.hh * g.hw);
+            const int hy = rem / g.hw, hx = rem - hy * g.hw;
+            const int img = o.img0 + ti;
+            int iy = iy0 + hy, ix = ix0 + hx;
+            const bool used = hp < npix;
+            bool ok = used && img < g.n_img && iy >= 0 && ix >= 0;
+            if (g.zins) { ok = ok && !((iy | ix) & 1); iy >>= 1; ix >>= 1; }      // transposed stride-2 conv: zeros between the pixels of x
+            ok = ok && iy < g.H && ix < g.W;
+            h_off[i] = ok ? (unsigned)((((img * g.H + iy) * g.W + ix) * a.cin) * 4 + j * 16) : MIL_OOB;
+            h_lds[i] = used ? hp * PIXB + j * 8 : lds_w_off - (LO + 16);      // unused slots: a spare [8 B .. 64 .. 8 B] behind the halo tile
+        }
+    }
+    int pixbase[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) pixbase[m] = mil_pix_base<PIXB>(g, (wm * 4 + m) * 16 + r, 1) + gq * T::CGB;
+    int toff[NTAP];
+#pragma unroll
+    for (int tap = 0; tap < NTAP; ++tap) toff[tap] = ((tap / KS) * g.hw + (tap % KS)) * PIXB;
+    f32x4_t acc[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[m][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const size_t chunk_bytes = (size_t)NTAP * WIDE_NT * 64 * 32;
+    const char* wbase = reinterpret_cast<const char*>(a.w) + (size_t)cb * nchunks * chunk_bytes + (size_t)tid * 16;
+    u32x4_t rh[NPH], rw[NPW];
+    auto fetch = [&](int ch) {
+#pragma unroll
+        for (int i = 0; i < NPH; ++i)
+            rh[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, h_off[i] == MIL_OOB ? MIL_OOB : h_off[i] + (unsigned)(ch * WIDE_CK * 4), 0, 0);
+        const char* src = wbase + (size_t)ch * chunk_bytes;
+#pragma unroll
+        for (int i = 0; i < NPW; ++i) rw[i] = *reinterpret_cast<const u32x4_t*>(src + i * 256 * 16);
+    };
+    fetch(0);
+    for (int ch = 0; ch < nchunks; ++ch) {
+        __syncthreads();                       // the previous chunk's fragment reads are done
+#pragma unroll
+        for (int i = 0; i < NPH; ++i) mil_commit_piece<T, LO>(ldsA + h_lds[i], rh[i]);      // out-of-image pieces: zeros in both planes
+#pragma unroll
+        for (int i = 0; i < NPW; ++i) *reinterpret_cast<u32x4_t*>(ldsW + (tid & 1) * WPL + ((tid >> 1) + 128 * i) * 16) = rw[i];
+        __syncthreads();
+        if (ch + 1 < nchunks) fetch(ch + 1);   // lands while the loop below runs
+        {
+            constexpr int TOT = NTAP * 4, LA = TOT > 2 ? 2 : 1, R = LA + 1;
+            Frag8<T> ring[R], bq[2][2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bq[0][j] = lds_pix_frag<T, WPL>(ldsW + ((wn * 2 + j) * 64 + lane) * 16);
+#pragma unroll
+            for (int q = 0; q < LA; ++q) ring[q % R] = lds_pix_frag<T, LO>(ldsA + pixbase[q % 4] + toff[q / 4]);
+#pragma unroll
+            for (int q = 0; q < TOT; ++q) {
+                const int tap = q / 4, m = q % 4;
+                if (q + LA < TOT) ring[(q + LA) % R] = lds_pix_frag<T, LO>(ldsA + pixbase[(q + LA) % 4] + toff[(q + LA) / 4]);
+                if (m == 0 && tap + 1 < NTAP) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) bq[(tap + 1) & 1][j] = lds_pix_frag<T, WPL>(ldsW + (((tap + 1) * WIDE_NT + wn * 2 + j) * 64 + lane) * 16);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[m][j] = mma8(ring[q % R], bq[tap & 1][j], acc[m][j]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    __syncthreads();
+    float* epi = reinterpret_cast<float*>(smem);             // [128 px][64 ch] fp32
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                epi[((wm * 4 + m) * 16 + gq * 4 + i) * WIDE_NB + (wn * 2 + j) * 16 + r] = acc[m][j][i];
+    __syncthreads();
+    wide_epilogue<T>(a, o, epi, cb, tid);
+}
+
 // fp32 master [Cout][Cin][k][k] -> [co_block][ci_chunk][tap][4][64][8] (mode 0 forward, 1 dgrad; see conv_igemm)
 template <typename T>
 __global__ void wide_pack_kernel(const float* __restrict__ w, typename T::elem* __restrict__ out, int cout, int cin, int ks,
@@ -338,7 +507,14 @@ __global__ void wide_pack_kernel(const float* __restrict__ w, typename T::elem* 
         if (!mode) val = w[((size_t)nout * cin + kin) * kk + tap];
         else val = w[((size_t)kin * cin + nout) * kk + (kk - 1 - tap)];
     }
-    out[idx] = (typename T::elem)val;
+    if constexpr (T::SPLIT) {                   // fragment = [hi: 8 bf16][lo: 8 bf16] per lane (32 bytes, as 8 floats)
+        const __bf16 h = (__bf16)val;
+        __bf16* o = reinterpret_cast<__bf16*>(out) + (idx >> 3) * 16 + (idx & 7);
+        o[0] = h;
+        o[8] = (__bf16)(val - (float)h);
+    } else {
+        out[idx] = (typename T::elem)val;
+    }
 }
 
 extern "C" int mil_wide_packed_elems(size_t* elems, int cout, int cin, int ks, int mode) {
@@ -355,9 +531,18 @@ extern "C" int mil_wide_pack_weights(const float* w, void* wpack, int cout, int 
     const unsigned grid = (unsigned)((total + 255) / 256);
     if (dtype == MIL_DT_BF16) hipLaunchKernelGGL(wide_pack_kernel<BF16>, dim3(grid), dim3(256), 0, st, w, (__bf16*)wpack, cout, cin, ks, mode, total);
     else if (dtype == MIL_DT_F32) hipLaunchKernelGGL(wide_pack_kernel<F32>, dim3(grid), dim3(256), 0, st, w, (float*)wpack, cout, cin, ks, mode, total);
+    else if (dtype == MIL_DT_F32S) hipLaunchKernelGGL(wide_pack_kernel<F32S>, dim3(grid), dim3(256), 0, st, w, (float*)wpack, cout, cin, ks, mode, total);
     else return MIL_ERR_ARG;
     MIL_CHECK_LAUNCH();
     return MIL_OK;
+}
+
+// The pipelined split-precision forms have no tile threshold of their own: every launch whose geometry fits takes them.  The
+// MIL_PF_MIN_TILES test knob, when set, applies to them as it does to the persistent kernels of conv_igemm.hip (launches with
+// fewer tiles run the plain form), so that a test can run one problem through both forms.
+static int wide_x3_pf_min_tiles() {
+    const char* e = mil_test_knob("MIL_PF_MIN_TILES");
+    return e ? atoi(e) : 0;
 }
 
 template <typename T>
@@ -395,6 +580,22 @@ static int launch_wide(WideArgs<T> a, hipStream_t st) {
             return MIL_OK;
         }
     }
+    if constexpr (T::SPLIT) {
+        // the same launches in split precision: wide_conv_x3_pf_kernel (8 fp32 halo pieces per thread)
+        const int halo_px = (a.g.hh * a.g.hw) << a.g.ti_log2;
+        const size_t xb = (size_t)a.g.n_img * a.g.H * a.g.W * a.cin * 4;
+        if (a.g.stride == 1 && halo_px <= 256 && xb < ((size_t)1 << 31) && tiles >= wide_x3_pf_min_tiles()) {
+            const int a_pf = a_bytes + WIDE_CK * 2 + 16;      // + dump slot (hi and lo piece) for the unused halo piece slots
+            int lds_pf = a_pf + w_bytes;
+            if (lds_pf < 128 * WIDE_NB * 4) lds_pf = 128 * WIDE_NB * 4;
+            auto kpf = a.g.ks == 3 ? wide_conv_x3_pf_kernel<3> : wide_conv_x3_pf_kernel<1>;
+            if (lds_pf > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kpf), hipFuncAttributeMaxDynamicSharedMemorySize, lds_pf) != hipSuccess)
+                return MIL_ERR_LAUNCH;
+            hipLaunchKernelGGL(kpf, dim3(tiles, a.cout / WIDE_NB), dim3(256), lds_pf, st, a, a_pf, (unsigned)xb);
+            MIL_CHECK_LAUNCH();
+            return MIL_OK;
+        }
+    }
     auto kern = wide_conv_kernel<T>;
     if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
@@ -423,6 +624,11 @@ extern "C" int mil_wide_conv(const void* x, const void* wpack, const float* bias
         a.x = (const float*)x; a.w = (const float*)wpack; a.bias = bias; a.res = (const float*)res; a.act = (const float*)act;
         a.y = (float*)y; a.g = g; a.cin = cin; a.cout = cout; a.apply_relu = apply_relu; a.slope = slope;
         return launch_wide<F32>(a, st);
+    } else if (dtype == MIL_DT_F32S) {
+        WideArgs<F32S> a{};
+        a.x = (const float*)x; a.w = (const float*)wpack; a.bias = bias; a.res = (const float*)res; a.act = (const float*)act;
+        a.y = (float*)y; a.g = g; a.cin = cin; a.cout = cout; a.apply_relu = apply_relu; a.slope = slope;
+        return launch_wide<F32S>(a, st);
     }
     return MIL_ERR_ARG;
 }
@@ -455,7 +661,8 @@ __device__ __forceinline__ void wide_load_otile(char* lds, const typename T::ele
         if (img < g.n_img && oy < g.Ho && ox < g.Wo)
             v = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(z) +
                     ((((size_t)img * g.Ho + oy) * g.Wo + ox) * ctot + c0) * ESZ + j * 16);
-        *reinterpret_cast<uint4*>(lds + tp * PIXZ + j * 16) = v;
+        if constexpr (T::SPLIT) mil_commit_piece<T, WIDE_NB * 2>(lds + tp * PIXZ + j * 8, __builtin_bit_cast(u32x4_t, v));     // [hi: 64 bf16][lo: 64 bf16]
+        else *reinterpret_cast<uint4*>(lds + tp * PIXZ + j * 16) = v;
     }
 }
 
@@ -482,11 +689,11 @@ __global__ __launch_bounds__(256) void wide_wgrad_kernel(WideWgradArgs<T> a) {
         const int mt = wave + 4 * i;
         mvalid[i] = mt < MT;
         int rg, sub;
-        if constexpr (T::DT == MIL_DT_BF16) { const int p = lane & 3; rg = 2 * mt + (p >> 1); sub = (p & 1) * 8; }
+        if constexpr (T::TR16) { const int p = lane & 3; rg = 2 * mt + (p >> 1); sub = (p & 1) * 8; }
         else { const int row = lane & 15; rg = 2 * mt + (row >> 3); sub = (row & 7) * 4; }
         if (rg >= RG) rg = 0;
         const int tap = rg / CG, cg = rg - tap * CG;
-        toff[i] = ((tap / KS) * g.hw + (tap % KS)) * PIXB + cg * (8 * ESZ) + sub;
+        toff[i] = ((tap / KS) * g.hw + (tap % KS)) * PIXB + cg * T::CGB + sub;
     }
     f32x4_t acc[MW][WIDE_NT];
 #pragma unroll
@@ -500,7 +707,35 @@ __global__ __launch_bounds__(256) void wide_wgrad_kernel(WideWgradArgs<T> a) {
         wide_load_halo<T>(ldsX, a.x, g, o, tid, a.cin, ch * WIDE_CK);
         wide_load_otile<T>(ldsZ, a.dz, g, o, tid, a.cout, cb * WIDE_NB);
         __syncthreads();
-        if constexpr (T::DT == MIL_DT_BF16) {
+        if constexpr (T::SPLIT) {
+            // both operands transposed out of each plane as in the bf16 form below; dW += x_lo*dz_hi + x_hi*dz_lo + x_hi*dz_hi
+            const int q4 = (lane & 15) >> 2, p = lane & 3, gq = lane >> 4;
+            for (int k32 = 0; k32 < 128; k32 += 32) {
+                const int tp0 = k32 + 8 * gq + q4, tp1 = tp0 + 4;
+                const int pb0 = mil_pix_base<PIXB>(g, tp0, g.stride), pb1 = mil_pix_base<PIXB>(g, tp1, g.stride);
+                const char* z0 = ldsZ + tp0 * PIXZ + p * 8;
+                const char* z1 = ldsZ + tp1 * PIXZ + p * 8;
+                bf16x8_t bh[WIDE_NT], bl[WIDE_NT];
+#pragma unroll
+                for (int nt = 0; nt < WIDE_NT; ++nt) {
+                    bh[nt] = mil_tr_pair(z0 + nt * 32, z1 + nt * 32);
+                    bl[nt] = mil_tr_pair(z0 + WIDE_NB * 2 + nt * 32, z1 + WIDE_NB * 2 + nt * 32);
+                }
+#pragma unroll
+                for (int i = 0; i < MW; ++i) {
+                    if (mvalid[i]) {
+                        const bf16x8_t ah = mil_tr_pair(ldsX + pb0 + toff[i], ldsX + pb1 + toff[i]);
+                        const bf16x8_t al = mil_tr_pair(ldsX + pb0 + toff[i] + WIDE_CK * 2, ldsX + pb1 + toff[i] + WIDE_CK * 2);
+#pragma unroll
+                        for (int nt = 0; nt < WIDE_NT; ++nt) {
+                            acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[nt], acc[i][nt], 0, 0, 0);
+                            acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[nt], acc[i][nt], 0, 0, 0);
+                            acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[nt], acc[i][nt], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        } else if constexpr (T::DT == MIL_DT_BF16) {
             const int q4 = (lane & 15) >> 2, p = lane & 3, gq = lane >> 4;
             for (int k32 = 0; k32 < 128; k32 += 32) {
                 const int tp0 = k32 + 8 * gq + q4, tp1 = tp0 + 4;
@@ -789,6 +1024,9 @@ static int wide_wgrad_entry(const void* x, const void* dz, float* dw, void* ws, 
                                              : run_wide_wgrad<BF16, 1>(x, dz, dw, ws, ws_bytes, g, cin, cout, accumulate, query, need, st);
     if (dtype == MIL_DT_F32) return ks == 3 ? run_wide_wgrad<F32, 3>(x, dz, dw, ws, ws_bytes, g, cin, cout, accumulate, query, need, st)
                                             : run_wide_wgrad<F32, 1>(x, dz, dw, ws, ws_bytes, g, cin, cout, accumulate, query, need, st);
+    // split precision: the slabs, the grid and the workspace of the exact-fp32 form
+    if (dtype == MIL_DT_F32S) return ks == 3 ? run_wide_wgrad<F32S, 3>(x, dz, dw, ws, ws_bytes, g, cin, cout, accumulate, query, need, st)
+                                             : run_wide_wgrad<F32S, 1>(x, dz, dw, ws, ws_bytes, g, cin, cout, accumulate, query, need, st);
     return MIL_ERR_ARG;
 }
 

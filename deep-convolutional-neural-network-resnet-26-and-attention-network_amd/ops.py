@@ -682,12 +682,17 @@ def avgpool_fc_bwd(dfeats, wfc, pooled, act, c, slope=LEAK, out=None, want_bias=
 
 # ---- wide (multiples of 64 channels) layers: the alt_resnet configuration -----------------------------------
 def wide_pack_weights(w, mode, dtype):
+    """fp32 [Cout,Cin,k,k] -> the channel-blocked fragment order of mil_wide_conv; dtype torch.bfloat16, torch.float32 (exact, or
+    split under `f32_mma`) or L.BF16X3."""
+    if dtype == L.BF16X3:                 # the split path's filters: fp32-sized fragments [hi | lo], packed under MIL_DT_F32S
+        with L.f32_mma(L.MIL_DT_F32S):
+            return wide_pack_weights(w, mode, torch.float32)
     w = w.detach().contiguous()
     cout, cin, ks, _ = w.shape
     elems = ctypes.c_size_t(0)
     L.check(L.lib().mil_wide_packed_elems(ctypes.byref(elems), cout, cin, ks, mode), "mil_wide_packed_elems")
     packed = torch.empty(elems.value, dtype=dtype, device=w.device)
-    L.check(L.lib().mil_wide_pack_weights(w.data_ptr(), packed.data_ptr(), cout, cin, ks, mode, L.dt_code(dtype),
+    L.check(L.lib().mil_wide_pack_weights(w.data_ptr(), packed.data_ptr(), cout, cin, ks, mode, L.dt_code(dtype, mma=True),
                                           L.stream_ptr()), "mil_wide_pack_weights")
     return packed
 
@@ -704,7 +709,7 @@ def wide_conv(x, wpack, cout, *, ks, stride, pad, out_hw=None, res=None, act=Non
     _need(act, y.shape, x.dtype, "act")
     L.check(L.lib().mil_wide_conv(x.data_ptr(), wpack.data_ptr(), L.ptr(bias), L.ptr(res), L.ptr(act), y.data_ptr(), n, h, w,
                                   cin, ho, wo, cout, ks, 1 if zero_insert else stride, pad, 1 if zero_insert else 0,
-                                  1 if relu else 0, slope, L.dt_code(x.dtype), L.stream_ptr()), "mil_wide_conv")
+                                  1 if relu else 0, slope, L.dt_code(x.dtype, mma=True), L.stream_ptr()), "mil_wide_conv")
     return y
 
 
@@ -746,12 +751,12 @@ def wide_wgrad(x, dz, cin, cout, *, ks, stride, pad, workspace=None, out=None):
     _need(dz, (n, ho, wo, cout), x.dtype, "dz")
     need = ctypes.c_size_t(0)
     L.check(L.lib().mil_wide_wgrad_workspace(ctypes.byref(need), n, h, w, cin, ho, wo, cout, ks, stride, pad,
-                                             L.dt_code(x.dtype)), "mil_wide_wgrad_workspace")
+                                             L.dt_code(x.dtype, mma=True)), "mil_wide_wgrad_workspace")
     if workspace is None or workspace.numel() * workspace.element_size() < need.value:
         workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
     dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device) if out is None else out
     _need(dw, (cout, cin, ks, ks), torch.float32, "dw")
     L.check(L.lib().mil_wide_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), workspace.data_ptr(),
                                    workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo, cout, ks, stride, pad,
-                                   0 if out is None else 1, L.dt_code(x.dtype), L.stream_ptr()), "mil_wide_wgrad")
+                                   0 if out is None else 1, L.dt_code(x.dtype, mma=True), L.stream_ptr()), "mil_wide_wgrad")
     return dw, workspace

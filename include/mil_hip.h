@@ -22,7 +22,9 @@
  *                          lo*hi + hi*lo + hi*hi with fp32 accumulation.  16 significant bits per operand: meets the 1e-3
  *                          gate on logits / attention weights (2.5e-4 measured) at 3/16 of the exact path's matrix time.
  *                          Accepted by mil_pack_conv_weights / mil_pack_job_fill (fragments [hi | lo], the byte count of
- *                          MIL_DT_F32), mil_conv_igemm, mil_conv_wgrad(_workspace), and — fused forms, where the shape has
+ *                          MIL_DT_F32), mil_conv_igemm, mil_conv_wgrad(_workspace), the wide-layer entry points
+ *                          mil_wide_pack_weights, mil_wide_conv and mil_wide_wgrad(_workspace) (argument and shape rules,
+ *                          packed byte count and workspace byte count of MIL_DT_F32), and — fused forms, where the shape has
  *                          one (MIL_ERR_UNSUPPORTED otherwise: the caller falls back to the un-fused calls) —
  *                          mil_conv_bwd_fused(_workspace) (20-channel layers), mil_conv_block_fwd (20-channel identity
  *                          blocks, maps of at least 8x16), mil_conv_chain (64 / 80 channels on 16x16 / 8x8 maps, and on the
@@ -416,7 +418,14 @@ int mil_head_bwd(const float* H, const int* bag_offsets, const int* inst_bag, co
  * Channel-blocked implicit GEMM (64-wide output blocks x 32-wide input chunks staged through LDS) for channel
  * counts that do not fit the resident-filter kernels above.  Replaces conv3x3 / conv1x1 of alt_resnet.py:24-33
  * (bias-free, ReLU = slope 0) forward, data-gradient (MIL_PACK_DGRAD packing + zero_insert for stride 2) and
- * weight-gradient.  cin % 32 == 0, cout % 64 == 0; same tensor layout and epilogue semantics as mil_conv_igemm. */
+ * weight-gradient.  cin % 32 == 0, cout % 64 == 0; same tensor layout and epilogue semantics as mil_conv_igemm.
+ * dtype: MIL_DT_BF16, MIL_DT_F32 or MIL_DT_F32S.  Packed filter: [co_block][ci_chunk][tap][4][64 lanes] fragments of eight
+ * consecutive input channels; a fragment is 8 bf16 (MIL_DT_BF16), 8 floats (MIL_DT_F32) or, under MIL_DT_F32S,
+ * [hi: 8 bf16][lo: 8 bf16] with hi = bf16(v), lo = bf16(v - hi) — the 32 bytes of the MIL_DT_F32 fragment, so
+ * mil_wide_packed_elems counts elements of float for both.  Under MIL_DT_F32S every tensor is fp32 as under MIL_DT_F32 (res
+ * and act enter the epilogue as exact fp32); x / dz are split into hi and lo bf16 planes on their way into LDS and each
+ * 32-deep k-step is three bf16 MFMAs.  mil_wide_wgrad is bit-repeatable in every mode (one slab per workgroup, fixed-order
+ * reduction); its workspace under MIL_DT_F32S is that of MIL_DT_F32. */
 int mil_wide_packed_elems(size_t* elems, int cout, int cin, int ks, int mode);
 int mil_wide_pack_weights(const float* w, void* wpack, int cout, int cin, int ks, int mode, int dtype, void* stream);
 int mil_wide_conv(const void* x, const void* wpack, const float* bias, const void* res, const void* act, void* y, int n_img,

@@ -1,8 +1,10 @@
 """Per-launch timing of the wide-layer kernels (csrc/conv_wide.hip) on the shapes of an alt_resnet [3,3,3,3] step at 256 tiles
 of 256x256: 3x3 stride-1 forward / data gradient and the weight gradient at 128 ch @32x32, 256 @16x16, 512 @8x8, plus the
 stride-2 entries.  Prints TFLOP/s per shape; `--check` compares each output with torch's conv on the CPU for a small batch.
+`--dtype` selects the compute mode: bf16 tensors, fp32 tensors on the exact-f32 MFMA, or fp32 tensors with split-precision
+(bf16x3) products.
 
-    python tools/bench_wide.py [--iters 20] [--n 256] [--check] [--only conv|wgrad|s2]
+    python tools/bench_wide.py [--iters 20] [--n 256] [--check] [--only conv|wgrad|s2] [--dtype bf16|fp32|bf16x3]
 """
 import argparse
 import os
@@ -15,6 +17,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mil_amd  # noqa: E402
 from mil_amd import _lib as L, ops  # noqa: E402
 
+MODES = {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": L.BF16X3}
+# --check bounds (forward, data gradient, weight gradient; max error over the reference's max).  bf16: the operands are
+# rounded before both sides, what is left is the bf16 rounding of the stored output (2^-9) / fp32 summation order.  fp32:
+# summation order of up to 4608 fp32 products.  bf16x3: 3 * 2^-18 per product (two roundings of lo, the dropped lo*lo).
+CHECK_TOL = {"bf16": (1e-2, 1e-2, 1e-3), "fp32": (1e-5, 1e-5, 1e-5), "bf16x3": (1e-4, 1e-4, 1e-4)}
 SHAPES = [(128, 128, 32, 1), (256, 256, 16, 1), (512, 512, 8, 1), (64, 128, 64, 2), (128, 256, 32, 2), (256, 512, 16, 2)]
 
 
@@ -37,8 +44,17 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--only", default="")
     ap.add_argument("--gconv", action="store_true", help="forward / data gradient on the gather-GEMM kernel (mil_gconv)")
+    ap.add_argument("--dtype", choices=sorted(MODES), default="bf16")
     a = ap.parse_args()
-    dt = torch.bfloat16
+    if a.gconv and a.dtype != "bf16":
+        ap.error("the gather-GEMM kernel is bf16 only")
+    mode = MODES[a.dtype]
+    dt = L.storage_dtype(mode)
+    with L.f32_mma(L.mma_code(mode)):
+        run(a, mode, dt)
+
+
+def run(a, mode, dt):
     gen = torch.Generator(device="cuda").manual_seed(3)
     for cin, cout, hw, stride in SHAPES:
         n = a.n
@@ -58,13 +74,13 @@ def main():
             def dgrad(zz):
                 return ops.gconv(zz, wb, cin, ks=3, stride=stride, pad=1, transposed=True, out_hw=(hw, hw))
             if not ops.gconv_supported(cout, cin, 3, stride):          # e.g. the 128 -> 64 channel gradient: a 64-wide output block
-                wb = ops.wide_pack_weights(w, L.PACK_DGRAD, dt)
+                wb = ops.wide_pack_weights(w, L.PACK_DGRAD, mode)
 
                 def dgrad(zz):
                     return ops.wide_conv(zz, wb, cin, ks=3, stride=1, pad=1, zero_insert=stride == 2, out_hw=(hw, hw))
         else:
-            wf = ops.wide_pack_weights(w, L.PACK_FWD, dt)
-            wb = ops.wide_pack_weights(w, L.PACK_DGRAD, dt)
+            wf = ops.wide_pack_weights(w, L.PACK_FWD, mode)
+            wb = ops.wide_pack_weights(w, L.PACK_DGRAD, mode)
 
             def fwd(xx, relu=True):
                 return ops.wide_conv(xx, wf, cout, ks=3, stride=stride, pad=1, relu=relu)
@@ -101,7 +117,8 @@ def main():
                                                dzs.float().cpu().permute(0, 3, 1, 2), stride=stride, padding=1)
             e_w = float((dw.cpu() - refw).abs().max() / refw.abs().max())
             print(f"{tag} check: fwd {e_f:.2e} dgrad {e_d:.2e} wgrad {e_w:.2e}", flush=True)
-            assert e_f < 1e-2 and e_d < 1e-2 and e_w < 1e-3, "mismatch"
+            tf, td, tw = CHECK_TOL[a.dtype]
+            assert e_f < tf and e_d < td and e_w < tw, "mismatch"
 
 
 if __name__ == "__main__":
