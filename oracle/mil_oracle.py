@@ -258,18 +258,47 @@ def alt_seeded_state(layers, num_classes, seed, requires_grad=False):
     return sd
 
 
-def alt_backbone(sd, x, layers):
-    """alt_resnet.py:128-145 (`_forward_impl`) with BasicBlock of :54-66: conv-relu-conv-(+identity/projection)-relu."""
-    t = F.relu(F.conv2d(x, sd["conv1.weight"], None, stride=2, padding=3))
-    t = F.max_pool2d(t, kernel_size=3, stride=2, padding=1)
+def _relu(v, pos=None):
+    """ReLU; `pos` (bool, same shape) forces the branch per element instead of the sign of v — see `patterns` of `backbone`."""
+    return F.relu(v) if pos is None else torch.where(pos, v, torch.zeros_like(v))
+
+
+def alt_backbone(sd, x, layers, patterns=None, acts=None):
+    """alt_resnet.py:128-145 (`_forward_impl`) with BasicBlock of :54-66: conv-relu-conv-(+identity/projection)-relu.
+
+    patterns (NOT reference arithmetic; the contract of `backbone(patterns=)`): the piecewise-linear network on a GIVEN
+    activation pattern — {"stem_tap": int64 [T,64,Hp,Wp] winning tap (ky*3+kx) of every max-pool window, "stem_pos": bool, its
+    winner > 0, "layerL.B.o1" / "layerL.B": bool [T,C,H,W], the gates of the block's two ReLUs}.  With the pattern of the
+    implementation under test, an fp64 run is the exact gradient of the linear piece that implementation took.
+    acts: a dict that receives "stem" (the ReLU output the pool reads; un-patterned runs only), "pool", "layerL.B.o1" and
+    "layerL.B" — what a pattern is read from."""
+    pre = F.conv2d(x, sd["conv1.weight"], None, stride=2, padding=3)
+    if patterns is None:
+        stem = F.relu(pre)
+        if acts is not None:
+            acts["stem"] = stem
+        t = F.max_pool2d(stem, kernel_size=3, stride=2, padding=1)
+    else:                       # ReLU is monotonic: pool the pre-activation at the given winners, then the given gate
+        n, c, h, w = pre.shape
+        hp, wp = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        win = F.unfold(F.pad(pre, (1, 1, 1, 1), value=float("-inf")), kernel_size=3, stride=2).view(n, c, 9, hp, wp)
+        t = _relu(win.gather(2, patterns["stem_tap"].view(n, c, 1, hp, wp)).squeeze(2), patterns["stem_pos"])
+    if acts is not None:
+        acts["pool"] = t
     for li, depth in enumerate(layers, start=1):
         for b in range(depth):
             p = f"layer{li}.{b}."
             stride = 2 if (b == 0 and li > 1) else 1
-            o = F.relu(F.conv2d(t, sd[p + "conv1.weight"], None, stride=stride, padding=1))
+            p1 = None if patterns is None else patterns[f"layer{li}.{b}.o1"]
+            p2 = None if patterns is None else patterns[f"layer{li}.{b}"]
+            o = _relu(F.conv2d(t, sd[p + "conv1.weight"], None, stride=stride, padding=1), p1)
+            if acts is not None:
+                acts[f"layer{li}.{b}.o1"] = o
             o = F.conv2d(o, sd[p + "conv2.weight"], None, stride=1, padding=1)
             key = p + "downsample.0.weight"
             shortcut = F.conv2d(t, sd[key], None, stride=stride) if key in sd else t
-            t = F.relu(o + shortcut)
+            t = _relu(o + shortcut, p2)
+            if acts is not None:
+                acts[f"layer{li}.{b}"] = t
     t = t.mean(dim=(2, 3))
     return t @ sd["fc.weight"].t() + sd["fc.bias"]

@@ -65,6 +65,8 @@ CONV_CASES = [
     (80, 80, 3, 1, 2, 8, 8),        # bf16: the pixel-resident kernel (eight images per workgroup)
     (80, 80, 3, 1, 9, 8, 8),        # two workgroups, seven empty image slots
     (80, 80, 3, 1, 1, 18, 18),
+    (64, 64, 3, 1, 3, 16, 16),      # alt_resnet layer 1: all 64 lanes of the 60-channel kernel objects carry data (no padding)
+    (64, 64, 3, 1, 2, 19, 23),      # the same, ragged tiles
 ]
 
 
@@ -374,14 +376,15 @@ def test_wide_conv_forward_dgrad_wgrad(ops, dtype, case):
     dz = round_to(torch.randn(lin.shape, generator=g), dtype)
     lin.backward(dz)
     act = round_to(torch.randn(x.shape, generator=g), dtype)
-    want = x.grad * (act > 0)
+    addend = round_to(torch.randn(x.shape, generator=g), dtype)
     wd = ops.wide_pack_weights(wt.detach().cuda(), L.PACK_DGRAD, dtype)
     dzg = to_nhwc(dz, dtype)
-    if stride == 2:
-        dx = ops.wide_conv(dzg, wd, cin, ks=ks, stride=1, pad=pad, zero_insert=True, out_hw=(h, w), act=to_nhwc(act, dtype))
-    else:
-        dx = ops.wide_conv(dzg, wd, cin, ks=ks, stride=1, pad=pad, act=to_nhwc(act, dtype))
-    assert rel_err(from_nhwc(dx, cin), want) < TOL[dtype]
+    zi = dict(zero_insert=True, out_hw=(h, w)) if stride == 2 else {}
+    dx = ops.wide_conv(dzg, wd, cin, ks=ks, stride=1, pad=pad, act=to_nhwc(act, dtype), **zi)
+    assert rel_err(from_nhwc(dx, cin), x.grad * (act > 0)) < TOL[dtype]
+    # with an addend, as alt_resnet._backward calls it (the block input's gradient: shortcut + conv1's, gated by the input)
+    dx = ops.wide_conv(dzg, wd, cin, ks=ks, stride=1, pad=pad, res=to_nhwc(addend, dtype), act=to_nhwc(act, dtype), **zi)
+    assert rel_err(from_nhwc(dx, cin), (x.grad + addend) * (act > 0)) < TOL[dtype]
     dw, _ws = ops.wide_wgrad(xg, dzg, cin, cout, ks=ks, stride=stride, pad=pad)
     assert rel_err(dw.cpu(), wt.grad) < 3e-5
     dw2, _ws = ops.wide_wgrad(xg, dzg, cin, cout, ks=ks, stride=stride, pad=pad)

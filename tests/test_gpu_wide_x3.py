@@ -5,8 +5,30 @@ Kernel bound.  A split operand v = hi + lo + r with hi = bf16(v), lo = bf16(v - 
 2^-8 |v| and its bf16 rounding loses at most 2^-9 of that).  A product a*b taken as a_lo*b_hi + a_hi*b_lo + a_hi*b_hi differs
 from a*b by a_lo*b_lo + r_a*b + a*r_b (+ second order): at most 2^-16 + 2 * 2^-17 = 3 * 2^-18 |a*b| — 0.375 of the 2^-15 the
 tests allow per product; the rest is room for the fp32 accumulation of the short contractions used here (cin <= 96 forward).
-A CPU simulation of the split arithmetic stayed at <= 0.15 of the bound on every shape below; plain bf16 operands exceed it
-27-fold and a form with one cross term missing 19-fold, so the bound tells the split form from both."""
+A CPU simulation of the split arithmetic stayed at <= 0.15 of the bound on the first four shapes below; plain bf16 operands exceed it
+27-fold and a form with one cross term missing 19-fold, so the bound tells the split form from both.
+
+Deep shapes (SHAPES[4:]: 128-512 channels, 4-16 input chunks, contractions up to K = 4608, eight 4x4 images per tile).  The same
+CPU simulation (hi = bf16(v), lo = bf16(v - hi), three fp32 convolutions, this module's own seeded inputs) on those seven
+shapes, worst error as a multiple of the bound the test uses:
+    form                             correct split, largest     one cross term dropped, smallest   plain bf16, smallest
+    forward                          0.073 (256->512 1x1 s2)    7.2  (512->512 3x3)                11.0 (512->512 3x3)
+    data gradient + addend, gated    0.056 (128->256 s2 to 8x8) 6.9  (512->512 3x3)                 9.9 (512->512 3x3)
+    weight gradient                  0.20  (128->256 s2, 10x10) 16.7 (128->128 3x3)                27.4 (128->128 3x3)
+("dropped": the smaller of the two ways to drop a cross term; correct split at 512->512 3x3: 0.020 / 0.027 / 0.16.)  The
+data-gradient bound is REL * conv_transpose(|dz|, |w|) plus one fp32 rounding of the sum with the addend,
+2^-23 |conv_transpose(dz, w) + addend|.  REL separates right from wrong at every depth.
+
+Which form a geometry selects (`launch_wide`, 128-pixel tiles from `mil_geom_tiles(g, 7)`): maps wider or taller than 8 run 16x8
+tiles of one image (3x3 halo 10x18 = 180 pixels), maps up to 8x8 run 8x8 tiles of two images (2 x 10x10 = 200), maps up to 4x4 run
+4x4 tiles of eight images, whose 3x3 halo is 8 x 6x6 = 288 pixels: more than the 256 the pipelined form holds.  So every 3x3
+stride-1 or zero-insert launch on maps of at most 4x4 runs the plain wide_conv_kernel<F32S> by its geometry, no environment knob
+involved: SHAPES[9] (512 -> 512 on 4x4) and SHAPES[10], the smallest such launch (two chunks, one output block, 4x3 maps, a
+one-image second group).  1x1 launches (halo <= 128 pixels) always fit the pipelined form.  The fewer-images-per-tile fallback
+(`mil_geom_set(a.g, 3, 3, 1)`) is taken in split precision exactly where exact fp32 takes it (the same 144-byte pixel record
+and 72 KB filter slice): a 3x3 stride-2 FORWARD onto maps of at most 4x4, whose eight 9x9 halos are 648 pixels = 91 KB.
+SHAPES[6] (128 -> 256, 8x8 -> 4x4) is such a launch.  No stride-1 or zero-insert launch reaches the fallback (288 pixels are
+41 KB), and the weight gradient has none."""
 import functools
 import inspect
 import os
@@ -29,7 +51,16 @@ SHAPES = [
     (2, 10, 7, 96, 64, 1, 2, 0),        # 1x1 stride 2
     (3, 11, 11, 64, 128, 3, 2, 1),      # stride 2, odd map
     (5, 8, 8, 32, 64, 3, 1, 1),         # one chunk, two images per tile with a ragged last group
+    # the deep layers of the encoder (WIDE_CASES of test_gpu_kernels.py)
+    (2, 16, 16, 128, 128, 3, 1, 1),     # four chunks, 16x8 tiles
+    (2, 10, 10, 128, 256, 3, 2, 1),     # stride 2 onto 5x5 maps
+    (4, 8, 8, 128, 256, 3, 2, 1),       # stride 2 onto 4x4 maps: the forward takes the fewer-images-per-tile fallback
+    (5, 8, 8, 256, 256, 3, 1, 1),       # eight chunks, four output blocks, a one-image last group
+    (3, 8, 8, 256, 512, 1, 2, 0),       # the 1x1 stride-2 projection
+    (9, 4, 4, 512, 512, 3, 1, 1),       # sixteen chunks, K = 4608, eight images per tile: the plain kernel by its geometry
+    (9, 4, 3, 64, 64, 3, 1, 1),         # the smallest launch the geometry sends to the plain kernel (see the docstring)
 ]
+DEEP = list(range(4, len(SHAPES)))
 CASES = ["alt_l1111_n4_64", "alt_l2222_n2_96x80"]
 
 
@@ -51,7 +82,15 @@ def _problem(si):
         y = ops.wide_conv(x, wp, cout, ks=ks, stride=stride, pad=pad)
     y64 = F.conv2d(_nchw(x), wt.double().cpu(), stride=stride, padding=pad).permute(0, 2, 3, 1)
     bound = REL * F.conv2d(_nchw(x).abs(), wt.double().cpu().abs(), stride=stride, padding=pad).permute(0, 2, 3, 1)
-    return dict(x=x, w=wt, dz=dz, y=y, y64=y64, bound=bound)
+    g2 = torch.Generator().manual_seed(300 + si)         # the encoder's data-gradient call: an addend and a gate, shaped like x
+    addend, act = torch.randn((n, h, w, cin), generator=g2).cuda(), torch.randn((n, h, w, cin), generator=g2).cuda()
+    return dict(x=x, w=wt, dz=dz, y=y, y64=y64, bound=bound, addend=addend, act=act)
+
+
+def _dgrad_kw(si):
+    """The keyword arguments of `_Conv.dgrad` (alt_resnet.py) for SHAPES[si]: stride 2 is the zero-insert form."""
+    n, h, w, cin, cout, ks, stride, pad = SHAPES[si]
+    return dict(ks=ks, stride=1, pad=pad, zero_insert=True, out_hw=(h, w)) if stride == 2 else dict(ks=ks, stride=1, pad=pad)
 
 
 def _within(got, ref64, bound, what):
@@ -101,6 +140,29 @@ def test_wide_conv_split_zero_insert_dgrad_against_fp64():
     _within(dx, ref, bound, "zero-insert data gradient")
 
 
+@pytest.mark.parametrize("si", DEEP)
+def test_wide_conv_split_dgrad_with_addend_and_gate_against_fp64(si):
+    """The data gradient as `alt_resnet._backward` calls it: (conv_transpose(dz, w) + addend) * (act > 0) in one launch, the
+    zero-insert form at stride 2 (the 1x1 projection included), against fp64 per element."""
+    n, h, w, cin, cout, ks, stride, pad = SHAPES[si]
+    p = _problem(si)
+    wb = ops.wide_pack_weights(p["w"], L.PACK_DGRAD, L.BF16X3)
+    with L.f32_mma(L.MIL_DT_F32S):
+        dx = ops.wide_conv(p["dz"], wb, cin, res=p["addend"], act=p["act"], **_dgrad_kw(si))
+    assert tuple(dx.shape) == (n, h, w, cin)
+    w64, dz64 = p["w"].double().cpu(), _nchw(p["dz"])
+    ho, wo = dz64.shape[2:]
+    opad = (h - ((ho - 1) * stride - 2 * pad + ks), w - ((wo - 1) * stride - 2 * pad + ks))
+    lin = F.conv_transpose2d(dz64, w64, stride=stride, padding=pad, output_padding=opad).permute(0, 2, 3, 1)
+    mag = F.conv_transpose2d(dz64.abs(), w64.abs(), stride=stride, padding=pad, output_padding=opad).permute(0, 2, 3, 1)
+    assert tuple(lin.shape) == (n, h, w, cin)
+    total = lin + p["addend"].double().cpu()
+    gate = p["act"].cpu() > 0
+    _within(dx, total * gate, REL * mag + 2.0 ** -23 * total.abs(), f"data gradient + addend, gated {SHAPES[si]}")
+    off = dx.cpu()[~gate]
+    assert off.numel() > dx.numel() // 4 and bool((off == 0).all())            # gated-off elements are exactly 0
+
+
 # ---- 4c ---------------------------------------------------------------------------------------------------------------
 def test_wide_conv_split_epilogue_reads_exact_fp32():
     n, h, w, cin, cout, ks, stride, pad = SHAPES[0]
@@ -126,8 +188,10 @@ def test_wide_conv_split_epilogue_reads_exact_fp32():
 
 
 # ---- 4d ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("si", range(3))
+@pytest.mark.parametrize("si", [0, 1, 2] + DEEP)
 def test_wide_wgrad_split_against_fp64(si):
+    """SHAPES[9] (512 -> 512) has 128 (block, chunk) pairs and two tiles, SHAPES[8] 64 pairs and one: `run_wide_wgrad` clamps its
+    slabs per pair (512 / pairs) to the tile count."""
     n, h, w, cin, cout, ks, stride, pad = SHAPES[si]
     p = _problem(si)
     with L.f32_mma(L.MIL_DT_F32S):
@@ -151,14 +215,19 @@ PLAIN = "1000000000"       # MIL_PF_MIN_TILES above any tile count: the plain fo
 def test_wide_conv_split_pipelined_form_is_bit_identical_to_plain(monkeypatch):
     """wide_conv_x3_pf_kernel (stride-1 and zero-insert launches) against wide_conv_kernel<F32S> on the same problems: 3x3 with
     two chunks and ragged tiles, 3x3 with one chunk and a ragged image group, 1x1, the zero-insert data gradient, and the
-    full epilogue.  _problem() ran its stride-1 shapes on the pipelined form (checked against fp64 above)."""
+    full epilogue; the deep stride-1 shapes forward and as the gated data gradient with its addend, the deep zero-insert
+    launches (3x3 and the 1x1 projection) bare and with addend and gate.  _problem() ran its stride-1 shapes on the pipelined
+    form (checked against fp64 above).  SHAPES[9] and [10] run the plain kernel by their geometry either way (module
+    docstring): the knob changes nothing there."""
     runs = []
     for si, (n, h, w, cin, cout, ks, stride, pad) in enumerate(SHAPES):
         p = _problem(si)
         if stride == 1:
             runs.append((p["x"], p["w"], L.PACK_FWD, cout, dict(ks=ks, stride=1, pad=pad), p["y"]))
-        elif ks == 3:
-            runs.append((p["dz"], p["w"], L.PACK_DGRAD, cin, dict(ks=ks, stride=1, pad=pad, zero_insert=True, out_hw=(h, w)), None))
+        elif ks == 3 or si in DEEP:          # SHAPES[1] has no data gradient here: its 96 input channels are no multiple of 64
+            runs.append((p["dz"], p["w"], L.PACK_DGRAD, cin, _dgrad_kw(si), None))
+        if si in DEEP:
+            runs.append((p["dz"], p["w"], L.PACK_DGRAD, cin, dict(_dgrad_kw(si), res=p["addend"], act=p["act"]), None))
     p = _problem(0)
     gen = torch.Generator().manual_seed(13)
     res, act = (torch.randn(tuple(p["y"].shape), generator=gen).cuda() for _ in range(2))
@@ -166,7 +235,7 @@ def test_wide_conv_split_pipelined_form_is_bit_identical_to_plain(monkeypatch):
     x1 = p["x"]                                              # 1x1 stride 1 on the first shape's input
     w1 = torch.randn((128, 64, 1, 1), generator=gen).cuda() * 0.2
     runs.append((x1, w1, L.PACK_FWD, 128, dict(ks=1, stride=1, pad=0), None))
-    assert len(runs) == 5
+    assert len(runs) == 5 + 4 + 3 + 7           # deep: four stride-1 forwards, three bare zero-insert launches, seven gated gradients
     for x, w, mode, cout_x, kw, known in runs:
         wp = ops.wide_pack_weights(w, mode, L.BF16X3)
         with L.f32_mma(L.MIL_DT_F32S):

@@ -166,3 +166,46 @@ def test_forced_activation_pattern_reproduces_the_plain_run(golden_dir):
     assert float((f1 - f0).abs().max()) <= 1e-12 * float(f0.abs().max())
     for k in g0:
         assert float((g1[k] - g0[k]).abs().max()) <= 1e-10 * max(float(g0[k].abs().max()), 1e-30), k
+
+
+def alt_own_patterns(acts):
+    """The activation pattern of an `alt_backbone(acts=...)` run in the form its `patterns=` takes."""
+    import torch.nn.functional as F
+    stem = acts["stem"]
+    w = stem.shape[3]
+    _p, idx = F.max_pool2d(stem, 3, 2, 1, return_indices=True)
+    hp, wp = idx.shape[2:]
+    oy = torch.arange(hp).view(1, 1, hp, 1)
+    ox = torch.arange(wp).view(1, 1, 1, wp)
+    pat = {"stem_tap": (idx // w - (2 * oy - 1)) * 3 + (idx % w - (2 * ox - 1)), "stem_pos": acts["pool"] > 0}
+    pat.update({k: v > 0 for k, v in acts.items() if k.startswith("layer")})
+    return pat
+
+
+@pytest.mark.parametrize("name", ["alt_l1111_n4_64", "alt_l2222_n2_96x80"])
+def test_alt_forced_activation_pattern_reproduces_the_plain_run(golden_dir, name):
+    """`alt_backbone(patterns=...)` with the pattern of its own fp64 run gives that run's features and every parameter
+    gradient to 1e-12 — it is the reference of tests/test_gpu_alt_vjp.py."""
+    z = np.load(os.path.join(golden_dir, name + ".npz"))
+    layers = tuple(int(v) for v in z["layers"])
+    sd = {k: v.double().requires_grad_(True) for k, v in orc.alt_seeded_state(layers, int(z["num_classes"]), int(z["wseed"])).items()}
+    x, dfe = torch.from_numpy(z["x"]).double(), torch.from_numpy(z["dfeats"]).double()
+
+    def run(patterns, acts=None):
+        for v in sd.values():
+            v.grad = None
+        f = orc.alt_backbone(sd, x, layers, patterns=patterns, acts=acts)
+        f.backward(dfe)
+        return f.detach().clone(), {k: v.grad.clone() for k, v in sd.items()}
+
+    acts = {}
+    f0, g0 = run(None, acts)
+    pat = alt_own_patterns(acts)
+    assert int(pat["stem_tap"].min()) >= 0 and int(pat["stem_tap"].max()) <= 8
+    assert len(pat) == 2 + 2 * sum(layers)
+    f1, g1 = run(pat)
+    assert float((f1 - f0).abs().max()) <= 1e-12 * float(f0.abs().max())
+    assert set(g0) == set(k for k, _s in orc.alt_state_dict_spec(layers, int(z["num_classes"])))
+    for k in g0:
+        assert float(g0[k].abs().max()) > 0, k
+        assert float((g1[k] - g0[k]).abs().max()) <= 1e-12 * float(g0[k].abs().max()), k
