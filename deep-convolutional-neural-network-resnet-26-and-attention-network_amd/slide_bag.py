@@ -105,6 +105,19 @@ class SlideBag:
         self._ready()
         return self.prep.from_slide(self.slide, self.coords, None, out), self.coords.copy()
 
+    def attention_maps(self, output, scale, features=True, **renderer_args):
+        """The five tissue panels of the reference's `visualize` -> `create_map` (gbm/classify_combined.py:142-218) for one
+        forward's `output` dict over this bag's windows, uint8 [5, H//scale, W//scale, 3] on the slide's device
+        (`AttentionMapRenderer.render`): `A1` of `visualize_terms(output)` colours the rectangles, `output["Fterm"]` the
+        per-tile feature images (`features=False`: that panel stays white).  `renderer_args`: inset / alpha_tissue /
+        alpha_map of `AttentionMapRenderer`.  The ROIs themselves are not materialised."""
+        if self.coords is None:
+            raise RuntimeError("call build() first")
+        from .heatmap import AttentionMapRenderer
+        from .train import visualize_terms
+        renderer = AttentionMapRenderer(self.roi_size, scale, **renderer_args)
+        return renderer.render(self.slide, self.coords, visualize_terms(output)["A1"], output["Fterm"] if features else None)
+
     def rois(self, indices):
         """The chosen kept windows as pixels, uint8 [n,S,S,3] on the slide's device — materialised on request only."""
         if self.coords is None:

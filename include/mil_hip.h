@@ -230,6 +230,32 @@ int mil_tile_preprocess_win_u8(const uint8_t* base, int64_t base_bytes, const in
 int mil_roi_stats(const uint8_t* base, int64_t base_bytes, const int64_t* win_off, int64_t row_pitch, int n, int S,
                   int hue_min, int v_min, int v_max, int64_t* out, void* stream);
 
+/* Attention heat maps (gbm/classify_combined.py:169-218, create_map(): the five tissue axes of `tissue_plots`, :185) rendered at
+ * thumbnail scale from the source the windows lie in, instead of imshow() of every kept ROI ([T,1200,1200,3]) and one rectangle
+ * patch per tile on the host.  Windows: mil_roi_stats' source convention (base, base_bytes, DEVICE win_off [T], row_pitch, S x S
+ * interleaved RGB at any byte alignment, loads through buffer descriptors that end with the source).  D divides S; n = S / D.
+ * Window t owns the n x n block of output pixels whose top-left one is (out_pos[t][0], out_pos[t][1]) (row, col; DEVICE int32
+ * [T,2]) in each of the five panels of out, uint8 [5,Ht,Wt,3]; the part of a block outside [Ht,Wt] is not stored.  Blocks of
+ * two windows must not overlap (the caller's to ensure; overlapping blocks are written in no defined order).  All integer:
+ *     m[c]     = (sum over the window's pixels [aD,(a+1)D) x [bD,(b+1)D) of channel c + D*D/2) / (D*D)        for owned pixel (a,b)
+ *     panel 0  = m if i0 < 0, else (m*(256 - alpha_tissue) + jet_lut[i0][c]*alpha_tissue + 128) >> 8       (ax[0,0], :189-193)
+ *     panel 1  = viridis_lut[feat_idx[t][((a-g)*8/(n-2g))*10 + (b-g)*10/(n-2g)]][c] for g <= a,b < n-g, g = inset / D (0 when
+ *                n - 2g < 1); the border of the block and, with feat_idx == NULL, the whole panel are not written   (ax[0,1], :203)
+ *     panel 1+k = (255*(256 - alpha_map) + jet_lut[ik][c]*alpha_map + 128) >> 8 where ik >= 0, k = 1..3; else not written
+ *                                                                                                        (ax[1,0..2], :194-202)
+ * with ik = jet_idx[k*T + t] (DEVICE int16 [4,T]: row 0 the mean map, rows 1-3 the maps; negative = no rectangle, above 104
+ * read as 104), jet_lut uint8 [105,3], viridis_lut uint8 [256,3] (may be NULL with feat_idx), feat_idx uint8 [T,80] or NULL, the
+ * alphas in 1/256ths.  Pixels no window owns are not touched: the caller supplies the canvas.  The 32-bit channel sums hold
+ * 255*D*D + D*D/2 up to D = 4096: D > 4096 or n > 4000 (one output row's sums must fit 48 KB of LDS), and a row_pitch so large
+ * that the D source rows of one output row leave 31-bit offsets: MIL_ERR_UNSUPPORTED.  Null pointers (other than feat_idx and,
+ * with it, viridis_lut), S < 1, D < 1, S % D != 0, T < 0, base_bytes < 0, row_pitch < 3S, inset < 0, Ht or Wt < 1, an alpha outside
+ * [0,256]: MIL_ERR_ARG; T == 0: MIL_OK, no launch — all decided on the host before any GPU call.  Any T (launches of 65535
+ * windows).  No atomics on global memory, no workspace: bit-repeatable. */
+int mil_heatmap_render(const uint8_t* base, int64_t base_bytes, const int64_t* win_off, int64_t row_pitch, int T, int S, int D,
+                       const int32_t* out_pos, const int16_t* jet_idx, const uint8_t* feat_idx, const uint8_t* jet_lut,
+                       const uint8_t* viridis_lut, int inset, int alpha_tissue, int alpha_map, uint8_t* out, int Ht, int Wt,
+                       void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
