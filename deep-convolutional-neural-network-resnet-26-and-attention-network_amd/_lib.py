@@ -74,6 +74,7 @@ _SIGS = {
     "mil_tile_preprocess_win_u8": ([_vp, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_roi_stats": ([_vp, _c.c_int64, _vp, _c.c_int64, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "mil_heatmap_render": ([_vp, _c.c_int64, _vp, _c.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp], _i),
+    "mil_color_jitter_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
     "mil_stem_fwd_fused_xs": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_stem_fwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_block_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -16,13 +16,15 @@ class SlideBag:
     """slide: uint8 [H,W,3] (on the GPU for everything but the host bookkeeping).  `roi_size`, `padding`: the reference's
     `params['roi_size']` / `params['padding']`; `pad`: its Pad(100); `max_tiles`: the hard limit of `get_train_data`
     (RoiBuilder.py:230).  `selector`: a `RoiSelector` of the same roi_size (default: the reference's constants).  `coords`:
-    a loaded `coor_cache`, int [T,2] of (row, col) — `build()` then has nothing to do.
+    a loaded `coor_cache`, int [T,2] of (row, col) — `build()` then has nothing to do.  `color_jitter`: a `ColorJitter` —
+    `get_train_data` then jitters its tiles (RoiBuilder.py:200); validation and inference data never are.
 
     Unlike the reference, a bag with no kept window returns an EMPTY stack [0,3,R,R] from the three `get_*` methods, not the
     `torch.zeros(20,3,128,128)` placeholder of RoiBuilder.py:236,257 (which has neither the bag's resolution nor any tile of
     it); the caller decides what to do with a slide without tissue."""
 
-    def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None):
+    def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None,
+                 color_jitter=None):
         if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
             raise ValueError(f"expected a uint8 [H,W,3] slide, got {getattr(slide, 'dtype', type(slide))} "
                              f"{tuple(getattr(slide, 'shape', ()))}")
@@ -33,6 +35,7 @@ class SlideBag:
         if self.selector.roi_size != self.roi_size:
             raise ValueError(f"the selector cuts {self.selector.roi_size}-pixel windows, the bag {self.roi_size}-pixel ones")
         self.slide = slide
+        self.color_jitter = color_jitter
         self.coords = None                                   # coor_cache: int64 [T,2] numpy (row, col) once built
         if coords is not None:
             c = np.asarray(coords.cpu() if isinstance(coords, torch.Tensor) else coords)
@@ -84,15 +87,21 @@ class SlideBag:
             raise ValueError(f"choice must hold {self.max_tiles} distinct indices below {n}")
         return idx
 
-    def get_train_data(self, generator=None, choice=None, params=None, out="u8"):
+    def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None):
         """`get_train_data` (RoiBuilder.py:215-238): the cap of `choose`, then the train chain on the chosen windows with
-        `draw_params(generator)` or the injected `params` [n,4]."""
+        `draw_params(generator)` or the injected `params` [n,4].  A bag with a `color_jitter` then jitters the tiles with
+        `color_jitter.draw_params(n, generator)` (drawn after the crop / flip parameters) or the injected `jitter_params`;
+        a bag without one refuses `jitter_params`."""
         self._ready()
+        if jitter_params is not None and self.color_jitter is None:
+            raise ValueError("jitter_params given to a bag made without color_jitter=")
         idx = self.choose(generator, choice)
         c = self.coords if idx is None else self.coords[idx]
         if params is None:
             params = self.prep.draw_params(len(c), generator)
-        return self.prep.from_slide(self.slide, c, params, out)
+        if self.color_jitter is not None and jitter_params is None:
+            jitter_params = self.color_jitter.draw_params(len(c), generator)
+        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params)
 
     def get_validation_data(self, out="u8"):
         """`get_validation_data` (RoiBuilder.py:240-259): the flat chain on every kept window."""

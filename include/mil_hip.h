@@ -256,6 +256,27 @@ int mil_heatmap_render(const uint8_t* base, int64_t base_bytes, const int64_t* w
                        const uint8_t* viridis_lut, int inset, int alpha_tissue, int alpha_map, uint8_t* out, int Ht, int Wt,
                        void* stream);
 
+/* Colour jitter (RoiBuilder.py:200, the line the reference keeps commented out: transforms.ColorJitter(brightness=0.2,
+ * contrast=0.1, saturation=0.05, hue=0.02)) as torchvision's PIL backend computes it, IN PLACE on uint8 planar tiles [T,3,R,R]
+ * — what mil_tile_preprocess*_u8 write: after Resize and the flips, before ToTensor —, bit for bit Pillow's bytes.  Per tile t
+ * (all DEVICE arrays): order[t] (int32 [T,4]) the ops in the order they are applied, 0 brightness, 1 contrast, 2 saturation,
+ * 3 hue, any other value (-1) = no op, each op at most once; factors[t] (float [T,3]) = (fb, fc, fs); hue_shift[t] (int32 [T],
+ * its low 8 bits) what adjust_hue adds to h.
+ *     blend(d, x, a) = d + a * (x - d) in float32 (a rounded multiply, then a rounded add; no FMA), truncated to uint8 when
+ *                      0 <= a <= 1, otherwise 0 where <= 0, 255 where >= 255, truncated between        (libImaging/Blend.c)
+ *     L              = (19595 R + 38470 G + 7471 B + 0x8000) >> 16                                          (convert("L"))
+ *     brightness     blend(0, x, fb);      saturation  blend(L, x, fs)          (ImageEnhance.Brightness, ImageEnhance.Color)
+ *     contrast       blend(m, x, fc), m = (2 sum L + R*R) / (2 R*R) over the tile as it is when the op is reached
+ *                    = int(ImageStat.Stat(img.convert("L")).mean[0] + 0.5)                          (ImageEnhance.Contrast)
+ *     hue            convert("HSV"), h = (h + hue_shift) mod 256, convert("RGB"): Pillow's rgb2hsv / hsv2rgb with their
+ *                    float32 / double number formats; lossy also at shift 0                                   (adjust_hue)
+ * lsum (uint32 [T], device) is a caller-owned workspace: the call zeroes it (same stream) and leaves sum L of every tile with a
+ * contrast op in it; 255 R*R must fit 32 bits: R > 4096: MIL_ERR_UNSUPPORTED.  Null pointers, T < 0, R < 1: MIL_ERR_ARG;
+ * T == 0: MIL_OK, no launch — all decided on the host before any GPU call.  Any R >= 1 (the planes of a tile may start at any
+ * byte alignment; no access leaves a plane), any T (launches of 65535 tiles).  Integer sums only: bit-repeatable. */
+int mil_color_jitter_u8(uint8_t* tiles, const int32_t* order, const float* factors, const int32_t* hue_shift, uint32_t* lsum,
+                        int T, int R, void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
