@@ -91,7 +91,8 @@ class _Conv:
 
 
 class ResNet(nn.Module):
-    """[T,3,H,W] fp32 -> [T,num_classes] fp32 (alt_resnet.py:70-145)."""
+    """[T,3,H,W] fp32 (or the same tiles as `U8Tiles` / `S2dTiles`, see `forward`) -> [T,num_classes] fp32
+    (alt_resnet.py:70-145)."""
 
     def __init__(self, block=BasicBlock, layers=(2, 2, 2, 2), num_classes=1000, zero_init_residual=False, groups=1,
                  width_per_group=64, compute_dtype=torch.bfloat16):
@@ -137,6 +138,18 @@ class ResNet(nn.Module):
         return ps
 
     def forward(self, x):
+        """x: fp32 [T,3,H,W] tiles (the reference's tensor), or `preprocess.U8Tiles` — the same tiles as the uint8 images they
+        are (every compute mode; a CPU handle is moved to the module's device as uint8, nothing converts the stack to fp32) —
+        or `preprocess.S2dTiles`, the same tiles as the bf16 space-to-depth tensor the stem kernels read (bf16 compute mode
+        only).  The same handles `encoder.ResNet.forward` takes; features and gradients are bit for bit the fp32 tensor's.
+        What the backward re-reads is the handle's own tensor (the bytes, or the space-to-depth records): modifying it in
+        place between forward and backward raises."""
+        from .preprocess import S2dTiles, U8Tiles
+        if isinstance(x, S2dTiles):
+            x = x.xs
+        elif isinstance(x, U8Tiles):
+            x = x.u8.to(self.conv1.weight.device)
+        _feed_kind(x, self.compute_dtype)          # a feed the compute mode does not take raises here, before any device call
         return _AltFn.apply(self, x, *self.encoder_params())
 
 
@@ -164,20 +177,65 @@ def _packed_stem(net, dtype):
     return hit[1]
 
 
+def _feed_kind(x, mode):
+    """Which of the three feeds the tensor `x` is, "f32", "u8" or "s2d" (by its dtype, as `encoder.encoder_forward` tells them
+    apart); raises for a feed that `mode` does not take."""
+    if x.dtype == torch.bfloat16:       # the bf16 space-to-depth tensor [T,H/2,W/2,16] (preprocess.S2dTiles)
+        if x.dim() != 4 or x.shape[3] != 16:
+            raise ValueError(f"a bf16 input must be the space-to-depth tensor [T,H/2,W/2,16], got {tuple(x.shape)}")
+        if mode != torch.bfloat16:
+            raise ValueError("space-to-depth bf16 tiles feed the bf16 compute mode only (the fp32 modes take fp32 [T,3,H,W] tiles)")
+        return "s2d"
+    if x.dtype == torch.uint8:          # the uint8 images themselves (preprocess.U8Tiles): every compute mode
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"a uint8 input must be the planar tile stack [T,3,H,W], got {tuple(x.shape)}")
+        return "u8"
+    return "f32"
+
+
+def _stem_chain(xs, wp, bp):
+    """The three-call stem behind the space-to-depth tensor `xs` (shapes / modes without a fused kernel)."""
+    stem = ops.conv(xs, wp, bp, 64, ks=4, stride=1, pad=2, lrelu=True, slope=0.0)
+    pool, widx = ops.maxpool_fwd(stem)
+    return pool, widx, tuple(stem.shape[1:3])
+
+
 def _forward(net, x, mode):
     """`mode`: the compute mode the filters are packed for; the caller holds the matching `L.f32_mma`."""
     dtype = L.storage_dtype(mode)
+    kind = _feed_kind(x, mode)
     wp, bp = _packed_stem(net, mode)
-    fused = ops.stem_fwd_fused(x, wp, bp, 64, slope=0.0, dtype=dtype)
-    if fused is not None:
-        xs, pool, widx = fused
-        stem_hw = tuple(xs.shape[1:3])
+    # What the backward's stem weight gradient reads: the space-to-depth tensor `xs`.  The fp32 feed keeps the one its forward
+    # made; the uint8 feed keeps the BYTES (`x8`, a quarter of an fp32 stack, 0.37 of a bf16 xs) and rebuilds xs from them just
+    # before that call; the s2d feed's xs is the caller's own tensor.  `src` is the caller's tensor the backward depends on:
+    # its version counter is recorded, so an in-place change before backward raises instead of giving a wrong conv1 gradient.
+    x8 = src = None
+    if kind == "u8":
+        src, x8, xs = x, x.contiguous(), None
+        fused = ops.stem_fwd_fused_u8(x8, wp, bp, 64, slope=0.0, dtype=dtype)
+        if fused is not None:
+            pool, widx = fused
+            stem_hw = (x8.shape[2] // 2, x8.shape[3] // 2)
+        else:
+            pool, widx, stem_hw = _stem_chain(ops.stem_s2d_u8(x8, dtype), wp, bp)
+    elif kind == "s2d":
+        src, xs = x, x.contiguous()
+        fused = ops.stem_fwd_fused_xs(xs, wp, bp, 64, slope=0.0)
+        if fused is not None:
+            pool, widx = fused
+            stem_hw = tuple(xs.shape[1:3])
+        else:
+            pool, widx, stem_hw = _stem_chain(xs, wp, bp)
     else:
-        xs = ops.stem_s2d(x, dtype)
-        stem = ops.conv(xs, wp, bp, 64, ks=4, stride=1, pad=2, lrelu=True, slope=0.0)
-        pool, widx = ops.maxpool_fwd(stem)
-        stem_hw = tuple(stem.shape[1:3])
-    saved = {"xs": xs, "stem_hw": stem_hw, "widx": widx, "blocks": []}
+        fused = ops.stem_fwd_fused(x, wp, bp, 64, slope=0.0, dtype=dtype)
+        if fused is not None:
+            xs, pool, widx = fused
+            stem_hw = tuple(xs.shape[1:3])
+        else:
+            xs = ops.stem_s2d(x, dtype)
+            pool, widx, stem_hw = _stem_chain(xs, wp, bp)
+    saved = {"xs": xs, "x8": x8, "x_src": src, "x_version": None if src is None else src._version, "dtype": dtype,
+             "stem_hw": stem_hw, "widx": widx, "blocks": []}
     t = pool
     for blk in net.blocks():
         c1, c2 = _packed_conv(net, blk.conv1, mode), _packed_conv(net, blk.conv2, mode)
@@ -193,6 +251,10 @@ def _forward(net, x, mode):
 
 
 def _backward(net, saved, dfeats):
+    if saved["x_src"] is not None and saved["x_src"]._version != saved["x_version"]:
+        raise RuntimeError("the input tiles were modified in place between the encoder's forward and backward: conv1's gradient is "
+                           "computed from them (the uint8 / space-to-depth feed keeps the caller's tensor, not a copy).  Keep the "
+                           "tensor untouched until backward, or feed a clone")
     blocks = saved["blocks"]
     last_out = blocks[-1][2]
     dz, dwfc, dbfc = ops.avgpool_fc_bwd(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], last_out, 512,
@@ -212,7 +274,8 @@ def _backward(net, saved, dfeats):
         dz = c1.dgrad(dz1, xin.shape[1:3], addend=addend, act=mask)
         grads.append((g1, g2, gd))
     dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"], slope=0.0)
-    dwstem, _ = ops.conv_wgrad(saved["xs"], dstem, 3, 64, ks=4, stride=1, pad=2, stem=True, want_bias=False)
+    xs = saved["xs"] if saved["xs"] is not None else ops.stem_s2d_u8(saved["x8"], saved["dtype"])      # the uint8 feed: rebuilt here
+    dwstem, _ = ops.conv_wgrad(xs, dstem, 3, 64, ks=4, stride=1, pad=2, stem=True, want_bias=False)
     flat = [dwstem]
     for g1, g2, gd in reversed(grads):
         flat += [g1, g2]

@@ -55,9 +55,13 @@ __host__ __device__ constexpr int sf_lds_bytes() {
 // FROM_XS (bf16 only): the tiles arrive as the bf16 space-to-depth tensor itself — the s2d tile is a plain halo copy in
 // 16-byte pieces (1.07 GB read per 2048 tiles of 256x256 instead of 1.6 GB of fp32 in 304-byte plane segments), everything
 // behind it is the same code on the same LDS bytes: bit-identical pooled map and winner records.
-template <int NT, int NW, bool X3 = false, bool FROM_XS = false>
+// U8 (bf16 only): the tiles arrive as planar bytes (u8_feed.cuh).  The load items are the fp32 feed's — (row, pair, colour): four
+// columns of one plane in two rows — fetched as two 4-byte loads instead of two 16-byte loads (0.4 GB per 2048 tiles of
+// 256x256) and committed through mil_u8_item; behind the s2d tile, again the same code on the same LDS bytes.
+template <int NT, int NW, bool X3 = false, bool FROM_XS = false, bool U8 = false>
 __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kernel(StemFwdArgs a) {
     static_assert(!X3, "bf16 only");
+    static_assert(!(U8 && FROM_XS), "one feed at a time");
     using T = BF16;
     constexpr int PH = SF_PH;                                 // pooled rows per tile
     constexpr int SF_SH = sf_sh(PH), SF_XH = sf_xh(PH), SF_NITEM = sf_nitem(PH), SF_NSTEM = sf_nstem(PH), SF_MTILES = sf_mtiles(PH);
@@ -92,7 +96,8 @@ __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kerne
     }
     const int H = a.H, W = a.W, H2 = a.H2, W2 = a.W2, Ho = a.Ho, Wo = a.Wo;
     const __amdgpu_buffer_rsrc_t rs_x = FROM_XS ? mil_rsrc(a.xs_in, (unsigned)((size_t)a.n_img * H2 * W2 * 32))
-                                                : mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
+                                      : U8 ? mil_rsrc(a.x8, (unsigned)((size_t)a.n_img * 3 * H * W))
+                                           : mil_rsrc(a.x, (unsigned)((size_t)a.n_img * 3 * H * W * 4));
     const __amdgpu_buffer_rsrc_t rs_xs = mil_rsrc(a.xs, (unsigned)((size_t)a.n_img * H2 * W2 * 32));
     const __amdgpu_buffer_rsrc_t rs_p = mil_rsrc(a.pool, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP * OESZ));
     const __amdgpu_buffer_rsrc_t rs_i = mil_rsrc(a.widx, (unsigned)((size_t)a.n_img * Ho * Wo * COUTP));
@@ -114,7 +119,7 @@ __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kerne
             const int pair = idx % SF_NPAIR, t = idx / SF_NPAIR;
             const int c = t % 3, row = t / 3;
             l_lds[i] = ((row * SF_XW + 2 * pair) * SF_XPIX + c * 8) | (row << 18) | (pair << 24);
-            l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * 4;
+            l_rel[i] = ((c * H + 2 * row) * W + 4 * pair) * (U8 ? 1 : 4);
         }
     }
     // s2d tile interior -> xs tensor: 16-B piece id = tid + NTHR*i -> (row (NTHR/64)*i + tid>>6, col (tid>>1)&31, half tid&1)
@@ -155,7 +160,8 @@ __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kerne
     const int t_end = min(t_begin + per, a.ntiles);
     int tile = t_begin + (blockIdx.x >> 3);
 
-    u32x4_t r0[SF_NLOAD], r1[FROM_XS ? 1 : SF_NLOAD];
+    using LoadT = typename std::conditional<U8, unsigned, u32x4_t>::type;
+    LoadT r0[SF_NLOAD], r1[FROM_XS ? 1 : SF_NLOAD];
     auto fetch = [&](int t) {
         const int tx = t % a.tiles_x, q = t / a.tiles_x, ty = q % a.tiles_y, img = q / a.tiles_y;
         const int y0 = 2 * PH * ty - 3, c0 = 64 * tx - 8;        // first s2d row / first input column of the tile
@@ -170,14 +176,19 @@ __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kerne
             }
             return;
         }
-        const int base = (((img * 3) * H + 2 * y0) * W + c0) * 4;
+        const int base = (((img * 3) * H + 2 * y0) * W + c0) * (U8 ? 1 : 4);
 #pragma unroll
         for (int i = 0; i < SF_NLOAD; ++i) {
             const int row = (l_lds[i] >> 18) & 31, pair = l_lds[i] >> 24;
             const bool ok = (unsigned)(y0 + row) < (unsigned)H2 && (unsigned)(c0 + 4 * pair) < (unsigned)W;      // row 31 is never inside
             const unsigned off = ok ? (unsigned)(base + l_rel[i]) : MIL_OOB;
-            r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
-            r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(W * 4), 0, 0);
+            if constexpr (U8) {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, off + (unsigned)W, 0, 0);
+            } else {
+                r0[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0);
+                r1[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + (unsigned)(W * 4), 0, 0);
+            }
         }
     };
     if (tile < t_end) fetch(tile);
@@ -194,11 +205,18 @@ __global__ __launch_bounds__(64 * NW, NT <= 2 ? 2 : 1) void stem_fwd_fused_kerne
         } else
 #pragma unroll
         for (int i = 0; i < SF_NLOAD; ++i) {
-            const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
-            const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
             bf16x4_t pa, pb;
+            if constexpr (U8) {      // out-of-image items commit zeros (the conv's padding), not decode(0) = -1
+                const int row = (l_lds[i] >> 18) & 31, pair = l_lds[i] >> 24;
+                const bool ok = (unsigned)(2 * PH * ty - 3 + row) < (unsigned)H2 && (unsigned)(64 * tx - 8 + 4 * pair) < (unsigned)W;
+                bf16x4_t qa, qb;
+                mil_u8_item<false>(r0[i], r1[i], ok, pa, pb, qa, qb);
+            } else {
+                const f32x4_t v0 = __builtin_bit_cast(f32x4_t, r0[i]), v1 = __builtin_bit_cast(f32x4_t, r1[i]);
+                const float fa[4] = {v0[0], v0[1], v1[0], v1[1]}, fb[4] = {v0[2], v0[3], v1[2], v1[3]};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+                for (int j = 0; j < 4; ++j) { pa[j] = (__bf16)fa[j]; pb[j] = (__bf16)fb[j]; }
+            }
             char* dst = smem + (l_lds[i] & 0x3FFFF);
             *reinterpret_cast<bf16x4_t*>(dst) = pa;
             *reinterpret_cast<bf16x4_t*>(dst + SF_XPIX) = pb;
@@ -842,18 +860,18 @@ static int launch_stem_fwd_pool(StemFwdArgs a, hipStream_t st) {
 
 #include "stem_walk.cuh"
 
-template <int NT, bool FROM_XS = false>
+template <int NT, bool FROM_XS = false, bool U8 = false>
 static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
     constexpr int COUTP = mil_nt_to_cp(NT);
     constexpr int OESZ = 2;
     const int lds = sf_lds_bytes<NT>();
     constexpr int NW = 4;
     a.tiles_y = (a.Ho + SF_PH - 1) / SF_PH;
-    auto kern = stem_fwd_fused_kernel<NT, NW, false, FROM_XS>;
+    auto kern = stem_fwd_fused_kernel<NT, NW, false, FROM_XS, U8>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return MIL_ERR_LAUNCH;
     // every tensor is addressed with 32-bit offsets below 2 GiB: split the launch by images
-    size_t per_img = FROM_XS ? 0 : (size_t)3 * a.H * a.W * 4;
+    size_t per_img = FROM_XS ? 0 : (size_t)3 * a.H * a.W * (U8 ? 1 : 4);
     const size_t xs_img = (size_t)a.H2 * a.W2 * 32, p_img = (size_t)a.Ho * a.Wo * COUTP * OESZ;
     if (xs_img > per_img) per_img = xs_img;
     if (p_img > per_img) per_img = p_img;
@@ -863,6 +881,7 @@ static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
         StemFwdArgs b = a;
         b.n_img = n_total - i0 < chunk ? n_total - i0 : chunk;
         b.x = a.x ? a.x + (size_t)i0 * 3 * a.H * a.W : nullptr;
+        b.x8 = a.x8 ? a.x8 + (size_t)i0 * 3 * a.H * a.W : nullptr;
         b.xs_in = a.xs_in ? a.xs_in + (size_t)i0 * a.H2 * a.W2 * 16 : nullptr;
         b.xs = a.xs ? a.xs + (size_t)i0 * a.H2 * a.W2 * 16 : nullptr;
         b.pool = static_cast<char*>(a.pool) + (size_t)i0 * a.Ho * a.Wo * COUTP * OESZ;
@@ -879,7 +898,7 @@ static int launch_stem_fwd(StemFwdArgs a, hipStream_t st) {
         MIL_CHECK_LAUNCH();
 #ifdef MIL_STAMP
         static const char* const ph[7] = {"convert", "barrier-x", "fetch-issue", "gemm", "stem-store", "barrier-s", "pool"};
-        sb.report("stem_fwd_fused_kernel", grid, NW, 7, ph, st);
+        sb.report(U8 ? "stem_fwd_fused_kernel<u8>" : "stem_fwd_fused_kernel", grid, NW, 7, ph, st);
 #endif
     }
     return MIL_OK;
@@ -913,14 +932,17 @@ extern "C" int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const 
 }
 
 // The same pass fed by uint8 tiles x [n,3,H,W] (planar bytes standing for ((u / 255) - 0.5) / 0.5, u8_feed.cuh): pool / widx are
-// bit-identical to mil_stem_fwd_fused(decoded tiles, xs = NULL).  20-channel stem (cout_p 24), bf16 or split precision; no
-// space-to-depth copy (the backward is mil_stem_bwd_fused_u8).  H even, W % 4 == 0, x 4-byte aligned, else MIL_ERR_UNSUPPORTED.
+// bit-identical to mil_stem_fwd_fused(decoded tiles, xs = NULL).  20-channel stem (cout_p 24): bf16 or split precision, the
+// backward is mil_stem_bwd_fused_u8.  64-channel stem (cout_p 64, alt_resnet): bf16 only — no fused 64-channel split-precision
+// stem exists for any feed — and the caller rebuilds the space-to-depth tensor for the weight gradient (mil_stem_s2d_u8).  No
+// space-to-depth copy is written.  H even, W % 4 == 0, x 4-byte aligned, else MIL_ERR_UNSUPPORTED.
 extern "C" int mil_stem_fwd_fused_u8(const uint8_t* x_u8, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx,
                                      int n_img, int H, int W, int cout_p, float slope, int dtype, void* stream) {
     if (!x_u8 || !wpack || !pool || !widx || n_img < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
     if ((dtype != MIL_DT_BF16 && dtype != MIL_DT_F32S) || (H & 1) || (W & 3) || (reinterpret_cast<uintptr_t>(x_u8) & 3) || slope < 0.f || slope >= 1.f)
         return MIL_ERR_UNSUPPORTED;
-    if (cout_p != 24) return MIL_ERR_UNSUPPORTED;
+    if (cout_p != 24 && cout_p != 64) return MIL_ERR_UNSUPPORTED;
+    if (cout_p == 64 && dtype != MIL_DT_BF16) return MIL_ERR_UNSUPPORTED;
     if (n_img == 0) return MIL_OK;
     StemFwdArgs a{};
     a.x8 = x_u8; a.w = wpack; a.bias = bias_pad; a.pool = pool; a.widx = widx;
@@ -929,6 +951,7 @@ extern "C" int mil_stem_fwd_fused_u8(const uint8_t* x_u8, const void* wpack, con
     a.tiles_y = (a.Ho + 7) / 8; a.tiles_x = (a.Wo + 15) / 16;
     a.slope = slope;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (cout_p == 64) return launch_stem_fwd<4, false, true>(a, st);
     if (mil_stem_walk_wanted(a, mil_num_cus() * 2))
         return dtype == MIL_DT_F32S ? launch_stem_fwd_walk<true, true>(a, st) : launch_stem_fwd_walk<false, true>(a, st);
     return dtype == MIL_DT_F32S ? launch_stem_fwd_pool<true, false, true>(a, st) : launch_stem_fwd_pool<false, false, true>(a, st);

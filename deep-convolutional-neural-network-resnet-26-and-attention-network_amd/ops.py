@@ -467,13 +467,16 @@ def stem_fwd_fused(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat
 def stem_fwd_fused_u8(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat16):
     """(pool, widx) of the whole stem in one pass over uint8 tiles x [n,3,H,W] (see mil_stem_fwd_fused_u8): bit for bit
     stem_fwd_fused(decoded tiles, keep_s2d=False).  None when the shape / dtype has no fused kernel (the caller then runs
-    stem_s2d_u8 / conv / maxpool_fwd)."""
+    stem_s2d_u8 / conv / maxpool_fwd).  cout_p 24 (the narrow encoder: bf16 or split precision) or 64 (alt_resnet: bf16 only)."""
     _need_u8_tiles(x)
     n, c, h, w = x.shape
     code = L.dt_code(dtype, mma=True)
-    if code != L.MIL_DT_F32S and dtype != torch.bfloat16:
+    if code == L.MIL_DT_F32S:               # split precision: the 20-channel stem only, as stem_fwd_fused
+        if cout_p != 24:
+            return None
+    elif dtype != torch.bfloat16:
         return None
-    if h % 2 or w % 4 or cout_p != 24 or x.data_ptr() % 4:
+    if h % 2 or w % 4 or cout_p not in (24, 64) or x.data_ptr() % 4:
         return None
     h2, w2 = h // 2, w // 2
     hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1

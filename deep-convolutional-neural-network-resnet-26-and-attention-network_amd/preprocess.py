@@ -15,7 +15,8 @@ from . import _lib as L
 class S2dTiles:
     """A stack of tiles held as the bf16 space-to-depth tensor the stem kernels read, `xs [T, R/2, R/2, 16]` (channel =
     c*4 + dy*2 + dx of the 2x2 pixel block, 12 real): what `TilePreprocessor(..., out="s2d")` returns and what
-    `Attention.forward` / `forward_bags` / `ResNet.forward` accept in place of the fp32 `[T,3,R,R]` stack (bf16 compute mode).
+    `Attention.forward` / `forward_bags` / `ResNet.forward` of both encoders (`encoder.ResNet`, `alt_resnet.ResNet`) accept in
+    place of the fp32 `[T,3,R,R]` stack (bf16 compute mode).
     `shape` is the shape of the fp32 stack it stands for; indexing with a tensor / slice selects tiles."""
 
     def __init__(self, xs):
@@ -53,7 +54,8 @@ class U8Tiles:
     """A stack of tiles held as the 8-bit images they are: `u8 [T,3,H,W]` uint8, planar (the fp32 tensor's own indexing, one
     byte per element), standing for the fp32 stack `((u8.float() / 255) - 0.5) / 0.5` that ToTensor + Normalize(.5,.5) makes of
     them (RoiBuilder.py:193-210).  What `TilePreprocessor(..., out="u8")` returns and what `Attention.forward` / `forward_bags` /
-    `forward_tile_parallel` / `ResNet.forward` accept in place of the fp32 stack in EVERY compute mode: the decode is lossless,
+    `forward_tile_parallel` / `ResNet.forward` of both encoders (`encoder.ResNet`, `alt_resnet.ResNet`) accept in place of the
+    fp32 stack in EVERY compute mode: the decode is lossless,
     so outputs and gradients are bit for bit those of the fp32 tensor, at a quarter of its bytes.  A handle on the CPU is
     moved to the module's device as uint8.  Same surface as `S2dTiles`, plus `.float()`."""
 

@@ -379,10 +379,13 @@ int mil_stem_fwd_fused(const float* x_nchw, const void* wpack, const float* bias
 int mil_stem_fwd_fused_xs(const void* xs, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx, int n_img,
                           int H2, int W2, int cout_p, float slope, int dtype, void* stream);
 /* The same pass fed by uint8 tiles x_u8 [n,3,H,W] (the uint8 feed above; RoiBuilder.py:203-204 -> gbm/model.py:24-26,51-53 without
- * the fp32 stack in between): mil_stem_fwd_fused with xs == NULL, cout_p == 24, dtype MIL_DT_BF16 or MIL_DT_F32S.  pool / widx are
- * bit-identical to mil_stem_fwd_fused on the decoded tiles; the tiled and the row-walk kernel are chosen by the same rule
- * (MIL_STEM_WALK included).  H even, W % 4 == 0, x_u8 4-byte aligned, else MIL_ERR_UNSUPPORTED (the caller then runs
- * mil_stem_s2d_u8 / mil_conv_igemm / mil_maxpool_fwd).  The backward is mil_stem_bwd_fused_u8. */
+ * the fp32 stack in between): mil_stem_fwd_fused with xs == NULL.  cout_p == 24 (the 20-channel stem): dtype MIL_DT_BF16 or
+ * MIL_DT_F32S, the tiled and the row-walk kernel are chosen by the same rule (MIL_STEM_WALK included), the backward is
+ * mil_stem_bwd_fused_u8.  cout_p == 64 (alt_resnet's stem): MIL_DT_BF16 only (MIL_DT_F32S is MIL_ERR_UNSUPPORTED: there is no
+ * fused 64-channel split-precision stem for any feed), the tiled kernel; the stem weight gradient reads the space-to-depth
+ * tensor, which the caller rebuilds with mil_stem_s2d_u8.  pool / widx are bit-identical to mil_stem_fwd_fused on the decoded
+ * tiles.  H even, W % 4 == 0, x_u8 4-byte aligned, else MIL_ERR_UNSUPPORTED (the caller then runs mil_stem_s2d_u8 /
+ * mil_conv_igemm / mil_maxpool_fwd). */
 int mil_stem_fwd_fused_u8(const uint8_t* x_u8, const void* wpack, const float* bias_pad, void* pool, uint8_t* widx, int n_img,
                           int H, int W, int cout_p, float slope, int dtype, void* stream);
 
