@@ -108,6 +108,10 @@ _SIGS = {
     "mil_pack_job_bytes": ([], _i),
     "mil_pack_job_fill": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i], _i),
     "mil_pack_all": ([_vp, _i, _vp], _i),
+    "mil_stats_job_bytes": ([], _i),
+    "mil_stats_job_fill": ([_vp, _vp, _c.c_longlong, _i, _i, _i], _i),
+    "mil_tensor_stats_workspace": ([_c.POINTER(_sz), _vp, _i], _i),
+    "mil_tensor_stats_all": ([_vp, _vp, _i, _vp, _vp, _sz, _vp], _i),
     "mil_head_workspace_floats": ([_c.POINTER(_sz), _i, _i], _i),
     "mil_head_grad_floats": ([], _i),
     "mil_head_rec_floats": ([], _i),

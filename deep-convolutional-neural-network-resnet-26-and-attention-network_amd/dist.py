@@ -29,6 +29,7 @@ class FlatParams:
 
     def __init__(self, module):
         self.params = [p for p in module.parameters() if p.requires_grad]
+        self.names = [n for n, p in module.named_parameters() if p.requires_grad]      # the same order (summary.parameter_stats)
         if not self.params:
             raise ValueError("module has no trainable parameters")
         dev = self.params[0].device

@@ -88,6 +88,8 @@ class ResNet(nn.Module):
         self._pack_table = None
         self._pack_version = None
         self._side = None
+        # a `summary.ActivationSummary` while one is attached: handed the tensors the forward keeps anyway, after the last launch
+        self.activation_summary = None
 
     def _make_layer(self, planes, blocks, stride=1):
         shortcut = None
@@ -380,6 +382,9 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
             hooks.fire(net.avgpool, hooks.nchw(t, STAGE_WIDTHS[-1]), pooled.view(pooled.shape[0], -1, 1, 1))
         if hooks.hooked(net.fc):
             hooks.fire(net.fc, pooled, feats)
+    watcher = getattr(net, "activation_summary", None)      # (getattr: a module object pickled before the attribute existed)
+    if watcher is not None:             # statistics of what the kernels stored, read where it lies (summary.py)
+        watcher.observe(pool, saved["blocks"], pooled, feats)
     return feats, saved
 
 

@@ -68,6 +68,30 @@ class BagTrainer:
             self.pending = 0
 
 
+def _layer_weight_records(named_parameters):
+    from .summary import parameter_stats
+    names, stats = parameter_stats(list(named_parameters))
+    return names, stats.cpu().tolist()                # the one device-to-host copy
+
+
+def layer_weight_summary_mean(named_parameters):
+    """`epoch_stats['model_mean_weights']` (gbm/classify_combined.py:484): {parameter name: float}, the shape
+    `plot_layer_metrics.py` plots per layer and epoch.  The reference's helper module is not part of its tree, so
+    the reading is this project's: the ARITHMETIC MEAN OF THE ELEMENTS of each parameter (the fp64 sum of the fp32 elements over
+    their number).  All parameters in one device call and one copy (`summary.parameter_stats`, which also carries min and max
+    for anyone who wants |w|).  A parameter that holds a NaN / inf element reports nan."""
+    names, recs = _layer_weight_records(named_parameters)
+    return {n: (r[1] / r[7] if r[6] == 0 and r[7] else float("nan")) for n, r in zip(names, recs)}
+
+
+def layer_weight_summary_max(named_parameters):
+    """`epoch_stats['model_max_weights']` (gbm/classify_combined.py:485): {parameter name: float}.  This project's reading (see
+    `layer_weight_summary_mean`): the LARGEST ELEMENT of each parameter (signed, not |w|), exactly as stored.  A parameter that
+    holds a NaN / inf element reports nan."""
+    names, recs = _layer_weight_records(named_parameters)
+    return {n: (r[4] if r[6] == 0 and r[7] else float("nan")) for n, r in zip(names, recs)}
+
+
 def _minmax_f32(values):
     """`matplotlib.colors.Normalize()(x)` with autoscaling, restated.  matplotlib and numpy are third-party code
     outside the reference tree (matplotlib 3.10.8 / numpy 2.2 in this image; the reference pins no versions):

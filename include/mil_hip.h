@@ -514,6 +514,26 @@ int mil_pack_job_fill(void* job_host, const float* w, const float* bias, void* o
                       int ks, int mode, int dtype);
 int mil_pack_all(const void* jobs_device, int njobs, void* stream);
 
+/* ---- per-tensor summaries (gbm/classify_combined.py:418 prime_activation_summary, :484-485 weight mean / max) -------
+ * Statistics of a whole TABLE of tensors read where they lie, in TWO launches (per-chunk partial records, then one
+ * finishing workgroup per tensor): no copy, no host synchronisation, no atomics, bit-repeatable.
+ * A job is `n_pix` records of `c_pad` elements (MIL_DT_F32 or MIL_DT_BF16) of which the first `c_real` count: a
+ * channel-padded NHWC activation, or with c_real = c_pad = 1 a flat run such as one parameter inside the flat bucket.
+ * `x` needs the alignment of its element only.  out[job][8] (fp64): [0] finite elements, [1] their sum, [2] their sum
+ * of squares, [3] min and [4] max over them (+inf / -inf when there is none), [5] finite elements < 0 (-0.0 is not),
+ * [6] NaN / +-inf elements, [7] n_pix * c_real.  Pad channels are never read into a statistic.  Elements are widened
+ * exactly and added in fp64 in an order that depends on the job's (n_pix, c_pad, dtype) alone.
+ * The table is mil_stats_job_bytes()-sized records filled on the host by mil_stats_job_fill; the caller hands the host
+ * table and a device copy of it.  mil_tensor_stats_workspace: bytes of `ws` for a table; the call writes every word of
+ * `out` and reads no word of `ws` it has not written itself.  njobs == 0: MIL_OK, nothing launched.  Argument errors
+ * (null pointer, c_real < 1, c_real > c_pad, n_pix < 0, njobs < 0, short ws: MIL_ERR_ARG; another dtype:
+ * MIL_ERR_UNSUPPORTED) are decided on the host before any GPU call. */
+int mil_stats_job_bytes(void);
+int mil_stats_job_fill(void* job_host, const void* x, long long n_pix, int c_real, int c_pad, int dtype);
+int mil_tensor_stats_workspace(size_t* bytes, const void* jobs_host, int njobs);
+int mil_tensor_stats_all(const void* jobs_device, const void* jobs_host, int njobs, double* out, void* ws,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
