@@ -188,6 +188,11 @@ def mma_code(compute_dtype):
     return MIL_DT_F32S if compute_dtype == BF16X3 else MIL_DT_F32
 
 
+def is_split(dtype):
+    """True inside `f32_mma(MIL_DT_F32S)` for the fp32 tensors of the split-precision mode (BF16X3)."""
+    return dtype == torch.float32 and _F32_MMA.code == MIL_DT_F32S
+
+
 def dt_code(dtype, dense_grads=False, mma=False):
     """MIL_DT_* code of a compute dtype; dense_grads selects MIL_DT_BF16_DGRAD / MIL_DT_F32S_DGRAD (gradient tensors of the
     20-channel layer at 20 channels per pixel instead of 24; see include/mil_hip.h).  mma=True (the convolution entry points and the filter

@@ -149,7 +149,7 @@ class ResNet(nn.Module):
             x = x.xs
         elif isinstance(x, U8Tiles):
             x = x.u8.to(self.conv1.weight.device)
-        _feed_kind(x, self.compute_dtype)          # a feed the compute mode does not take raises here, before any device call
+        ops.stem_feed_kind(x, self.compute_dtype)  # a feed the compute mode does not take raises here, before any device call
         return _AltFn.apply(self, x, *self.encoder_params())
 
 
@@ -177,65 +177,22 @@ def _packed_stem(net, dtype):
     return hit[1]
 
 
-def _feed_kind(x, mode):
-    """Which of the three feeds the tensor `x` is, "f32", "u8" or "s2d" (by its dtype, as `encoder.encoder_forward` tells them
-    apart); raises for a feed that `mode` does not take."""
-    if x.dtype == torch.bfloat16:       # the bf16 space-to-depth tensor [T,H/2,W/2,16] (preprocess.S2dTiles)
-        if x.dim() != 4 or x.shape[3] != 16:
-            raise ValueError(f"a bf16 input must be the space-to-depth tensor [T,H/2,W/2,16], got {tuple(x.shape)}")
-        if mode != torch.bfloat16:
-            raise ValueError("space-to-depth bf16 tiles feed the bf16 compute mode only (the fp32 modes take fp32 [T,3,H,W] tiles)")
-        return "s2d"
-    if x.dtype == torch.uint8:          # the uint8 images themselves (preprocess.U8Tiles): every compute mode
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"a uint8 input must be the planar tile stack [T,3,H,W], got {tuple(x.shape)}")
-        return "u8"
-    return "f32"
-
-
-def _stem_chain(xs, wp, bp):
-    """The three-call stem behind the space-to-depth tensor `xs` (shapes / modes without a fused kernel)."""
-    stem = ops.conv(xs, wp, bp, 64, ks=4, stride=1, pad=2, lrelu=True, slope=0.0)
-    pool, widx = ops.maxpool_fwd(stem)
-    return pool, widx, tuple(stem.shape[1:3])
-
-
 def _forward(net, x, mode):
     """`mode`: the compute mode the filters are packed for; the caller holds the matching `L.f32_mma`."""
     dtype = L.storage_dtype(mode)
-    kind = _feed_kind(x, mode)
+    kind = ops.stem_feed_kind(x, mode)
     wp, bp = _packed_stem(net, mode)
-    # What the backward's stem weight gradient reads: the space-to-depth tensor `xs`.  The fp32 feed keeps the one its forward
-    # made; the uint8 feed keeps the BYTES (`x8`, a quarter of an fp32 stack, 0.37 of a bf16 xs) and rebuilds xs from them just
-    # before that call; the s2d feed's xs is the caller's own tensor.  `src` is the caller's tensor the backward depends on:
-    # its version counter is recorded, so an in-place change before backward raises instead of giving a wrong conv1 gradient.
-    x8 = src = None
-    if kind == "u8":
-        src, x8, xs = x, x.contiguous(), None
-        fused = ops.stem_fwd_fused_u8(x8, wp, bp, 64, slope=0.0, dtype=dtype)
-        if fused is not None:
-            pool, widx = fused
-            stem_hw = (x8.shape[2] // 2, x8.shape[3] // 2)
-        else:
-            pool, widx, stem_hw = _stem_chain(ops.stem_s2d_u8(x8, dtype), wp, bp)
-    elif kind == "s2d":
-        src, xs = x, x.contiguous()
-        fused = ops.stem_fwd_fused_xs(xs, wp, bp, 64, slope=0.0)
-        if fused is not None:
-            pool, widx = fused
-            stem_hw = tuple(xs.shape[1:3])
-        else:
-            pool, widx, stem_hw = _stem_chain(xs, wp, bp)
-    else:
-        fused = ops.stem_fwd_fused(x, wp, bp, 64, slope=0.0, dtype=dtype)
-        if fused is not None:
-            xs, pool, widx = fused
-            stem_hw = tuple(xs.shape[1:3])
-        else:
-            xs = ops.stem_s2d(x, dtype)
-            pool, widx, stem_hw = _stem_chain(xs, wp, bp)
-    saved = {"xs": xs, "x8": x8, "x_src": src, "x_version": None if src is None else src._version, "dtype": dtype,
-             "stem_hw": stem_hw, "widx": widx, "blocks": []}
+    xc = x.contiguous()
+    xs, pool, widx, stem_hw, _ = ops.stem_forward(kind, xc, wp, bp, 64, dtype=dtype, slope=0.0, keep_s2d=True)
+    # What the backward's stem weight gradient reads is the space-to-depth tensor xs; what is saved for it, decided here:
+    #   f32: the xs its forward made, no version check
+    #   u8:  the contiguous BYTES (`x8`, a quarter of an fp32 stack, 0.37 of a bf16 xs); xs is rebuilt just before conv_wgrad
+    #   s2d: the caller's own tensor
+    # `x_src` is the caller's tensor the backward depends on (u8, s2d): its version counter is recorded, so an in-place
+    # change before backward raises instead of giving a wrong conv1 gradient.
+    src = None if kind == "f32" else x
+    saved = {"xs": None if kind == "u8" else xs, "x8": xc if kind == "u8" else None, "x_src": src,
+             "x_version": None if src is None else src._version, "dtype": dtype, "stem_hw": stem_hw, "widx": widx, "blocks": []}
     t = pool
     for blk in net.blocks():
         c1, c2 = _packed_conv(net, blk.conv1, mode), _packed_conv(net, blk.conv2, mode)

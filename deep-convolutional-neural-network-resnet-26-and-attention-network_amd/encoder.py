@@ -169,7 +169,7 @@ class ResNet(nn.Module):
             L.check(lib.mil_pack_all(table.data_ptr(), njobs, L.stream_ptr()), "mil_pack_all")
             self._pack_version = ver
 
-    def _packed(self, key, weight, bias, mode, dtype):
+    def _packed(self, key, mode):
         return self._pack_table[2][(key, mode)]
 
     # ---- forward hooks on children (the reference's children are live modules: SURVEY.md §8b) ----------------
@@ -220,89 +220,39 @@ def encoder_forward(net, x, dtype):
     """Runs the kernels; returns (feats [T,80] fp32, saved-state dict for the backward)."""
     net.refresh_packed(dtype)
     x = x.contiguous()                  # the tensor the kernels read — and, without a kept s2d copy, the one the backward re-reads
+    kind = ops.stem_feed_kind(x, dtype)
     hk = net.child_hooks()              # None unless a forward hook sits on a child module (then views are built for it)
-    wp, bp = net._packed("stem", net.conv1.weight, net.conv1.bias, L.PACK_STEM, dtype)
+    wp, bp = net._packed("stem", L.PACK_STEM)
     stem_hooked = hk is not None and hooks.any_hooked((net.conv1, net.relu, net.maxpool))
-    if x.dtype == torch.bfloat16:       # the tiles arrive as the bf16 space-to-depth tensor [T,H/2,W/2,16] (preprocess.S2dTiles)
-        if x.dim() != 4 or x.shape[3] != 16:
-            raise ValueError(f"a bf16 input must be the space-to-depth tensor [T,H/2,W/2,16], got {tuple(x.shape)}")
-        if dtype != torch.bfloat16:
-            raise ValueError("space-to-depth bf16 tiles feed the bf16 compute mode only (the fp32 modes take fp32 [T,3,H,W] tiles)")
-        return _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in=x)
-    if x.dtype == torch.uint8:          # the tiles arrive as the uint8 images they are (preprocess.U8Tiles): every compute mode
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"a uint8 input must be the planar tile stack [T,3,H,W], got {tuple(x.shape)}")
-        return _encoder_forward_from_u8(net, x, dtype, hk, stem_hooked, wp, bp)
-    return _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in=None)
-
-
-def _encoder_forward_from_u8(net, x, dtype, hk, stem_hooked, wp, bp):
-    """The stem of `_encoder_forward_from` for uint8 tiles: the decisions the fp32 input takes (fused forward or the three-call
-    chain, what the backward re-reads), the uint8 tensor saved in place of the fp32 one.  Nothing converts the stack to fp32
-    (a hooked stem is handed `U8Tiles(x).float()`, as the reference's hook would see)."""
-    if net.keep_s2d:
-        x = x.clone()                   # `keep_s2d`: a library-owned copy for the backward — here the uint8 tensor itself
-    fused = ops.stem_fwd_fused_u8(x, wp, bp, ops.cpad(STEM_WIDTH), dtype=dtype) if (net.fuse_stem_forward and not stem_hooked) else None
-    split = dtype == torch.float32 and L.dt_code(dtype, mma=True) == L.MIL_DT_F32S
-    xs = None
-    if fused is not None:
-        pool, widx = fused
-        stem_hw = (x.shape[2] // 2, x.shape[3] // 2)
-        if not net.fuse_backward and not split:      # the un-fused backward wants the s2d tensor anyway (as keep_s2d of the fp32 feed)
-            xs = ops.stem_s2d_u8(x, dtype)
-    else:
+    split = L.is_split(dtype)           # bf16x3: no s2d form feeds its fused kernels
+    # What the stem keeps for the backward: the one place it is decided.  xs: the space-to-depth tensor; x: the tiles.
+    #   feed | keep_s2d set                                      | no keep_s2d          | saved for the backward
+    #   f32  | split: an fp32 clone of the tiles.  Otherwise the | x is saved and its   | as left
+    #        | fused forward writes xs (also written when        | version recorded     |
+    #        | not fuse_backward)                                |                      |
+    #   u8   | a clone of the bytes, in every mode               | the fused forward    | xs is rebuilt by stem_s2d_u8 only when fused,
+    #        |                                                   | never writes xs      | not fuse_backward and not split; else x
+    #   s2d  | n/a                                               | n/a                  | xs is the caller's tensor, always version-checked
+    # Where the three-call chain runs (no fused kernel, a hooked stem) the xs it made is saved and x is not.  A recorded
+    # version makes an in-place change between forward and backward raise instead of silently giving a wrong conv1 gradient.
+    if net.keep_s2d and (kind == "u8" or (kind == "f32" and split)):
+        x = x.clone()
+    xs, pool, widx, stem_hw, stem = ops.stem_forward(
+        kind, x, wp, bp, ops.cpad(STEM_WIDTH), dtype=dtype, allow_fused=net.fuse_stem_forward and not stem_hooked,
+        keep_s2d=kind == "f32" and (net.keep_s2d or not net.fuse_backward) and not split)
+    if xs is None and kind == "u8" and not net.fuse_backward and not split:
         xs = ops.stem_s2d_u8(x, dtype)
-        stem = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=True)
-        pool, widx = ops.maxpool_fwd(stem)
-        stem_hw = tuple(stem.shape[1:3])
-        if stem_hooked:                 # the hooked children see what the reference's would (NCHW fp32, 20 channels)
-            if hooks.hooked(net.conv1):
-                from .preprocess import U8Tiles
-                pre = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=False)
-                hooks.fire(net.conv1, U8Tiles(x).float(), hooks.nchw(pre, STEM_WIDTH))
-            stem_v = hooks.nchw(stem, STEM_WIDTH)
-            hooks.fire(net.relu, stem_v, stem_v)
-            hooks.fire(net.maxpool, stem_v, hooks.nchw(pool, STEM_WIDTH))
-    saved = {"xs": xs, "x": x if xs is None else None, "x_src": x if xs is None else None,
+    if stem_hooked:                     # the hooked children see what the reference's would (NCHW fp32, 20 channels)
+        if hooks.hooked(net.conv1):     # pre-activation output: one extra launch, only ever paid under a hook
+            from .preprocess import U8Tiles
+            pre = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=False)
+            shown = x if kind == "f32" else U8Tiles(x).float() if kind == "u8" else hooks.s2d_to_nchw(xs)
+            hooks.fire(net.conv1, shown, hooks.nchw(pre, STEM_WIDTH))
+        stem_v = hooks.nchw(stem, STEM_WIDTH)
+        hooks.fire(net.relu, stem_v, stem_v)            # in place upstream (gbm/model.py:25): input is the output
+        hooks.fire(net.maxpool, stem_v, hooks.nchw(pool, STEM_WIDTH))
+    saved = {"kind": kind, "xs": xs, "x": x if xs is None else None, "x_src": x if (xs is None or kind == "s2d") else None,
              "x_version": x._version, "stem_hw": stem_hw, "widx": widx, "blocks": []}
-    return _encoder_forward_body(net, pool, saved, dtype, hk)
-
-
-def _encoder_forward_from(net, x, dtype, hk, stem_hooked, wp, bp, xs_in):
-    # no space-to-depth copy is kept (keep_s2d False): the fused stem backward rebuilds its tiles from x itself
-    split = dtype == torch.float32 and L.dt_code(dtype, mma=True) == L.MIL_DT_F32S       # bf16x3: never an s2d copy
-    if split and net.keep_s2d and xs_in is None:
-        x = x.clone()                   # this mode has no s2d form: `keep_s2d` keeps a library-owned fp32 copy for the backward instead
-    fused = None
-    if xs_in is None:
-        fused = ops.stem_fwd_fused(x, wp, bp, ops.cpad(STEM_WIDTH), dtype=dtype,
-                                   keep_s2d=(net.keep_s2d or not net.fuse_backward) and not split) if (net.fuse_stem_forward and not stem_hooked) else None
-    else:                               # no fp32 stack exists: the fused stem reads the s2d records themselves
-        fused = ops.stem_fwd_fused_xs(xs_in, wp, bp, ops.cpad(STEM_WIDTH)) if (net.fuse_stem_forward and not stem_hooked) else None
-        if fused is not None:
-            fused = (xs_in,) + fused
-        x = hooks.s2d_to_nchw(xs_in) if stem_hooked else None          # a hooked stem sees the reference's tensor
-    if fused is not None:
-        xs, pool, widx = fused
-        stem_hw = (xs_in.shape[1], xs_in.shape[2]) if xs_in is not None else (x.shape[2] // 2, x.shape[3] // 2)
-    else:
-        xs = xs_in if xs_in is not None else ops.stem_s2d(x, dtype)
-        stem = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=True)
-        pool, widx = ops.maxpool_fwd(stem)
-        stem_hw = tuple(stem.shape[1:3])
-        if stem_hooked:                 # the hooked children see what the reference's would (NCHW fp32, 20 channels)
-            if hooks.hooked(net.conv1):   # pre-activation output: one extra launch, only ever paid under a hook
-                pre = ops.conv(xs, wp, bp, ops.cpad(STEM_WIDTH), ks=4, stride=1, pad=2, lrelu=False)
-                hooks.fire(net.conv1, x, hooks.nchw(pre, STEM_WIDTH))
-            stem_v = hooks.nchw(stem, STEM_WIDTH)
-            hooks.fire(net.relu, stem_v, stem_v)            # in place upstream (gbm/model.py:25): input is the output
-            hooks.fire(net.maxpool, stem_v, hooks.nchw(pool, STEM_WIDTH))
-    # the stem output itself is not kept.  Without an s2d copy the backward rebuilds its tiles from the INPUT tensor: its
-    # version counter is recorded so that an in-place change between forward and backward raises instead of silently
-    # giving a wrong conv1 gradient (keep_s2d=True keeps a library-owned copy where the caller cannot promise that)
-    src = xs_in if xs_in is not None else x             # the caller's tensor the backward re-reads
-    saved = {"xs": xs, "x": x if xs is None else None, "x_src": src if (xs is None or xs_in is not None) else None,
-             "x_version": src._version, "stem_hw": stem_hw, "widx": widx, "blocks": []}
     return _encoder_forward_body(net, pool, saved, dtype, hk)
 
 
@@ -322,8 +272,8 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
             if net.block_position(bi)[1] == 0:
                 stage_in = t
             hooks.refuse(blk, ["conv1", "conv2"] + (["downsample", "downsample.0"] if blk.downsample is not None else []))
-        w1, b1 = net._packed(f"b{bi}.c1", blk.conv1.weight, blk.conv1.bias, L.PACK_FWD, dtype)
-        w2, b2 = net._packed(f"b{bi}.c2", blk.conv2.weight, blk.conv2.bias, L.PACK_FWD, dtype)
+        w1, b1 = net._packed(f"b{bi}.c1", L.PACK_FWD)
+        w2, b2 = net._packed(f"b{bi}.c2", L.PACK_FWD)
         if s == 1 and blk.downsample is None and net.fuse_block_forward:      # whole block in one pass (24/40 channels)
             both = ops.conv_block_fwd(t, w1, b1, w2, b2)
             if both is None:                             # 80 channels on 8x8 maps: both convs on the LDS-resident images
@@ -337,7 +287,7 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
                 continue
         pair = None
         if blk.downsample is not None:
-            wd, _ = net._packed(f"b{bi}.ds", blk.downsample[0].weight, None, L.PACK_FWD, dtype)
+            wd, _ = net._packed(f"b{bi}.ds", L.PACK_FWD)
             if s == 2 and net.fuse_stage_entry:          # both stride-2 convs in one pass over the block input
                 pair = ops.conv_s2_entry(t, w1, b1, wd, ops.cpad(cout))
         if pair is not None:
@@ -353,8 +303,8 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
                 all(b.stride == 1 and b.downsample is None for b in rest)):
             convs = [dict(w=w2, bias=b2, res=short, lrelu=True)]
             for j, b in enumerate(rest):
-                wa, ba = net._packed(f"b{bi + 1 + j}.c1", b.conv1.weight, b.conv1.bias, L.PACK_FWD, dtype)
-                wb, bb = net._packed(f"b{bi + 1 + j}.c2", b.conv2.weight, b.conv2.bias, L.PACK_FWD, dtype)
+                wa, ba = net._packed(f"b{bi + 1 + j}.c1", L.PACK_FWD)
+                wb, bb = net._packed(f"b{bi + 1 + j}.c2", L.PACK_FWD)
                 convs += [dict(w=wa, bias=ba, lrelu=True), dict(w=wb, bias=bb, res=2 * j, lrelu=True)]
             outs = ops.conv_chain(o1, convs)
             if outs is not None:
@@ -434,16 +384,14 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
             assert key is not None, "deferred reductions need one workspace per call site: pass key="
             return ops.conv_wgrad(xin, dzz, cin, cout, workspace=batch.workspace(("w", key), need), **kw)
         if not use_side:
-            if ws[-1] is None or ws[-1].numel() * 4 < need:
-                ws[-1] = torch.empty((need + 3) // 4, dtype=torch.float32, device=xin.device)
+            ws[-1] = ops.workspace_for(ws[-1], need, xin.device)
             return ops.conv_wgrad(xin, dzz, cin, cout, workspace=ws[-1], **kw)
         k = rr[0] % len(sides)
         rr[0] += 1
         side = sides[k]
         side.wait_stream(main)                       # dz was produced on the main stream
         with torch.cuda.stream(side):
-            if ws[k] is None or ws[k].numel() * 4 < need:   # launches on one stream are serialised: one buffer each
-                ws[k] = torch.empty((need + 3) // 4, dtype=torch.float32, device=xin.device)
+            ws[k] = ops.workspace_for(ws[k], need, xin.device)   # launches on one stream are serialised: one buffer each
             out = ops.conv_wgrad(xin, dzz, cin, cout, workspace=ws[k], **kw)
         xin.record_stream(side)
         dzz.record_stream(side)
@@ -465,8 +413,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
             return None
         if batch is not None:
             return ops.conv_bwd_fused(dzz, wd, xin, cin, cout, addend=addend, mask=mask, workspace=batch.workspace(("f", key), need), out=out)
-        if fws is None or fws.numel() * 4 < need:
-            fws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dzz.device)
+        fws = ops.workspace_for(fws, need, dzz.device)
         return ops.conv_bwd_fused(dzz, wd, xin, cin, cout, addend=addend, mask=mask, workspace=fws, out=out)
 
     # weight-gradient producers record their slab reductions; leaving the block runs them all in one launch
@@ -477,8 +424,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         has no such kernel (then the per-block path below runs)."""
         li, j, depth = net.block_position(bi)
         e = bi - depth + 1
-        split_ = dtype == torch.float32 and L.dt_code(dtype, mma=True) == L.MIL_DT_F32S
-        if j != depth - 1 or depth < 2 or depth > 3 or not net.fuse_backward or not (dtype == torch.bfloat16 or split_):
+        if j != depth - 1 or depth < 2 or depth > 3 or not net.fuse_backward or not (dtype == torch.bfloat16 or L.is_split(dtype)):
             return None
         ent = blocks[e]
         if ent.stride != 2 or ent.downsample is None or any(b.stride != 1 or b.downsample is not None for b in blocks[e + 1:bi + 1]):
@@ -490,13 +436,13 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         convs, src = [], None                   # src: chain output that is the gradient entering the current block (None: dz_out)
         for k in range(bi, e, -1):
             xin_k, o1_k, _ = saved["blocks"][k]
-            w2d_k, _ = net._packed(f"b{k}.c2", blocks[k].conv2.weight, None, L.PACK_DGRAD, dtype)
-            w1d_k, _ = net._packed(f"b{k}.c1", blocks[k].conv1.weight, None, L.PACK_DGRAD, dtype)
+            w2d_k, _ = net._packed(f"b{k}.c2", L.PACK_DGRAD)
+            w1d_k, _ = net._packed(f"b{k}.c1", L.PACK_DGRAD)
             convs.append(dict(w=w2d_k, act=o1_k))                                            # dmid_k = lrelu'(o1) * conv2^T(dz_k)
             convs.append(dict(w=w1d_k, res=dz_out if src is None else src, act=xin_k))       # dz_{k-1} = lrelu'(x) * (conv1^T(dmid_k) + dz_k)
             src = len(convs) - 1
         _xin_e, o1_e, _ = saved["blocks"][e]
-        w2d_e, _ = net._packed(f"b{e}.c2", ent.conv2.weight, None, L.PACK_DGRAD, dtype)
+        w2d_e, _ = net._packed(f"b{e}.c2", L.PACK_DGRAD)
         convs.append(dict(w=w2d_e, act=o1_e))                                                # the entry block's dz1
         outs = ops.conv_chain(dz_out, convs)
         if outs is None:
@@ -526,7 +472,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                     pre.update(chain)
             if pre.get(bi) == "done":
                 continue
-            w2d, _ = net._packed(f"b{bi}.c2", blk.conv2.weight, None, L.PACK_DGRAD, dtype)
+            w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
             if bi in pre:                               # stage entry behind a chain: dz of its output and dz1 are there, dW2/db2 too
                 dz, dz1 = pre[bi]
                 fused = "chain"
@@ -543,7 +489,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                 if s == 1 and blk.downsample is None and net.fuse_backward:
                     # 80 channels on 8x8 maps: the block's two transposed convs on the LDS-resident images, one launch:
                     # dz1 = lrelu'(o1) * conv2^T(dz),  dz(prev) = lrelu'(x) * (conv1^T(dz1) + dz)
-                    w1d_, _ = net._packed(f"b{bi}.c1", blk.conv1.weight, None, L.PACK_DGRAD, dtype)
+                    w1d_, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
                     chain = ops.conv_pair(dz, w2d, None, w1d_, None, actA=o1, resB=dz, actB=xin if bi > 0 else None)
                     if chain is not None:
                         dz1, dz_prev = chain
@@ -551,7 +497,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                         dz = dz_prev
                         continue
                 dz1 = ops.conv(dz, w2d, None, ops.cpad(cout), ks=3, stride=1, pad=1, act=o1)
-            w1d, _ = net._packed(f"b{bi}.c1", blk.conv1.weight, None, L.PACK_DGRAD, dtype)
+            w1d, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
             mask = xin if bi > 0 else None          # block 0 reads the max-pool output (no activation in between)
             if s == 1 and blk.downsample is None and net.fuse_backward:
                 fused = fused_bwd(dz1, w1d, xin, cin, cout, dz, mask is not None, gout(blk.conv1.weight, blk.conv1.bias), key=(bi, 1))
@@ -577,12 +523,11 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                     grads[f"b{bi}.ds"] = wgrad(xin, dz, cin, cout, key=(bi, 0), ks=1, stride=s, pad=0, want_bias=False,
                                                out=gout(blk.downsample[0].weight, None))
                 if s == 2 and net.fuse_backward:     # both transposed convs + the mask in one pass over the compact dz maps
-                    ws2, _ = net._packed(f"b{bi}.c1", blk.conv1.weight, blk.downsample[0].weight, L.PACK_DGRAD_S2, dtype)
+                    ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
                     # the gradient chain of the first (20-channel) stage below this point runs on kernels that read the
                     # dense layout, when every one of them exists for these shapes: the fused backward and the fused stem backward
                     dense_cx = None
-                    split = dtype == torch.float32 and L.dt_code(dtype, mma=True) == L.MIL_DT_F32S
-                    if (net.dense_grads and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or split) and bi > 0 and
+                    if (net.dense_grads and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or L.is_split(dtype)) and bi > 0 and
                             all(b.stride == 1 and b.downsample is None for b in blocks[:bi]) and
                             ops.bwd_fused_workspace_bytes(xin.shape[0], xin.shape[1], xin.shape[2], cin, cin, 3, 1, dtype, True) is not None and
                             ops.stem_bwd_dense_ok(saved["x"] if saved["xs"] is None else saved["xs"], dtype)):
@@ -591,7 +536,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                     if fused is not None:
                         dz = fused
                         continue
-                wdd, _ = net._packed(f"b{bi}.ds", blk.downsample[0].weight, None, L.PACK_DGRAD, dtype)
+                wdd, _ = net._packed(f"b{bi}.ds", L.PACK_DGRAD)
                 if s == 2:
                     addend = ops.conv(dz, wdd, None, ops.cpad(cin), ks=1, stride=1, pad=0, zero_insert=True,
                                       out_hw=xin.shape[1:3])
@@ -607,12 +552,8 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         fused_stem = None
         if net.fuse_backward:               # pool backward + lrelu backward + stem wgrad in one pass (bf16 path)
             stem_ws = (lambda nb: batch.workspace(("s", 0), nb)) if batch is not None else None
-            if saved["xs"] is None:
-                stem_bwd = ops.stem_bwd_fused_u8 if saved["x"].dtype == torch.uint8 else ops.stem_bwd_fused_nchw
-                fused_stem = stem_bwd(saved["x"], dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias), ws_alloc=stem_ws)
-            else:
-                fused_stem = ops.stem_bwd_fused(saved["xs"], dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias),
-                                                ws_alloc=stem_ws)
+            src, src_kind = (saved["x"], saved["kind"]) if saved["xs"] is None else (saved["xs"], "s2d")
+            fused_stem = ops.stem_backward(src_kind, src, dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias), ws_alloc=stem_ws)
         if fused_stem is not None:
             grads["stem"] = fused_stem
         elif is_dense(dz, STEM_WIDTH):
@@ -620,7 +561,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
         else:
             dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
             if saved["xs"] is None:
-                saved["xs"] = (ops.stem_s2d_u8 if saved["x"].dtype == torch.uint8 else ops.stem_s2d)(saved["x"], dz.dtype)
+                saved["xs"] = ops.stem_to_s2d(saved["kind"], saved["x"], dz.dtype)
             grads["stem"] = wgrad(saved["xs"], dstem, 3, STEM_WIDTH, key=("stem", 0), ks=4, stride=1, pad=2, stem=True,
                                   out=gout(net.conv1.weight, net.conv1.bias))
 

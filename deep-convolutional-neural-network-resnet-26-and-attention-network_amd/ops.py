@@ -1,6 +1,7 @@
 """Thin tensor-level wrappers over the C ABI (include/mil_hip.h).  Each wrapper checks shapes on the
 host (a wrong extent in a hand-written kernel is a GPU fault, not an exception), allocates outputs with
 torch (plumbing) and enqueues the HIP kernel on torch's current stream."""
+import collections
 import ctypes
 
 import torch
@@ -57,9 +58,7 @@ class ReduceBatch:
                 raise RuntimeError(f"slab workspace {key!r} handed out twice inside one deferred-reduction block: the second "
                                    "producer would overwrite slabs the batched reduction has not read yet")
             self.handed.add(key)
-        t = self.ws.get(key)
-        if t is None or t.numel() * 4 < nbytes:
-            t = self.ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        t = self.ws[key] = workspace_for(self.ws.get(key), nbytes, self.device)
         return t
 
     def __enter__(self):
@@ -95,29 +94,36 @@ def _need(t, shape, dtype, name):
         raise ValueError(f"{name}: expected {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
 
 
-def stem_s2d(x, dtype):
-    """[n,3,H,W] fp32 NCHW -> [n,ceil(H/2),ceil(W/2),16] NHWC space-to-depth of `dtype`."""
-    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError(f"expected a CUDA fp32 [N,3,H,W] tile stack, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    x = x.contiguous()
-    n, _, h, w = x.shape
-    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 16), dtype=dtype, device=x.device)
-    L.check(L.lib().mil_stem_s2d(x.data_ptr(), out.data_ptr(), n, h, w, L.dt_code(dtype), L.stream_ptr()), "mil_stem_s2d")
-    return out
+def workspace_for(workspace, need, device):
+    """`workspace` when it holds `need` bytes, else a fresh fp32 buffer that does."""
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+    return workspace
 
 
-def _need_u8_tiles(x):
-    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8 or not x.is_cuda or not x.is_contiguous():
-        raise ValueError(f"expected a contiguous CUDA uint8 [N,3,H,W] tile stack, got {tuple(x.shape)} {x.dtype} on {x.device}")
+def _grad_out(out, specs, device):
+    """(gradient tensors, accumulate flag) for `specs` = (shape, name) per tensor: fresh fp32 tensors the kernel overwrites
+    (out None), or the caller's own tensors, checked, which it accumulates into (p.grad views).  A spec of None stands for
+    a tensor the caller does not want: None when allocating."""
+    if out is None:
+        return [None if sp is None else torch.empty(sp[0], dtype=torch.float32, device=device) for sp in specs], 0
+    for t, (shape, name) in zip(out, specs):
+        _need(t, shape, torch.float32, name)
+    return out, 1
 
 
-def stem_s2d_u8(x, dtype):
-    """stem_s2d from uint8 tiles [n,3,H,W] (the uint8 feed, see mil_stem_s2d_u8): bit for bit stem_s2d of the decoded tensor."""
-    _need_u8_tiles(x)
-    n, _, h, w = x.shape
-    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 16), dtype=dtype, device=x.device)
-    L.check(L.lib().mil_stem_s2d_u8(x.data_ptr(), out.data_ptr(), n, h, w, L.dt_code(dtype), L.stream_ptr()), "mil_stem_s2d_u8")
-    return out
+def _launch(symbol, label, *args, missing_ok=False):
+    """Enqueue `symbol(*args)`, bracketed with events when TIMER wants `label` (None: a launch that is never timed).  False
+    when the library has no kernel for these arguments (rc 2) and the caller has another path (`missing_ok`) — no end event
+    is recorded then; every other failure raises."""
+    end = TIMER.bracket(label) if TIMER and label is not None else None
+    rc = getattr(L.lib(), symbol)(*args)
+    if rc == 2 and missing_ok:
+        return False
+    L.check(rc, symbol)
+    if end is not None:
+        end.record()
+    return True
 
 
 def pack_weights(w, bias, mode, dtype):
@@ -157,13 +163,10 @@ def conv(x, wpack, bias_pad, cout_p, *, ks, stride, pad, out_hw=None, res=None, 
     _need(x, x.shape, x.dtype, "x")
     _need(res, y.shape, x.dtype, "res")
     _need(act, y.shape, x.dtype, "act")
-    end = TIMER.bracket(("conv", cin_p, cout_p, ks, stride, bool(zero_insert), n, ho, wo)) if TIMER else None
-    L.check(L.lib().mil_conv_igemm(x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), L.ptr(res), L.ptr(act), y.data_ptr(),
-                                   n, h, w, cin_p, ho, wo, cout_p, ks, 1 if zero_insert else stride, pad,
-                                   1 if zero_insert else 0, 1 if lrelu else 0, slope, L.dt_code(x.dtype, mma=True), L.stream_ptr()),
-            "mil_conv_igemm")
-    if end is not None:
-        end.record()
+    _launch("mil_conv_igemm", ("conv", cin_p, cout_p, ks, stride, bool(zero_insert), n, ho, wo),
+            x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), L.ptr(res), L.ptr(act), y.data_ptr(),
+            n, h, w, cin_p, ho, wo, cout_p, ks, 1 if zero_insert else stride, pad,
+            1 if zero_insert else 0, 1 if lrelu else 0, slope, L.dt_code(x.dtype, mma=True), L.stream_ptr())
     return y
 
 
@@ -180,24 +183,14 @@ def conv_wgrad(x, dz, cin, cout, *, ks, stride, pad, stem=False, want_bias=True,
     _, ho, wo, cout_p = dz.shape
     _need(dz, (n, ho, wo, cpad(cout)), x.dtype, "dz")
     _need(x, (n, h, w, 16 if stem else cpad(cin)), x.dtype, "x")
-    need = wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, ks, stride, pad, stem, x.dtype)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    workspace = workspace_for(workspace, wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, ks, stride, pad, stem, x.dtype), x.device)
     kk = 7 if stem else ks
-    if out is None:
-        dw = torch.empty((cout, cin, kk, kk), dtype=torch.float32, device=x.device)
-        db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
-    else:                         # accumulate straight into caller-owned gradient tensors (p.grad views)
-        dw, db = out
-        _need(dw, (cout, cin, kk, kk), torch.float32, "dw")
-        _need(db, (cout,), torch.float32, "db")
-    end = TIMER.bracket(("wgrad", cin_p, cout_p, ks, stride, n, ho, wo)) if TIMER else None
-    L.check(L.lib().mil_conv_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), L.ptr(db), workspace.data_ptr(),
-                                   workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo, cout, ks, stride,
-                                   pad, 1 if stem else 0, 0 if out is None else 1, L.dt_code(x.dtype, mma=True), L.stream_ptr()),
-            "mil_conv_wgrad")
-    if end is not None:
-        end.record()
+    (dw, db), accumulate = _grad_out(out, (((cout, cin, kk, kk), "dw"), ((cout,), "db") if want_bias or out is not None else None),
+                                     x.device)
+    _launch("mil_conv_wgrad", ("wgrad", cin_p, cout_p, ks, stride, n, ho, wo),
+            x.data_ptr(), dz.data_ptr(), dw.data_ptr(), L.ptr(db), workspace.data_ptr(),
+            workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo, cout, ks, stride,
+            pad, 1 if stem else 0, accumulate, L.dt_code(x.dtype, mma=True), L.stream_ptr())
     return dw, db
 
 
@@ -224,24 +217,14 @@ def conv_bwd_fused(dz, wpack_dgrad, x, cin, cout, *, addend=None, mask=True, ks=
     _need(dz, (n, h, w, cout if dense else cpad(cout)), dz.dtype, "dz")
     _need(x, (n, h, w, cpad(cin)), dz.dtype, "x")
     _need(addend, (n, h, w, cin if dense else cpad(cin)), dz.dtype, "addend")
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dz.device)
+    workspace = workspace_for(workspace, need, dz.device)
     dx = torch.empty((n, h, w, cin), dtype=dz.dtype, device=dz.device) if dense else torch.empty_like(x)
-    if out is None:
-        dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=dz.device)
-        db = torch.empty(cout, dtype=torch.float32, device=dz.device)
-    else:
-        dw, db = out
-        _need(dw, (cout, cin, ks, ks), torch.float32, "dw")
-        _need(db, (cout,), torch.float32, "db")
-    end = TIMER.bracket(("bwd_fused", cpad(cout), cpad(cin), ks, 1, False, n, h, w, addend is not None)) if TIMER else None
-    L.check(L.lib().mil_conv_bwd_fused(dz.data_ptr(), wpack_dgrad.data_ptr(), x.data_ptr(), L.ptr(addend), dx.data_ptr(),
-                                       dw.data_ptr(), db.data_ptr(), workspace.data_ptr(),
-                                       workspace.numel() * workspace.element_size(), n, h, w, cout, cin, ks, pad,
-                                       1 if mask else 0, 0 if out is None else 1, slope, L.dt_code(dz.dtype, dense, mma=True), L.stream_ptr()),
-            "mil_conv_bwd_fused")
-    if end is not None:
-        end.record()
+    (dw, db), accumulate = _grad_out(out, (((cout, cin, ks, ks), "dw"), ((cout,), "db")), dz.device)
+    _launch("mil_conv_bwd_fused", ("bwd_fused", cpad(cout), cpad(cin), ks, 1, False, n, h, w, addend is not None),
+            dz.data_ptr(), wpack_dgrad.data_ptr(), x.data_ptr(), L.ptr(addend), dx.data_ptr(),
+            dw.data_ptr(), db.data_ptr(), workspace.data_ptr(),
+            workspace.numel() * workspace.element_size(), n, h, w, cout, cin, ks, pad,
+            1 if mask else 0, accumulate, slope, L.dt_code(dz.dtype, dense, mma=True), L.stream_ptr())
     return dx, dw, db
 
 
@@ -287,14 +270,10 @@ def conv_block_fwd(x, wpack1, bias1, wpack2, bias2, *, slope=LEAK):
     _need(x, x.shape, x.dtype, "x")
     o1 = torch.empty_like(x)
     y = torch.empty_like(x)
-    end = TIMER.bracket(("block_fwd", cp, n, h, w)) if TIMER else None
-    rc = L.lib().mil_conv_block_fwd(x.data_ptr(), wpack1.data_ptr(), L.ptr(bias1), wpack2.data_ptr(), L.ptr(bias2),
-                                    o1.data_ptr(), y.data_ptr(), n, h, w, cp, slope, code, L.stream_ptr())
-    if rc == 2:
+    if not _launch("mil_conv_block_fwd", ("block_fwd", cp, n, h, w),
+                   x.data_ptr(), wpack1.data_ptr(), L.ptr(bias1), wpack2.data_ptr(), L.ptr(bias2),
+                   o1.data_ptr(), y.data_ptr(), n, h, w, cp, slope, code, L.stream_ptr(), missing_ok=True):
         return None
-    L.check(rc, "mil_conv_block_fwd")
-    if end is not None:
-        end.record()
     return o1, y
 
 
@@ -332,13 +311,9 @@ def conv_chain(x, convs, *, slope=LEAK):
         arr[k].res, arr[k].act = L.ptr(ops_["res"]), L.ptr(ops_["act"])
         arr[k].out = outs[k].data_ptr()
         arr[k].lrelu = 1 if c.get("lrelu") else 0
-    end = TIMER.bracket(("chain", cp, n, h, w, len(convs))) if TIMER else None
-    rc = L.lib().mil_conv_chain(x.data_ptr(), ctypes.addressof(arr), len(convs), n, h, w, cp, slope, code, L.stream_ptr())
-    if rc == 2:
+    if not _launch("mil_conv_chain", ("chain", cp, n, h, w, len(convs)),
+                   x.data_ptr(), ctypes.addressof(arr), len(convs), n, h, w, cp, slope, code, L.stream_ptr(), missing_ok=True):
         return None
-    L.check(rc, "mil_conv_chain")
-    if end is not None:
-        end.record()
     return outs
 
 
@@ -361,14 +336,10 @@ def conv_s2_entry(x, wpack3, bias_pad, wpack1, cout_p, *, slope=LEAK):
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     y1 = torch.empty((n, ho, wo, cout_p), dtype=x.dtype, device=x.device)
     y2 = torch.empty_like(y1)
-    end = TIMER.bracket(("s2_entry", cin_p, cout_p, n, h, w)) if TIMER else None
-    rc = L.lib().mil_conv_s2_entry(x.data_ptr(), wpack3.data_ptr(), L.ptr(bias_pad), wpack1.data_ptr(), y1.data_ptr(),
-                                   y2.data_ptr(), n, h, w, cin_p, cout_p, slope, code, L.stream_ptr())
-    if rc == 2:
+    if not _launch("mil_conv_s2_entry", ("s2_entry", cin_p, cout_p, n, h, w),
+                   x.data_ptr(), wpack3.data_ptr(), L.ptr(bias_pad), wpack1.data_ptr(), y1.data_ptr(),
+                   y2.data_ptr(), n, h, w, cin_p, cout_p, slope, code, L.stream_ptr(), missing_ok=True):
         return None
-    L.check(rc, "mil_conv_s2_entry")
-    if end is not None:
-        end.record()
     return y1, y2
 
 
@@ -388,23 +359,13 @@ def conv_wgrad_pair(x, dz1, dz2, cin, cout, *, workspace=None, out=None):
     if rc == 2:
         return None
     L.check(rc, "mil_conv_wgrad_pair_workspace")
-    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
-        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
-    if out is None:
-        dw3 = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-        db3 = torch.empty(cout, dtype=torch.float32, device=x.device)
-        dw1 = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=x.device)
-    else:
-        dw3, db3, dw1 = out
-        _need(dw3, (cout, cin, 3, 3), torch.float32, "dw3")
-        _need(db3, (cout,), torch.float32, "db3")
-        _need(dw1, (cout, cin, 1, 1), torch.float32, "dw1")
-    rc = L.lib().mil_conv_wgrad_pair(x.data_ptr(), dz1.data_ptr(), dz2.data_ptr(), dw3.data_ptr(), db3.data_ptr(), dw1.data_ptr(),
-                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo,
-                                     cout, 0 if out is None else 1, code, L.stream_ptr())
-    if rc == 2:
+    workspace = workspace_for(workspace, need.value, x.device)
+    (dw3, db3, dw1), accumulate = _grad_out(out, (((cout, cin, 3, 3), "dw3"), ((cout,), "db3"), ((cout, cin, 1, 1), "dw1")), x.device)
+    if not _launch("mil_conv_wgrad_pair", None,
+                   x.data_ptr(), dz1.data_ptr(), dz2.data_ptr(), dw3.data_ptr(), db3.data_ptr(), dw1.data_ptr(),
+                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo,
+                   cout, accumulate, code, L.stream_ptr(), missing_ok=True):
         return None
-    L.check(rc, "mil_conv_wgrad_pair")
     return dw3, db3, dw1, workspace
 
 
@@ -421,231 +382,238 @@ def conv_dgrad_s2(dz1, dz2, wpack, cx_p, out_hw, *, act=None, slope=LEAK, dense_
     _need(dz2, dz1.shape, dz1.dtype, "dz2")
     y = torch.empty((n, hh, ww, dense_cx if dense else cx_p), dtype=dz1.dtype, device=dz1.device)
     _need(act, (n, hh, ww, cx_p), dz1.dtype, "act")
-    end = TIMER.bracket(("dgrad_s2", cz_p, cx_p, n, hh, ww)) if TIMER else None
-    rc = L.lib().mil_conv_dgrad_s2(dz1.data_ptr(), L.ptr(dz2), wpack.data_ptr(), L.ptr(act), y.data_ptr(), n, h, w, cz_p,
-                                   hh, ww, cx_p, slope, L.dt_code(dz1.dtype, dense, mma=True), L.stream_ptr())
+    if not _launch("mil_conv_dgrad_s2", ("dgrad_s2", cz_p, cx_p, n, hh, ww),
+                   dz1.data_ptr(), L.ptr(dz2), wpack.data_ptr(), L.ptr(act), y.data_ptr(), n, h, w, cz_p,
+                   hh, ww, cx_p, slope, L.dt_code(dz1.dtype, dense, mma=True), L.stream_ptr(), missing_ok=True):
+        return None
+    return y
+
+
+# ---- the stem: one description per feed ---------------------------------------------------------------------
+# The tiles reach the stem as fp32 [n,3,H,W] ("f32"), as the uint8 images they are ("u8", preprocess.U8Tiles) or as the bf16
+# space-to-depth tensor [n,H/2,W/2,16] ("s2d", preprocess.S2dTiles).  The kernels are one template family
+# (csrc/stem_fused.hip); a feed is what differs on the host: which tensor is acceptable (`ok`; `strict`: it must be
+# contiguous already, else a contiguous copy is made; `expected`: the ValueError's text), the pointer alignment the fused
+# kernels' vector loads need, the layout its extents are read from (`planar`: [n,3,H,W]), the C symbols and the timer labels.
+StemFeed = collections.namedtuple("StemFeed", "planar ok strict expected align fwd bwd bwd_ws s2d fwd_label bwd_label")
+
+
+def _planar_tiles(dtype):
+    return lambda x: x.dim() == 4 and x.shape[1] == 3 and x.dtype == dtype and x.is_cuda
+
+
+STEM_FEEDS = {
+    "f32": StemFeed(planar=True, ok=_planar_tiles(torch.float32), strict=False, align=16,
+                    expected="expected a CUDA fp32 [N,3,H,W] tile stack, got {shape} {dtype} on {device}",
+                    fwd="mil_stem_fwd_fused", bwd="mil_stem_bwd_fused_nchw", bwd_ws="mil_stem_bwd_fused_nchw_workspace",
+                    s2d="mil_stem_s2d", fwd_label="stem_fwd", bwd_label="stem_bwd"),
+    "u8": StemFeed(planar=True, ok=_planar_tiles(torch.uint8), strict=True, align=4,
+                   expected="expected a contiguous CUDA uint8 [N,3,H,W] tile stack, got {shape} {dtype} on {device}",
+                   fwd="mil_stem_fwd_fused_u8", bwd="mil_stem_bwd_fused_u8", bwd_ws="mil_stem_bwd_fused_u8_workspace",
+                   s2d="mil_stem_s2d_u8", fwd_label="stem_fwd_u8", bwd_label="stem_bwd_u8"),
+    "s2d": StemFeed(planar=False, ok=lambda x: x.dim() == 4 and x.shape[3] == 16 and x.dtype == torch.bfloat16 and x.is_cuda,
+                    strict=True, align=16, expected="expected a contiguous CUDA bf16 [N,H/2,W/2,16] tensor, got {shape} {dtype}",
+                    fwd="mil_stem_fwd_fused_xs", bwd="mil_stem_bwd_fused", bwd_ws="mil_stem_bwd_fused_workspace",
+                    s2d=None, fwd_label="stem_fwd_xs", bwd_label="stem_bwd_xs"),
+}
+
+
+def stem_feed_kind(x, mode):
+    """Which of the three feeds the tensor `x` is, "f32", "u8" or "s2d" (by its dtype); raises for a feed that the compute
+    mode (or its storage dtype) `mode` does not take."""
+    if x.dtype == torch.bfloat16:       # the bf16 space-to-depth tensor [T,H/2,W/2,16] (preprocess.S2dTiles)
+        if x.dim() != 4 or x.shape[3] != 16:
+            raise ValueError(f"a bf16 input must be the space-to-depth tensor [T,H/2,W/2,16], got {tuple(x.shape)}")
+        if mode != torch.bfloat16:
+            raise ValueError("space-to-depth bf16 tiles feed the bf16 compute mode only (the fp32 modes take fp32 [T,3,H,W] tiles)")
+        return "s2d"
+    if x.dtype == torch.uint8:          # the uint8 images themselves (preprocess.U8Tiles): every compute mode
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"a uint8 input must be the planar tile stack [T,3,H,W], got {tuple(x.shape)}")
+        return "u8"
+    return "f32"
+
+
+def _feed_tensor(f, x):
+    """The tensor the kernels of feed `f` read: `x`, checked and contiguous."""
+    if not f.ok(x) or (f.strict and not x.is_contiguous()):
+        raise ValueError(f.expected.format(shape=tuple(x.shape), dtype=x.dtype, device=x.device))
+    return x.contiguous()
+
+
+def _stem_extents(f, x):
+    """(n, (H, W) of the tiles, (h2, w2) of their space-to-depth form, the extents the feed's kernels are given)."""
+    if f.planar:
+        n, _, h, w = x.shape
+        return n, (h, w), (h // 2, w // 2), (h, w)
+    n, h2, w2, _ = x.shape
+    return n, (2 * h2, 2 * w2), (h2, w2), (h2, w2)
+
+
+def _stem_s2d(kind, x, dtype):
+    f = STEM_FEEDS[kind]
+    x = _feed_tensor(f, x)
+    n, _, h, w = x.shape
+    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 16), dtype=dtype, device=x.device)
+    _launch(f.s2d, None, x.data_ptr(), out.data_ptr(), n, h, w, L.dt_code(dtype), L.stream_ptr())
+    return out
+
+
+def _stem_fwd(kind, x, wpack, bias_pad, cout_p, slope, dtype, keep_s2d):
+    """(xs, pool, widx) of the whole stem in one pass over the tiles of feed `kind` (xs: the space-to-depth copy the f32 feed
+    writes under keep_s2d, else None), or None when the shape / mode has no fused kernel.  bf16 with 24 or 64 channels; split
+    precision: the 20-channel stem only, fp32 pooled map, never an s2d copy."""
+    f = STEM_FEEDS[kind]
+    x = _feed_tensor(f, x)
+    code = L.dt_code(dtype, mma=True)
+    if code == L.MIL_DT_F32S:
+        if keep_s2d or cout_p != 24:
+            return None
+    elif dtype != torch.bfloat16:
+        return None
+    n, (h, w), (h2, w2), ext = _stem_extents(f, x)
+    if (f.planar and (h % 2 or w % 4)) or cout_p not in (24, 64) or x.data_ptr() % f.align:
+        return None
+    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+    xs = torch.empty((n, h2, w2, 16), dtype=dtype, device=x.device) if keep_s2d else None
+    pool = torch.empty((n, hp, wp, cout_p), dtype=dtype, device=x.device)
+    widx = torch.empty((n, hp, wp, cout_p), dtype=torch.uint8, device=x.device)
+    dst = (L.ptr(xs), pool.data_ptr(), widx.data_ptr()) if kind == "f32" else (pool.data_ptr(), widx.data_ptr())
+    if not _launch(f.fwd, (f.fwd_label, cout_p, n, h, w), x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), *dst, n, *ext,
+                   cout_p, slope, code, L.stream_ptr(), missing_ok=True):
+        return None
+    return xs, pool, widx
+
+
+def _stem_bwd(kind, x, g_pool, widx, workspace, out, slope, ws_alloc):
+    """(dW [20,3,7,7], db [20]) of the stem from the pooled-output gradient in one pass over the saved input of feed `kind`, or
+    None when the input is not that feed's or the shape / dtype / alignment has no fused kernel.  A 20-channel g_pool is the
+    dense gradient layout (MIL_DT_BF16_DGRAD / MIL_DT_F32S_DGRAD)."""
+    f = STEM_FEEDS[kind]
+    if not f.ok(x) or not x.is_contiguous() or x.data_ptr() % f.align:
+        return None
+    n, (h, w), (h2, w2), ext = _stem_extents(f, x)
+    dense = g_pool.shape[-1] == 20
+    gdt = g_pool.dtype if f.planar else x.dtype
+    code = L.dt_code(gdt, dense, mma=True)
+    need = ctypes.c_size_t(0)
+    rc = getattr(L.lib(), f.bwd_ws)(ctypes.byref(need), n, *ext, code)
     if rc == 2:
         return None
-    L.check(rc, "mil_conv_dgrad_s2")
-    if end is not None:
-        end.record()
-    return y
+    L.check(rc, f.bwd_ws)
+    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+    _need(g_pool, (n, hp, wp, 20 if dense else 24), gdt, "g_pool")
+    _need(widx, (n, hp, wp, 24), torch.uint8, "widx")
+    if ws_alloc is not None:                 # deferred reductions: the slab buffer must outlive this call
+        workspace = ws_alloc(need.value)
+    workspace = workspace_for(workspace, need.value, x.device)
+    (dw, db), accumulate = _grad_out(out, (((20, 3, 7, 7), "dw"), ((20,), "db")), x.device)
+    if not _launch(f.bwd, (f.bwd_label, n, h, w), x.data_ptr(), g_pool.data_ptr(), widx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, *ext, slope, accumulate, code,
+                   L.stream_ptr(), missing_ok=True):
+        return None
+    return dw, db
+
+
+# The public names: what bench.py, tools/ and the tests call (and spy on).  The encoders reach the kernels through these
+# module attributes too (`stem_forward`, `stem_backward`, `stem_to_s2d` below look them up at call time).
+def stem_s2d(x, dtype):
+    """[n,3,H,W] fp32 NCHW -> [n,ceil(H/2),ceil(W/2),16] NHWC space-to-depth of `dtype`."""
+    return _stem_s2d("f32", x, dtype)
+
+
+def stem_s2d_u8(x, dtype):
+    """stem_s2d from uint8 tiles [n,3,H,W] (the uint8 feed, see mil_stem_s2d_u8): bit for bit stem_s2d of the decoded tensor."""
+    return _stem_s2d("u8", x, dtype)
 
 
 def stem_fwd_fused(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat16, keep_s2d=True):
     """(xs, pool, widx) of the whole stem in one pass over the fp32 NCHW tiles (see mil_stem_fwd_fused), or None when
     the shape/dtype has no fused kernel (the caller then runs stem_s2d / conv / maxpool_fwd).  keep_s2d=False: no
     space-to-depth copy is written (xs is None); the backward then reads x itself (stem_bwd_fused_nchw)."""
-    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError(f"expected a CUDA fp32 [N,3,H,W] tile stack, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    x = x.contiguous()
-    n, c, h, w = x.shape
-    code = L.dt_code(dtype, mma=True)
-    if code == L.MIL_DT_F32S:               # split precision: fp32 pooled map, never an s2d copy (the backward reads x)
-        if keep_s2d or cout_p != 24:
-            return None
-    elif dtype != torch.bfloat16:
-        return None
-    if h % 2 or w % 4 or cout_p not in (24, 64) or x.data_ptr() % 16:
-        return None
-    h2, w2 = h // 2, w // 2
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    xs = torch.empty((n, h2, w2, 16), dtype=dtype, device=x.device) if keep_s2d else None
-    pool = torch.empty((n, hp, wp, cout_p), dtype=dtype, device=x.device)
-    widx = torch.empty((n, hp, wp, cout_p), dtype=torch.uint8, device=x.device)
-    end = TIMER.bracket(("stem_fwd", cout_p, n, h, w)) if TIMER else None
-    rc = L.lib().mil_stem_fwd_fused(x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), L.ptr(xs), pool.data_ptr(),
-                                    widx.data_ptr(), n, h, w, cout_p, slope, code, L.stream_ptr())
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_fwd_fused")
-    if end is not None:
-        end.record()
-    return xs, pool, widx
+    return _stem_fwd("f32", x, wpack, bias_pad, cout_p, slope, dtype, keep_s2d)
 
 
 def stem_fwd_fused_u8(x, wpack, bias_pad, cout_p, *, slope=LEAK, dtype=torch.bfloat16):
     """(pool, widx) of the whole stem in one pass over uint8 tiles x [n,3,H,W] (see mil_stem_fwd_fused_u8): bit for bit
-    stem_fwd_fused(decoded tiles, keep_s2d=False).  None when the shape / dtype has no fused kernel (the caller then runs
-    stem_s2d_u8 / conv / maxpool_fwd).  cout_p 24 (the narrow encoder: bf16 or split precision) or 64 (alt_resnet: bf16 only)."""
-    _need_u8_tiles(x)
-    n, c, h, w = x.shape
-    code = L.dt_code(dtype, mma=True)
-    if code == L.MIL_DT_F32S:               # split precision: the 20-channel stem only, as stem_fwd_fused
-        if cout_p != 24:
-            return None
-    elif dtype != torch.bfloat16:
-        return None
-    if h % 2 or w % 4 or cout_p not in (24, 64) or x.data_ptr() % 4:
-        return None
-    h2, w2 = h // 2, w // 2
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    pool = torch.empty((n, hp, wp, cout_p), dtype=dtype, device=x.device)
-    widx = torch.empty((n, hp, wp, cout_p), dtype=torch.uint8, device=x.device)
-    end = TIMER.bracket(("stem_fwd_u8", cout_p, n, h, w)) if TIMER else None
-    rc = L.lib().mil_stem_fwd_fused_u8(x.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), pool.data_ptr(), widx.data_ptr(), n, h, w,
-                                       cout_p, slope, code, L.stream_ptr())
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_fwd_fused_u8")
-    if end is not None:
-        end.record()
-    return pool, widx
+    stem_fwd_fused(decoded tiles, keep_s2d=False).  cout_p 24 (the narrow encoder: bf16 or split precision) or 64
+    (alt_resnet: bf16 only)."""
+    fused = _stem_fwd("u8", x, wpack, bias_pad, cout_p, slope, dtype, False)
+    return None if fused is None else fused[1:]
 
 
 def stem_fwd_fused_xs(xs, wpack, bias_pad, cout_p, *, slope=LEAK):
     """(pool, widx) of the whole stem in one pass over the bf16 space-to-depth tiles xs [n,H2,W2,16] (see
     mil_stem_fwd_fused_xs), or None when the shape has no fused kernel."""
-    if xs.dim() != 4 or xs.shape[3] != 16 or xs.dtype != torch.bfloat16 or not xs.is_cuda or not xs.is_contiguous():
-        raise ValueError(f"expected a contiguous CUDA bf16 [N,H/2,W/2,16] tensor, got {tuple(xs.shape)} {xs.dtype}")
-    n, h2, w2, _ = xs.shape
-    if cout_p not in (24, 64) or xs.data_ptr() % 16:
-        return None
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    pool = torch.empty((n, hp, wp, cout_p), dtype=torch.bfloat16, device=xs.device)
-    widx = torch.empty((n, hp, wp, cout_p), dtype=torch.uint8, device=xs.device)
-    end = TIMER.bracket(("stem_fwd_xs", cout_p, n, 2 * h2, 2 * w2)) if TIMER else None
-    rc = L.lib().mil_stem_fwd_fused_xs(xs.data_ptr(), wpack.data_ptr(), L.ptr(bias_pad), pool.data_ptr(), widx.data_ptr(), n, h2, w2,
-                                       cout_p, slope, L.MIL_DT_BF16, L.stream_ptr())
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_fwd_fused_xs")
-    if end is not None:
-        end.record()
-    return pool, widx
+    fused = _stem_fwd("s2d", xs, wpack, bias_pad, cout_p, slope, torch.bfloat16, False)
+    return None if fused is None else fused[1:]
 
 
 def stem_bwd_fused(xs, g_pool, widx, *, workspace=None, out=None, slope=LEAK, ws_alloc=None):
-    """(dW [20,3,7,7], db [20]) of the stem from the pooled-output gradient in one pass (see mil_stem_bwd_fused),
-    or None when the shape/dtype has no fused kernel."""
-    n, h2, w2, c = xs.shape
-    dense = g_pool.shape[-1] == 20            # dense gradient layout (MIL_DT_BF16_DGRAD)
-    need = ctypes.c_size_t(0)
-    rc = L.lib().mil_stem_bwd_fused_workspace(ctypes.byref(need), n, h2, w2, L.dt_code(xs.dtype, dense))
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_bwd_fused_workspace")
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    _need(xs, (n, h2, w2, 16), xs.dtype, "xs")
-    _need(g_pool, (n, hp, wp, 20 if dense else 24), xs.dtype, "g_pool")
-    _need(widx, (n, hp, wp, 24), torch.uint8, "widx")
-    if ws_alloc is not None:                 # deferred reductions: the slab buffer must outlive this call
-        workspace = ws_alloc(need.value)
-    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
-        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=xs.device)
-    if out is None:
-        dw = torch.empty((20, 3, 7, 7), dtype=torch.float32, device=xs.device)
-        db = torch.empty(20, dtype=torch.float32, device=xs.device)
-    else:
-        dw, db = out
-        _need(dw, (20, 3, 7, 7), torch.float32, "dw")
-        _need(db, (20,), torch.float32, "db")
-    end = TIMER.bracket(("stem_bwd_xs", n, 2 * h2, 2 * w2)) if TIMER else None
-    L.check(L.lib().mil_stem_bwd_fused(xs.data_ptr(), g_pool.data_ptr(), widx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h2, w2,
-                                       slope, 0 if out is None else 1, L.dt_code(xs.dtype, dense), L.stream_ptr()),
-            "mil_stem_bwd_fused")
-    if end is not None:
-        end.record()
-    return dw, db
+    """The fused stem backward reading the bf16 space-to-depth copy xs [n,H2,W2,16] (see mil_stem_bwd_fused)."""
+    return _stem_bwd("s2d", xs, g_pool, widx, workspace, out, slope, ws_alloc)
 
 
 def stem_bwd_fused_nchw(x, g_pool, widx, *, workspace=None, out=None, slope=LEAK, ws_alloc=None):
-    """stem_bwd_fused without a kept space-to-depth copy: reads the fp32 tiles x [n,3,H,W] (see mil_stem_bwd_fused_nchw);
-    None when the shape/dtype/alignment has no such kernel."""
-    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
-        return None
-    n, _, h, w = x.shape
-    dense = g_pool.shape[-1] == 20            # dense gradient layout (MIL_DT_BF16_DGRAD / MIL_DT_F32S_DGRAD)
-    need = ctypes.c_size_t(0)
-    rc = L.lib().mil_stem_bwd_fused_nchw_workspace(ctypes.byref(need), n, h, w, L.dt_code(g_pool.dtype, dense, mma=True))
-    if rc == 2 or x.data_ptr() % 16:
-        return None
-    L.check(rc, "mil_stem_bwd_fused_nchw_workspace")
-    h2, w2 = h // 2, w // 2
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    _need(g_pool, (n, hp, wp, 20 if dense else 24), g_pool.dtype, "g_pool")
-    _need(widx, (n, hp, wp, 24), torch.uint8, "widx")
-    if ws_alloc is not None:                 # deferred reductions: the slab buffer must outlive this call
-        workspace = ws_alloc(need.value)
-    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
-        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
-    if out is None:
-        dw = torch.empty((20, 3, 7, 7), dtype=torch.float32, device=x.device)
-        db = torch.empty(20, dtype=torch.float32, device=x.device)
-    else:
-        dw, db = out
-        _need(dw, (20, 3, 7, 7), torch.float32, "dw")
-        _need(db, (20,), torch.float32, "db")
-    end = TIMER.bracket(("stem_bwd", n, h, w)) if TIMER else None
-    rc = L.lib().mil_stem_bwd_fused_nchw(x.data_ptr(), g_pool.data_ptr(), widx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                         workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h, w,
-                                         slope, 0 if out is None else 1, L.dt_code(g_pool.dtype, dense, mma=True), L.stream_ptr())
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_bwd_fused_nchw")
-    if end is not None:
-        end.record()
-    return dw, db
+    """The fused stem backward without a kept space-to-depth copy: reads the fp32 tiles x [n,3,H,W] (see mil_stem_bwd_fused_nchw)."""
+    return _stem_bwd("f32", x, g_pool, widx, workspace, out, slope, ws_alloc)
 
 
 def stem_bwd_fused_u8(x, g_pool, widx, *, workspace=None, out=None, slope=LEAK, ws_alloc=None):
-    """stem_bwd_fused_nchw reading uint8 tiles x [n,3,H,W] (see mil_stem_bwd_fused_u8); None when the shape / dtype / alignment
-    has no such kernel."""
-    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8 or not x.is_cuda or not x.is_contiguous():
-        return None
-    n, _, h, w = x.shape
-    dense = g_pool.shape[-1] == 20            # dense gradient layout (MIL_DT_BF16_DGRAD / MIL_DT_F32S_DGRAD)
-    need = ctypes.c_size_t(0)
-    rc = L.lib().mil_stem_bwd_fused_u8_workspace(ctypes.byref(need), n, h, w, L.dt_code(g_pool.dtype, dense, mma=True))
-    if rc == 2 or x.data_ptr() % 4:
-        return None
-    L.check(rc, "mil_stem_bwd_fused_u8_workspace")
-    h2, w2 = h // 2, w // 2
-    hp, wp = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
-    _need(g_pool, (n, hp, wp, 20 if dense else 24), g_pool.dtype, "g_pool")
-    _need(widx, (n, hp, wp, 24), torch.uint8, "widx")
-    if ws_alloc is not None:                 # deferred reductions: the slab buffer must outlive this call
-        workspace = ws_alloc(need.value)
-    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
-        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
-    if out is None:
-        dw = torch.empty((20, 3, 7, 7), dtype=torch.float32, device=x.device)
-        db = torch.empty(20, dtype=torch.float32, device=x.device)
-    else:
-        dw, db = out
-        _need(dw, (20, 3, 7, 7), torch.float32, "dw")
-        _need(db, (20,), torch.float32, "db")
-    end = TIMER.bracket(("stem_bwd_u8", n, h, w)) if TIMER else None
-    rc = L.lib().mil_stem_bwd_fused_u8(x.data_ptr(), g_pool.data_ptr(), widx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), n, h, w,
-                                       slope, 0 if out is None else 1, L.dt_code(g_pool.dtype, dense, mma=True), L.stream_ptr())
-    if rc == 2:
-        return None
-    L.check(rc, "mil_stem_bwd_fused_u8")
-    if end is not None:
-        end.record()
-    return dw, db
+    """stem_bwd_fused_nchw reading uint8 tiles x [n,3,H,W] (see mil_stem_bwd_fused_u8)."""
+    return _stem_bwd("u8", x, g_pool, widx, workspace, out, slope, ws_alloc)
 
 
 def stem_bwd_dense_ok(src, dtype):
     """True when the fused stem backward for this saved input (the fp32 or uint8 tiles [n,3,H,W], or the s2d copy
-    [n,H2,W2,16]) exists with the dense pooled-gradient layout."""
-    need = ctypes.c_size_t(0)
-    if src.dim() == 4 and src.shape[1] == 3 and src.dtype == torch.uint8:
-        n, _, h, w = src.shape
-        if not src.is_contiguous() or src.data_ptr() % 4:
-            return False
-        return L.lib().mil_stem_bwd_fused_u8_workspace(ctypes.byref(need), n, h, w, L.dt_code(dtype, True, mma=True)) == 0
-    if src.dim() == 4 and src.shape[1] == 3 and src.dtype == torch.float32:
-        n, _, h, w = src.shape
-        if not src.is_contiguous() or src.data_ptr() % 16:
-            return False
-        return L.lib().mil_stem_bwd_fused_nchw_workspace(ctypes.byref(need), n, h, w, L.dt_code(dtype, True, mma=True)) == 0
-    n, h2, w2, _ = src.shape
-    if dtype != torch.bfloat16:         # an fp32 s2d copy (hooked or un-fused stem of the fp32 modes): no fused backward reads it
+    [n,H2,W2,16]) exists with the dense pooled-gradient layout.  (An fp32 s2d copy — hooked or un-fused stem of the fp32
+    modes — is no feed: no fused backward reads it.)"""
+    for f in STEM_FEEDS.values():
+        if f.ok(src):
+            break
+    else:
         return False
-    return L.lib().mil_stem_bwd_fused_workspace(ctypes.byref(need), n, h2, w2, L.dt_code(dtype, True)) == 0
+    if not src.is_contiguous() or src.data_ptr() % f.align or (not f.planar and dtype != torch.bfloat16):
+        return False
+    n, _, _, ext = _stem_extents(f, src)
+    need = ctypes.c_size_t(0)
+    return getattr(L.lib(), f.bwd_ws)(ctypes.byref(need), n, *ext, L.dt_code(dtype, True, mma=True)) == 0
+
+
+def _public(symbol):
+    """The public wrapper of a stem symbol: this module's attribute of the same name without `mil_`, as it is NOW."""
+    return globals()[symbol[4:]]
+
+
+def stem_to_s2d(kind, x, dtype):
+    """The space-to-depth tensor of the tiles `x` of feed `kind` (an "s2d" feed is that tensor)."""
+    return x if kind == "s2d" else _public(STEM_FEEDS[kind].s2d)(x, dtype)
+
+
+def stem_backward(kind, src, g_pool, widx, **kw):
+    """The fused stem backward of feed `kind` (stem_bwd_fused_nchw / _u8 / stem_bwd_fused) on its saved input, or None."""
+    return _public(STEM_FEEDS[kind].bwd)(src, g_pool, widx, **kw)
+
+
+def stem_forward(kind, x, wpack, bias_pad, cout_p, *, dtype, slope=LEAK, keep_s2d=False, allow_fused=True):
+    """The stem on the tiles `x` of feed `kind`: the fused kernel when allowed and there is one, else stem_s2d* -> conv(ks=4)
+    -> maxpool_fwd.  Returns (xs, pool, widx, stem_hw, stem): xs is the space-to-depth tensor where one exists (the caller's
+    own for the "s2d" feed, the converter's when the chain ran, the fused kernel's under keep_s2d — "f32" only — else None);
+    stem is the un-pooled map when the chain ran (forward hooks are shown it), else None."""
+    fused = None
+    if allow_fused and kind == "f32":       # the three public signatures differ: the one place that tells them apart
+        fused = stem_fwd_fused(x, wpack, bias_pad, cout_p, slope=slope, dtype=dtype, keep_s2d=keep_s2d)
+    elif allow_fused and kind == "u8":
+        fused = stem_fwd_fused_u8(x, wpack, bias_pad, cout_p, slope=slope, dtype=dtype)
+    elif allow_fused:
+        fused = stem_fwd_fused_xs(x, wpack, bias_pad, cout_p, slope=slope)
+    if fused is not None:
+        xs, pool, widx = fused if kind == "f32" else ((x if kind == "s2d" else None),) + fused
+        return xs, pool, widx, _stem_extents(STEM_FEEDS[kind], x)[2], None
+    xs = stem_to_s2d(kind, x, dtype)
+    stem = conv(xs, wpack, bias_pad, cout_p, ks=4, stride=1, pad=2, lrelu=True, slope=slope)
+    pool, widx = maxpool_fwd(stem)
+    return xs, pool, widx, tuple(stem.shape[1:3]), stem
 
 
 def avgpool_fc_fwd(x, wfc, c, bias=None):
@@ -755,11 +723,9 @@ def wide_wgrad(x, dz, cin, cout, *, ks, stride, pad, workspace=None, out=None):
     need = ctypes.c_size_t(0)
     L.check(L.lib().mil_wide_wgrad_workspace(ctypes.byref(need), n, h, w, cin, ho, wo, cout, ks, stride, pad,
                                              L.dt_code(x.dtype, mma=True)), "mil_wide_wgrad_workspace")
-    if workspace is None or workspace.numel() * workspace.element_size() < need.value:
-        workspace = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=x.device)
-    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device) if out is None else out
-    _need(dw, (cout, cin, ks, ks), torch.float32, "dw")
-    L.check(L.lib().mil_wide_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), workspace.data_ptr(),
-                                   workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo, cout, ks, stride, pad,
-                                   0 if out is None else 1, L.dt_code(x.dtype, mma=True), L.stream_ptr()), "mil_wide_wgrad")
+    workspace = workspace_for(workspace, need.value, x.device)
+    (dw,), accumulate = _grad_out(None if out is None else (out,), (((cout, cin, ks, ks), "dw"),), x.device)
+    _launch("mil_wide_wgrad", None, x.data_ptr(), dz.data_ptr(), dw.data_ptr(), workspace.data_ptr(),
+            workspace.numel() * workspace.element_size(), n, h, w, cin, ho, wo, cout, ks, stride, pad,
+            accumulate, L.dt_code(x.dtype, mma=True), L.stream_ptr())
     return dw, workspace
