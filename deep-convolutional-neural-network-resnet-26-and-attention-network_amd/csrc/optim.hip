@@ -51,7 +51,8 @@ extern "C" int mil_pack_job_bytes(void) { return (int)sizeof(PackJob); }
 
 extern "C" int mil_pack_job_fill(void* job_host, const float* w, const float* bias, void* out, float* bias_pad, int cout,
                                  int cin, int ks, int mode, int dtype) {
-    if (!job_host || !w || !out || mode < 0 || mode > 3) return MIL_ERR_ARG;
+    if (!job_host || !w || !out || mode < 0 || mode > 4) return MIL_ERR_ARG;
+    if (!mil_pack_shape_ok(mode, cout, cin, ks)) return MIL_ERR_UNSUPPORTED;
     PackJob* j = reinterpret_cast<PackJob*>(job_host);
     *j = PackJob{};
     j->w = w; j->bias = bias; j->out = out; j->bias_pad = bias_pad;

@@ -5,6 +5,9 @@
 //   mode 1 (dgrad):    B[(tap,co)][ci] = W[co][ci][k-1-ky][k-1-kx]   (transposed + flipped)
 //   mode 2 (stem):     7x7 stride-2 filter re-indexed as a 4x4 filter over the 12 space-to-depth channels
 //   mode 3 (dgrad s2): parity-class order, see geom.cuh
+//   mode 4 (stem dgrad): the 7x7 stride-2 filter as the 4x4 TRANSPOSED filter over the 12 space-to-depth channels
+//                      (stem_dgrad.hip): B[(tap,co)][c*4+dy*2+dx] = W[co][c][5-2a+dy][5-2b+dx], tap = a*4+b reads dstem pixel
+//                      (r-1+a, q-1+b); 16 taps x 3 groups of 8 channels = 12 k-steps, one column tile, no bias
 // 3x3 filters whose K side has 20 channels carry a SECOND ordering behind the standard k-steps ("K20", geom.cuh):
 // 24 k-groups in 6 k-steps instead of 27 in 7, read by the 20-channel kernels that keep the LDS pixel record
 // [ch 0-15][ch 16-19][ch 16-19 of the next pixel].
@@ -14,6 +17,12 @@
 #define MIL_PACK_FWD 0
 #define MIL_PACK_DGRAD 1
 #define MIL_PACK_STEM 2
+#define MIL_PACK_STEM_DGRAD 4
+
+// MIL_PACK_STEM_DGRAD exists for the stem's own filter only
+__host__ inline bool mil_pack_shape_ok(int mode, int cout, int cin, int ks) {
+    return mode != MIL_PACK_STEM_DGRAD || (cout == 20 && cin == 3 && ks == 7);
+}
 
 struct PackJob {
     const float* w;
@@ -34,6 +43,7 @@ __host__ inline void mil_pack_job_dims(PackJob* j) {
     j->CG = cin_exec / 8;
     j->NT = (cout_exec + 15) / 16;
     j->nsteps_std = (ks_exec * ks_exec * j->CG + 3) / 4;
+    if (mode == MIL_PACK_STEM_DGRAD) { j->CG = mil_cpad(cout) / 8; j->NT = 1; j->nsteps_std = 16 * j->CG / 4; }
     if (mode == MIL_PACK_DGRAD_S2) { j->CG = mil_cpad(cout) / 8; j->NT = (mil_cpad(cin) + 15) / 16; j->nsteps_std = mil_s2_nsteps(j->CG); }
     j->k20 = mil_pack_has_k20(mode, cout, cin, ks) ? 1 : (mil_pack_has_sk6(mode, cout) ? 2 : 0);      // 2: the stem's SK6 order
     j->nsteps = j->nsteps_std + (j->k20 == 1 ? MIL_K20_STEPS : j->k20 == 2 ? MIL_SK6_STEPS : 0);
@@ -41,7 +51,7 @@ __host__ inline void mil_pack_job_dims(PackJob* j) {
 
 // element idx of job j's packed buffer (also fills bias_pad from the first NT*16 indices)
 __device__ __forceinline__ void mil_pack_job_elem(const PackJob& j, int idx) {
-    if (idx < j.NT * 16 && j.bias_pad && j.mode != MIL_PACK_DGRAD_S2) {
+    if (idx < j.NT * 16 && j.bias_pad && j.mode != MIL_PACK_DGRAD_S2 && j.mode != MIL_PACK_STEM_DGRAD) {
         const int n_out = (j.mode == MIL_PACK_DGRAD) ? j.cin : j.cout;
         j.bias_pad[idx] = (j.bias && idx < n_out) ? j.bias[idx] : 0.f;
     }
@@ -67,6 +77,12 @@ __device__ __forceinline__ void mil_pack_job_elem(const PackJob& j, int idx) {
             if (tap < kk && kin < j.cin && nout < j.cout) val = j.w[((size_t)nout * j.cin + kin) * kk + tap];
         } else if (j.mode == MIL_PACK_DGRAD) {
             if (tap < kk && kin < j.cout && nout < j.cin) val = j.w[((size_t)kin * j.cin + nout) * kk + (kk - 1 - tap)];
+        } else if (j.mode == MIL_PACK_STEM_DGRAD) {
+            if (tap < 16 && kin < j.cout && nout < 12) {
+                const int c = nout >> 2, dy = (nout >> 1) & 1, dx = nout & 1;
+                const int ky = 5 - 2 * (tap >> 2) + dy, kx = 5 - 2 * (tap & 3) + dx;
+                if (ky >= 0 && kx >= 0) val = j.w[(((size_t)kin * 3 + c) * 7 + ky) * 7 + kx];       // ky, kx <= 6 always
+            }
         } else {
             if (tap < 16 && kin < 12 && nout < j.cout) {
                 const int c = kin >> 2, dy = (kin >> 1) & 1, dx = kin & 1;

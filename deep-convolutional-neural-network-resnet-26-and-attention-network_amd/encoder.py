@@ -87,6 +87,7 @@ class ResNet(nn.Module):
         self._reduce_batch = None
         self._pack_table = None
         self._pack_version = None
+        self._stem_dgrad_pack = None    # (tag, fragments) of the stem's data-gradient filter: packed on first use (encoder_backward, want_dx)
         self._side = None
         # a `summary.ActivationSummary` while one is attached: handed the tensors the forward keeps anyway, after the last launch
         self.activation_summary = None
@@ -172,6 +173,17 @@ class ResNet(nn.Module):
     def _packed(self, key, mode):
         return self._pack_table[2][(key, mode)]
 
+    def stem_dgrad_packed(self, dtype):
+        """MIL_PACK_STEM_DGRAD fragments of conv1.weight for the storage dtype `dtype` (inside `L.f32_mma`, as the encoder
+        passes run).  Not part of the per-step pack table: only a backward that asks for the tiles' gradient needs them, so
+        they are packed on first use and again when the weight's storage, its `_version` or WEIGHT_EPOCH changes — the same
+        three signals `refresh_packed` watches (`invalidate_packed_weights` bumps the last)."""
+        w = self.conv1.weight
+        tag = (dtype, L.dt_code(dtype, mma=True), w.data_ptr(), w._version, WEIGHT_EPOCH[0])
+        if self._stem_dgrad_pack is None or self._stem_dgrad_pack[0] != tag:
+            self._stem_dgrad_pack = (tag, ops.pack_weights(w, None, L.PACK_STEM_DGRAD, dtype)[0])
+        return self._stem_dgrad_pack[1]
+
     # ---- forward hooks on children (the reference's children are live modules: SURVEY.md §8b) ----------------
     def block_position(self, bi):
         """(stage index, index inside the stage, stage depth) of block `bi` of `blocks()`."""
@@ -252,7 +264,8 @@ def encoder_forward(net, x, dtype):
         hooks.fire(net.relu, stem_v, stem_v)            # in place upstream (gbm/model.py:25): input is the output
         hooks.fire(net.maxpool, stem_v, hooks.nchw(pool, STEM_WIDTH))
     saved = {"kind": kind, "xs": xs, "x": x if xs is None else None, "x_src": x if (xs is None or kind == "s2d") else None,
-             "x_version": x._version, "stem_hw": stem_hw, "widx": widx, "blocks": []}
+             "x_version": x._version, "stem_hw": stem_hw, "widx": widx, "blocks": [],
+             "tile_hw": (2 * x.shape[1], 2 * x.shape[2]) if kind == "s2d" else tuple(x.shape[2:])}
     return _encoder_forward_body(net, pool, saved, dtype, hk)
 
 
@@ -338,9 +351,14 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
     return feats, saved
 
 
-def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
-    """Gradients of every encoder parameter, in `encoder_params()` order (the input is detached in
-    the reference, gbm/model.py:194-196, so no data-gradient is produced for the tiles)."""
+def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False, dx_reduce=None):
+    """Gradients of every encoder parameter, in `encoder_params()` order.  want_dx=True: returns (those gradients, dx, sal)
+    with the gradient of the tiles themselves behind the stem's weight gradient — `ops.maxpool_bwd` to the un-pooled stem
+    gradient, then `ops.stem_dgrad`: dx [T,3,H,W] fp32 (dx_reduce=None), or sal [T,H,W] = max_c |dx| and dx None
+    (dx_reduce="max_abs").  The gradient chain of the 20-channel stage then keeps its padded layout (the dense one has no
+    pool-gradient scatter), so the parameter gradients are those of `net.dense_grads = False`, bit for bit.  Without want_dx
+    nothing of this is packed or launched (`Attention.forward` detaches its input as the reference does,
+    gbm/model.py:194-196)."""
     blocks = list(net.blocks())
     grads = {}
     if saved["x_src"] is not None and saved["x_src"]._version != saved["x_version"]:
@@ -527,7 +545,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                     # the gradient chain of the first (20-channel) stage below this point runs on kernels that read the
                     # dense layout, when every one of them exists for these shapes: the fused backward and the fused stem backward
                     dense_cx = None
-                    if (net.dense_grads and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or L.is_split(dtype)) and bi > 0 and
+                    if (net.dense_grads and not want_dx and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or L.is_split(dtype)) and bi > 0 and
                             all(b.stride == 1 and b.downsample is None for b in blocks[:bi]) and
                             ops.bwd_fused_workspace_bytes(xin.shape[0], xin.shape[1], xin.shape[2], cin, cin, 3, 1, dtype, True) is not None and
                             ops.stem_bwd_dense_ok(saved["x"] if saved["xs"] is None else saved["xs"], dtype)):
@@ -549,7 +567,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
                               out_hw=xin.shape[1:3], res=addend, act=mask)
             else:
                 dz = ops.conv(dz1, w1d, None, ops.cpad(cin), ks=3, stride=1, pad=1, res=addend, act=mask)
-        fused_stem = None
+        fused_stem = dstem = None
         if net.fuse_backward:               # pool backward + lrelu backward + stem wgrad in one pass (bf16 path)
             stem_ws = (lambda nb: batch.workspace(("s", 0), nb)) if batch is not None else None
             src, src_kind = (saved["x"], saved["kind"]) if saved["xs"] is None else (saved["xs"], "s2d")
@@ -568,6 +586,13 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
     if use_side:
         for side in sides:
             main.wait_stream(side)
+    dx = sal = None
+    if want_dx:
+        if is_dense(dz, STEM_WIDTH):
+            raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
+        if dstem is None:                   # the fused stem backward never materialises it
+            dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
+        dx, sal = ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
     flat = [grads["stem"][0], grads["stem"][1]]
     for bi, blk in enumerate(blocks):
         flat += [grads[f"b{bi}.c1"][0], grads[f"b{bi}.c1"][1], grads[f"b{bi}.c2"][0], grads[f"b{bi}.c2"][1]]
@@ -575,8 +600,8 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True):
             flat.append(grads[f"b{bi}.ds"][0])
     flat.append(dwfc)
     if direct:
-        return [None] * len(flat)          # already accumulated into the parameters' .grad tensors
-    return flat
+        flat = [None] * len(flat)          # already accumulated into the parameters' .grad tensors
+    return (flat, dx, sal) if want_dx else flat
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -584,6 +609,9 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, net, x, *params):
         mode = net.compute_dtype            # torch.bfloat16, torch.float32 (exact-f32 MFMA) or L.BF16X3 (fp32 tensors, split products)
         dtype = L.storage_dtype(mode)
+        if ctx.needs_input_grad[1] and not (x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
+            raise NotImplementedError("a gradient for the tiles exists for the fp32 [T,3,H,W] feed only: the bf16 space-to-depth "
+                                      "tensor (S2dTiles) holds rounded values, and no kernel writes a gradient in its layout")
         with L.f32_mma(L.mma_code(mode)):
             feats, saved = encoder_forward(net, x.detach(), dtype)
         ctx.net, ctx.saved, ctx.dtype, ctx.mode = net, saved, dtype, mode
@@ -591,7 +619,11 @@ class _EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeats):
+        want_dx = ctx.needs_input_grad[1]
         with L.f32_mma(L.mma_code(ctx.mode)):
-            grads = encoder_backward(ctx.net, ctx.saved, dfeats, ctx.dtype, allow_direct=all(ctx.needs_input_grad[2:]))
+            grads = encoder_backward(ctx.net, ctx.saved, dfeats, ctx.dtype, allow_direct=all(ctx.needs_input_grad[2:]), want_dx=want_dx)
         ctx.saved = None
+        if want_dx:                         # x.requires_grad_(): the tiles' own gradient, behind the stem's weight gradient
+            grads, dx, _sal = grads
+            return (None, dx, *grads)
         return (None, None, *grads)

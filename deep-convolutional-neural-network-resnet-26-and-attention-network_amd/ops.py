@@ -616,6 +616,37 @@ def stem_forward(kind, x, wpack, bias_pad, cout_p, *, dtype, slope=LEAK, keep_s2
     return xs, pool, widx, tuple(stem.shape[1:3]), stem
 
 
+def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None):
+    """Data gradient of the stem convolution (see mil_stem_dgrad): dstem [n,ceil(H/2),ceil(W/2),24] — the un-pooled stem
+    gradient `maxpool_bwd` returns, bf16 or fp32 — and the MIL_PACK_STEM_DGRAD fragments of conv1.weight -> (dx, sal) for
+    tiles of hw = (H, W).  reduce=None: dx [n,3,H,W] fp32 and sal None.  reduce="max_abs": sal [n,H,W] fp32 = max_c |dx| from
+    the same accumulators, and dx None unless a `dx` tensor is handed in to be written too.  `dx` / `sal`: the caller's own
+    output tensors (checked) in place of fresh ones."""
+    if reduce not in (None, "max_abs"):
+        raise ValueError(f"reduce must be None or 'max_abs', got {reduce!r}")
+    if dstem.dim() != 4:
+        raise ValueError(f"dstem must be [n,H2,W2,24], got {tuple(dstem.shape)}")
+    n = dstem.shape[0]
+    h, w = hw
+    code = L.dt_code(dstem.dtype, mma=True)
+    _need(dstem, (n, (h + 1) // 2, (w + 1) // 2, 24), dstem.dtype, "dstem")
+    elems = ctypes.c_size_t(0)
+    L.check(L.lib().mil_packed_weight_elems(ctypes.byref(elems), 20, 3, 7, L.PACK_STEM_DGRAD), "mil_packed_weight_elems")
+    _need(wpack, (elems.value,), dstem.dtype, "wpack")
+    if reduce is None:
+        if sal is not None:
+            raise ValueError("sal is written under reduce='max_abs' only")
+        if dx is None:
+            dx = torch.empty((n, 3, h, w), dtype=torch.float32, device=dstem.device)
+    elif sal is None:
+        sal = torch.empty((n, h, w), dtype=torch.float32, device=dstem.device)
+    _need(dx, (n, 3, h, w), torch.float32, "dx")
+    _need(sal, (n, h, w), torch.float32, "sal")
+    _launch("mil_stem_dgrad", ("stem_dgrad", n, h, w, reduce is not None), dstem.data_ptr(), wpack.data_ptr(), L.ptr(dx),
+            L.ptr(sal), n, h, w, 0 if reduce is None else 1, code, L.stream_ptr())
+    return dx, sal
+
+
 def avgpool_fc_fwd(x, wfc, c, bias=None):
     n, h, w, cp = x.shape
     nf = wfc.shape[0]

@@ -34,7 +34,8 @@
  *                          channels; the dense-output code MIL_DT_F32S_DGRAD only for the 40 -> 20 entry, cz_p == 40),
  *                          mil_stem_fwd_fused (xs must be null: no space-to-depth copy),
  *                          mil_stem_bwd_fused_nchw(_workspace) and their uint8-feed forms mil_stem_fwd_fused_u8 and
- *                          mil_stem_bwd_fused_u8(_workspace); every pointwise entry point takes MIL_DT_F32 for the same tensors.
+ *                          mil_stem_bwd_fused_u8(_workspace), and mil_stem_dgrad (MIL_PACK_STEM_DGRAD fragments [hi | lo]); every
+ *                          pointwise entry point takes MIL_DT_F32 for the same tensors.
  *   - master weights, biases, all gradients of parameters, and the whole MIL head are fp32.
  */
 #ifndef MIL_HIP_H
@@ -72,6 +73,8 @@ extern "C" {
 #define MIL_PACK_DGRAD 1 /* B[(tap,co)][ci] = W[co][ci][k-1-ky][k-1-kx]             */
 #define MIL_PACK_STEM 2  /* 7x7/s2 filter as a 4x4/s1 filter over space-to-depth x  */
 #define MIL_PACK_DGRAD_S2 3 /* parity-class order for mil_conv_dgrad_s2; `bias` = 1x1 projection weight */
+#define MIL_PACK_STEM_DGRAD 4 /* the 7x7/s2 stem filter as the 4x4 transposed filter of mil_stem_dgrad: cout=20, cin=3, ks=7 only
+                               * (any other shape: MIL_ERR_UNSUPPORTED from the three packing entry points); no bias_pad */
 
 /* ABI version of this header (bumped on any signature change). */
 int mil_abi_version(void);
@@ -418,6 +421,23 @@ int mil_stem_bwd_fused_u8_workspace(size_t* bytes, int n, int H, int W, int dtyp
 int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, const uint8_t* widx, float* dw, float* db,
                           void* workspace, size_t workspace_bytes, int n, int H, int W, float slope, int accumulate,
                           int dtype, void* stream);
+
+/* Data gradient of the stem convolution: what autograd of Conv2d(3,20,7,2,3) (gbm/model.py:24) returns for its INPUT when the
+ * tiles require a gradient — the step `vanilla_backprop.py` / `grad_times_image.py` of the reference's vendored saliency toolkit
+ * (pytorch-cnn-visualizations-master/src) take through the first layer.  dstem [n,H2,W2,24] (H2 = ceil(H/2), W2 = ceil(W/2);
+ * bf16 under MIL_DT_BF16, fp32 under MIL_DT_F32 / MIL_DT_F32S) is the gradient of the UN-POOLED stem output with the LeakyReLU
+ * mask applied, i.e. mil_maxpool_bwd's output; wpack = MIL_PACK_STEM_DGRAD fragments of conv1.weight.  The forward's 4x4 filter
+ * over the 12 space-to-depth channels runs transposed, one implicit GEMM (K = 16 taps x 24 channels) per 16x16 tile of
+ * space-to-depth pixels, and the result is stored depth-to-space:
+ *     reduce == 0: dx_nchw [n,3,H,W] fp32 (sal is not touched)
+ *     reduce == 1: sal [n,H,W] fp32 = max_c |dx| (Simonyan et al.'s saliency map) from the same accumulators; dx_nchw may be
+ *                  NULL, the three-channel gradient is then never written
+ * Odd H / W: the phantom last space-to-depth row / column is not stored.  No atomics, no workspace: bit-repeatable.
+ * Null dstem / wpack, both outputs null, the output `reduce` selects null, reduce outside {0,1}, n < 0, H or W < 1, another
+ * dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch; one image's dstem of 2 GiB or more: MIL_ERR_UNSUPPORTED — all decided on the
+ * host before any GPU call. */
+int mil_stem_dgrad(const void* dstem, const void* wpack, float* dx_nchw, float* sal, int n, int H, int W, int reduce, int dtype,
+                   void* stream);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten + Linear(80,L,bias=False) (gbm/model.py:31-32,58-60).
  * x [n,hw,cp] -> pooled [n,c] fp32 (kept for backward), feats [n,nf] fp32 = pooled @ wfc^T (+ bias when given:
