@@ -7,7 +7,8 @@ include/mil_hip.h (NHWC, channel-padded, fp32 or bf16 operands) and a custom aut
 provides the backward (dgrad / wgrad / pooling backward) from saved NHWC activations.
 """
 import contextlib
-import os
+import ctypes
+import functools
 
 import torch
 from torch import nn
@@ -107,6 +108,15 @@ class ResNet(nn.Module):
             for blk in getattr(self, f"layer{i + 1}"):
                 yield blk
 
+    def stages(self):
+        """The four stages as (index of the stage's first block in `blocks()`, [its blocks])."""
+        out, first = [], 0
+        for i in range(4):
+            blks = list(getattr(self, f"layer{i + 1}"))
+            out.append((first, blks))
+            first += len(blks)
+        return out
+
     def encoder_params(self):
         """Flat, ordered parameter list handed to the autograd Function."""
         ps = [self.conv1.weight, self.conv1.bias]
@@ -140,7 +150,6 @@ class ResNet(nn.Module):
     def refresh_packed(self, dtype):
         """Make the packed filters current: rebuild the job table if storage moved, re-run the single pack launch
         if any weight changed (parameter version counters, or WEIGHT_EPOCH bumped by FlatAdam.step)."""
-        import ctypes
         lib = L.lib()
         specs = self._pack_specs()
         ptr_tag = (dtype, L.dt_code(dtype, mma=True)) + tuple(w.data_ptr() for _k, w, _b, _m in specs) + tuple(0 if b is None else b.data_ptr() for _k, _w, b, _m in specs)
@@ -269,75 +278,88 @@ def encoder_forward(net, x, dtype):
     return _encoder_forward_body(net, pool, saved, dtype, hk)
 
 
+class _Forward:
+    """One forward pass behind the stem: keeps each block's (xin, o1, out) for the backward and shows them to the hooks."""
+
+    def __init__(self, net, saved, hk):
+        self.net, self.saved, self.hk = net, saved, hk
+        self.stage_in = None                # input of the stage being run: what a hook on the stage's Sequential is shown
+
+    def begin(self, blk):
+        if self.hk is not None:             # the tensors inside a block never exist outside a kernel
+            hooks.refuse(blk, ["conv1", "conv2"] + (["downsample", "downsample.0"] if blk.downsample is not None else []))
+
+    def keep(self, bi, blk, xin, o1, out):
+        self.saved["blocks"].append((xin, o1, out))
+        if self.hk is not None:
+            self.net._fire_block_hooks(bi, blk, self.stage_in, xin, o1, out)
+        return out
+
+
+def _identity_block_forward(fw, bi, blk, t):
+    """A block with the identity shortcut: out = lrelu(conv2(lrelu(conv1(t))) + t)."""
+    net = fw.net
+    fw.begin(blk)
+    w1, b1 = net._packed(f"b{bi}.c1", L.PACK_FWD)
+    w2, b2 = net._packed(f"b{bi}.c2", L.PACK_FWD)
+    both = None
+    if net.fuse_block_forward:              # whole block in one pass (24/40 channels)
+        both = ops.conv_block_fwd(t, w1, b1, w2, b2)
+        if both is None:                    # 80 channels on 8x8 maps: both convs on the LDS-resident images
+            both = ops.conv_pair(t, w1, b1, w2, b2, lreluA=True, resB=t, lreluB=True)
+    if both is None:
+        cp = ops.cpad(blk.conv1.out_channels)
+        o1 = ops.conv(t, w1, b1, cp, ks=3, stride=1, pad=1, lrelu=True)
+        both = o1, ops.conv(o1, w2, b2, cp, ks=3, stride=1, pad=1, res=t, lrelu=True)
+    return fw.keep(bi, blk, t, *both)
+
+
+def _entry_block_forward(fw, first, stage, t):
+    """The first block of a stage that opens with a projection shortcut and, where the stage-wide chain runs, the identity
+    blocks behind it.  Returns (output, how many of the stage's blocks have run)."""
+    net, blk = fw.net, stage[0]
+    fw.begin(blk)
+    s, cp = blk.stride, ops.cpad(blk.conv1.out_channels)
+    w1, b1 = net._packed(f"b{first}.c1", L.PACK_FWD)
+    w2, b2 = net._packed(f"b{first}.c2", L.PACK_FWD)
+    wd, _ = net._packed(f"b{first}.ds", L.PACK_FWD)
+    pair = None
+    if s == 2 and net.fuse_stage_entry:     # both stride-2 convs in one pass over the block input
+        pair = ops.conv_s2_entry(t, w1, b1, wd, cp)
+    if pair is None:
+        pair = ops.conv(t, w1, b1, cp, ks=3, stride=s, pad=1, lrelu=True), ops.conv(t, wd, None, cp, ks=1, stride=s, pad=0)
+    o1, short = pair
+    # A stage whose maps fit the pixel-resident kernel (whole images in LDS: the 80-channel stage at 256x256 tiles): this
+    # entry block's conv2 and BOTH convs of every identity block behind it as ONE chain launch
+    rest = stage[1:]
+    if rest and net.fuse_block_forward and len(rest) <= 2 and all(b.stride == 1 and b.downsample is None for b in rest):
+        convs = [dict(w=w2, bias=b2, res=short, lrelu=True)]
+        for j in range(len(rest)):
+            wa, ba = net._packed(f"b{first + 1 + j}.c1", L.PACK_FWD)
+            wb, bb = net._packed(f"b{first + 1 + j}.c2", L.PACK_FWD)
+            convs += [dict(w=wa, bias=ba, lrelu=True), dict(w=wb, bias=bb, res=2 * j, lrelu=True)]
+        outs = ops.conv_chain(o1, convs)
+        if outs is not None:
+            fw.keep(first, blk, t, o1, outs[0])
+            for j, b in enumerate(rest):
+                fw.begin(b)
+                fw.keep(first + 1 + j, b, outs[2 * j], outs[2 * j + 1], outs[2 * j + 2])
+            return outs[-1], len(stage)
+    out = ops.conv(o1, w2, b2, cp, ks=3, stride=1, pad=1, res=short, lrelu=True)
+    return fw.keep(first, blk, t, o1, out), 1
+
+
 def _encoder_forward_body(net, pool, saved, dtype, hk):
     """Everything behind the stem: the residual stages, the average pool and the fc layer."""
+    fw = _Forward(net, saved, hk)
     t = pool
-    stage_in = pool
-    all_blocks = list(net.blocks())
-    chained = 0                         # blocks already run (and recorded) by a stage-wide conv chain
-    for bi, blk in enumerate(all_blocks):
-        if chained:
-            chained -= 1
-            continue
-        cout = blk.conv1.out_channels
-        s = blk.stride
-        if hk is not None:
-            if net.block_position(bi)[1] == 0:
-                stage_in = t
-            hooks.refuse(blk, ["conv1", "conv2"] + (["downsample", "downsample.0"] if blk.downsample is not None else []))
-        w1, b1 = net._packed(f"b{bi}.c1", L.PACK_FWD)
-        w2, b2 = net._packed(f"b{bi}.c2", L.PACK_FWD)
-        if s == 1 and blk.downsample is None and net.fuse_block_forward:      # whole block in one pass (24/40 channels)
-            both = ops.conv_block_fwd(t, w1, b1, w2, b2)
-            if both is None:                             # 80 channels on 8x8 maps: both convs on the LDS-resident images
-                both = ops.conv_pair(t, w1, b1, w2, b2, lreluA=True, resB=t, lreluB=True)
-            if both is not None:
-                o1, out = both
-                saved["blocks"].append((t, o1, out))
-                if hk is not None:
-                    net._fire_block_hooks(bi, blk, stage_in, t, o1, out)
-                t = out
-                continue
-        pair = None
-        if blk.downsample is not None:
-            wd, _ = net._packed(f"b{bi}.ds", L.PACK_FWD)
-            if s == 2 and net.fuse_stage_entry:          # both stride-2 convs in one pass over the block input
-                pair = ops.conv_s2_entry(t, w1, b1, wd, ops.cpad(cout))
-        if pair is not None:
-            o1, short = pair
-        else:
-            o1 = ops.conv(t, w1, b1, ops.cpad(cout), ks=3, stride=s, pad=1, lrelu=True)
-            short = ops.conv(t, wd, None, ops.cpad(cout), ks=1, stride=s, pad=0) if blk.downsample is not None else t
-        # A stage whose maps fit the pixel-resident kernel (whole images in LDS: the 80-channel stage at 256x256 tiles): this
-        # entry block's conv2 and BOTH convs of every identity block behind it as ONE chain launch
-        depth = net.block_position(bi)[2] if blk.downsample is not None else 0
-        rest = all_blocks[bi + 1:bi + depth] if depth else []
-        if (rest and net.fuse_block_forward and net.block_position(bi)[1] == 0 and len(rest) <= 2 and
-                all(b.stride == 1 and b.downsample is None for b in rest)):
-            convs = [dict(w=w2, bias=b2, res=short, lrelu=True)]
-            for j, b in enumerate(rest):
-                wa, ba = net._packed(f"b{bi + 1 + j}.c1", L.PACK_FWD)
-                wb, bb = net._packed(f"b{bi + 1 + j}.c2", L.PACK_FWD)
-                convs += [dict(w=wa, bias=ba, lrelu=True), dict(w=wb, bias=bb, res=2 * j, lrelu=True)]
-            outs = ops.conv_chain(o1, convs)
-            if outs is not None:
-                saved["blocks"].append((t, o1, outs[0]))
-                if hk is not None:
-                    net._fire_block_hooks(bi, blk, stage_in, t, o1, outs[0])
-                for j, b in enumerate(rest):
-                    xin_j, o1_j, out_j = outs[2 * j], outs[2 * j + 1], outs[2 * j + 2]
-                    saved["blocks"].append((xin_j, o1_j, out_j))
-                    if hk is not None:
-                        hooks.refuse(b, ["conv1", "conv2"])
-                        net._fire_block_hooks(bi + 1 + j, b, stage_in, xin_j, o1_j, out_j)
-                t = outs[-1]
-                chained = len(rest)
-                continue
-        out = ops.conv(o1, w2, b2, ops.cpad(cout), ks=3, stride=1, pad=1, res=short, lrelu=True)
-        saved["blocks"].append((t, o1, out))
-        if hk is not None:
-            net._fire_block_hooks(bi, blk, stage_in, t, o1, out)
-        t = out
+    for first, stage in net.stages():
+        fw.stage_in = t
+        ran = 0
+        if stage[0].downsample is not None:
+            t, ran = _entry_block_forward(fw, first, stage, t)
+        for j in range(ran, len(stage)):
+            t = _identity_block_forward(fw, first + j, stage[j], t)
     pooled, feats = ops.avgpool_fc_fwd(t, net.fc.weight.detach(), STAGE_WIDTHS[-1])
     saved["pooled"] = pooled
     if hk is not None:
@@ -351,6 +373,277 @@ def _encoder_forward_body(net, pool, saved, dtype, hk):
     return feats, saved
 
 
+_MAIN_STREAM = contextlib.nullcontext()
+
+
+def _is_dense(t, c):
+    return t.shape[-1] == c and ops.cpad(c) != c
+
+
+class _Backward:
+    """One backward pass: what its steps read (the net, the saved activations, the storage dtype), the gradients they leave
+    in `grads` under (block, 1 | 2 | 0 for conv1 | conv2 | the projection) or ("stem", 0), and the workspace policy."""
+
+    def __init__(self, net, saved, dtype, allow_direct, want_dx):
+        self.net, self.saved, self.dtype, self.want_dx = net, saved, dtype, want_dx
+        self.blocks = list(net.blocks())
+        self.grads = {}
+        # in-place accumulation into the parameters' .grad: opt-in (dist.FlatParams sets direct_grad; plain loss.backward() only),
+        # and only when autograd wants a gradient for every encoder parameter (allow_direct, from ctx.needs_input_grad)
+        self.direct = net.direct_grad and allow_direct and all(p.grad is not None and p.grad.is_contiguous() for p in net.encoder_params())
+        # Weight gradients only consume (x, dz) and nothing downstream waits for them, so under overlap_wgrad they run on
+        # side streams (round-robin, one slab workspace each) beside the sequential dgrad chain: the small late-layer
+        # and stride-2 launches do not fill 256 CUs alone.
+        self.main = torch.cuda.current_stream()
+        self.sides = net._side_streams()
+        self.rr = 0                         # weight-gradient launches put on side streams so far
+        self.ws = {}                        # the re-used buffers of a pass without deferred reductions
+        self.batch = None
+
+    def reductions(self, device):
+        """Context of the pass's weight-gradient launches.  With `batch_reductions` the producers record their slab reductions
+        in the net's ReduceBatch instead of launching them; leaving the context runs them all in one launch."""
+        net = self.net
+        if not net.batch_reductions or net.overlap_wgrad:
+            return contextlib.nullcontext()
+        if net._reduce_batch is None or net._reduce_batch.device != device:
+            net._reduce_batch = ops.ReduceBatch(device)
+        self.batch = net._reduce_batch
+        return self.batch
+
+    def out(self, *params):
+        """Destination gradient tensors (the parameters' own .grad) when accumulating in place, else None."""
+        return tuple(None if p is None else p.grad for p in params) if self.direct else None
+
+    def workspace(self, kind, key, need, launch, *args, **kw):
+        """`launch(*args, workspace=<slab buffer>, **kw)` for call site (kind, key); kind "w": a weight-gradient kernel, "f": a
+        fused backward, "p": the stage-entry pair.  The one place the three workspace policies are told apart.  need=None:
+        the wrapper sizes the buffer itself and returns the one it used as its last result, which is kept here."""
+        batch, side = self.batch, None
+        if batch is not None:                # deferred reduction: a slab buffer of its own, alive until the batched launch
+            store, slot = batch.ws, (kind, key)
+        elif kind == "w" and self.net.overlap_wgrad:
+            slot = self.rr % len(self.sides)
+            self.rr += 1
+            store, side = self.ws, self.sides[slot]
+            side.wait_stream(self.main)                      # dz was produced on the main stream
+        else:                                # one buffer, re-used; the fused backward's apart from the weight-gradient kernels'
+            store, slot = self.ws, "f" if kind == "f" else "w"
+        with (_MAIN_STREAM if side is None else torch.cuda.stream(side)):
+            if need is None:
+                buf = store.get(slot)
+            elif batch is not None:
+                buf = batch.workspace(slot, need)
+            else:                            # (launches on one stream are serialised: one buffer per stream)
+                buf = store[slot] = ops.workspace_for(store.get(slot), need, args[0].device)
+            res = launch(*args, workspace=buf, **kw)
+        if need is None and res is not None:
+            store[slot] = res[-1]            # under deferred reductions: kept until the batched reduction has run
+        if side is not None:
+            args[0].record_stream(side)
+            args[1].record_stream(side)
+        return res
+
+    def stem_allocator(self):
+        """`ws_alloc` for ops.stem_backward, which sizes its slabs itself: under deferred reductions they must outlive the
+        call and come from the ReduceBatch (key ("s", 0)); otherwise None, and the wrapper allocates."""
+        return None if self.batch is None else functools.partial(self.batch.workspace, ("s", 0))
+
+    def wgrad(self, conv, xin, dzz, key, stem=False):
+        """dW and db of `conv` from its input and the gradient of its output, left in grads[key].  stem: conv1, which runs as
+        a 4x4 stride-1 conv on the space-to-depth tensor."""
+        n, h, w, _ = xin.shape
+        _, ho, wo, _ = dzz.shape
+        cin, cout, bias = conv.in_channels, conv.out_channels, conv.bias
+        ks, stride, pad = (4, 1, 2) if stem else (conv.kernel_size[0], conv.stride[0], conv.padding[0])
+        need = ops.wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, ks, stride, pad, stem, xin.dtype)
+        self.grads[key] = self.workspace("w", key, need, ops.conv_wgrad, xin, dzz, cin, cout, ks=ks, stride=stride, pad=pad, stem=stem,
+                                         want_bias=bias is not None, out=self.out(conv.weight, bias))
+
+    def fused(self, conv, dzz, xin, addend, mask, key):
+        """The one-pass backward of block key[0]'s conv1 or conv2 (key[1]), both 3x3 stride-1: returns the data gradient
+        and leaves dW, db in grads[key] — or returns None where there is no such kernel for the shape, or none is wanted."""
+        if not self.net.fuse_backward:
+            return None
+        n, h, w, _ = dzz.shape
+        cin, cout = conv.in_channels, conv.out_channels
+        dense = _is_dense(dzz, cout)
+        need = ops.bwd_fused_workspace_bytes(n, h, w, cout, cin, 3, 1, dzz.dtype, dense)
+        if need is None:
+            if dense:
+                raise RuntimeError("dense gradient layout chosen for a shape without a fused backward kernel")
+            return None
+        wd, _ = self.net._packed(f"b{key[0]}.c{key[1]}", L.PACK_DGRAD)
+        res = self.workspace("f", key, need, ops.conv_bwd_fused, dzz, wd, xin, cin, cout, addend=addend, mask=mask, out=self.out(conv.weight, conv.bias))
+        if res is None:
+            return None
+        self.grads[key] = res[1:]
+        return res[0]
+
+    def join(self):
+        if self.net.overlap_wgrad:          # the main stream waits for the weight gradients on the side streams
+            for side in self.sides:
+                self.main.wait_stream(side)
+
+
+def _conv2_backward(bw, bi, dz):
+    """conv2 of block `bi`: leaves dW2/db2, and returns dz1 where the one-pass kernel made it on the way — else None, and
+    the caller picks the data-gradient kernel."""
+    conv = bw.blocks[bi].conv2
+    o1 = bw.saved["blocks"][bi][1]
+    dz1 = bw.fused(conv, dz, o1, None, True, (bi, 2))
+    if dz1 is None:
+        if _is_dense(dz, conv.out_channels):
+            raise RuntimeError("dense gradient layout without the fused backward")
+        bw.wgrad(conv, o1, dz, (bi, 2))
+    return dz1
+
+
+def _identity_block_backward(bw, bi, dz):
+    """Backward of identity-shortcut block `bi`: returns the gradient of its input."""
+    net, conv = bw.net, bw.blocks[bi].conv1
+    xin, o1, _out = bw.saved["blocks"][bi]
+    cp = ops.cpad(conv.out_channels)
+    w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
+    w1d, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
+    mask = xin if bi > 0 else None          # block 0 reads the max-pool output (no activation in between)
+    dz1 = _conv2_backward(bw, bi, dz)
+    if dz1 is None:
+        if net.fuse_backward:
+            # 80 channels on 8x8 maps: the block's two transposed convs on the LDS-resident images, one launch:
+            # dz1 = lrelu'(o1) * conv2^T(dz),  dz(prev) = lrelu'(x) * (conv1^T(dz1) + dz)
+            chain = ops.conv_pair(dz, w2d, None, w1d, None, actA=o1, resB=dz, actB=mask)
+            if chain is not None:
+                bw.wgrad(conv, xin, chain[0], (bi, 1))
+                return chain[1]
+        dz1 = ops.conv(dz, w2d, None, cp, ks=3, stride=1, pad=1, act=o1)
+    dz_prev = bw.fused(conv, dz1, xin, dz, mask is not None, (bi, 1))      # one pass: previous block's dz and dW1/db1
+    if dz_prev is None:
+        bw.wgrad(conv, xin, dz1, (bi, 1))
+        dz_prev = ops.conv(dz1, w1d, None, cp, ks=3, stride=1, pad=1, res=dz, act=mask)
+    return dz_prev
+
+
+def _first_stage_dense(bw, bi):
+    """Does the gradient chain of the first (20-channel) stage, below the stage-entry block `bi`, run in the dense layout?
+    Only when every kernel of it that reads the layout exists for these shapes: the fused backward and the fused stem
+    backward.  Not under want_dx: the tiles' gradient needs the un-pooled stem gradient in the padded layout (the dense one
+    has no pool-gradient scatter)."""
+    net, saved, dtype = bw.net, bw.saved, bw.dtype
+    xin = saved["blocks"][bi][0]
+    cin = bw.blocks[bi].conv1.in_channels
+    return (net.dense_grads and not bw.want_dx and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or L.is_split(dtype)) and bi > 0 and
+            all(b.stride == 1 and b.downsample is None for b in bw.blocks[:bi]) and
+            ops.bwd_fused_workspace_bytes(xin.shape[0], xin.shape[1], xin.shape[2], cin, cin, 3, 1, dtype, True) is not None and
+            ops.stem_bwd_dense_ok(saved["x"] if saved["xs"] is None else saved["xs"], dtype))
+
+
+def _entry_block_backward(bw, bi, dz, dz1=None):
+    """Backward of block `bi`, which has a projection shortcut (a stage entry): returns the gradient of its input.  dz1, the
+    gradient behind conv2, is given when a stage-wide chain produced it (and dW2/db2 with it)."""
+    net, blk = bw.net, bw.blocks[bi]
+    xin, o1, _out = bw.saved["blocks"][bi]
+    conv, proj, s = blk.conv1, blk.downsample[0], blk.stride
+    cin, cout = conv.in_channels, conv.out_channels
+    if dz1 is None:
+        dz1 = _conv2_backward(bw, bi, dz)
+        if dz1 is None:
+            w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
+            dz1 = ops.conv(dz, w2d, None, ops.cpad(cout), ks=3, stride=1, pad=1, act=o1)
+    mask = xin if bi > 0 else None          # block 0 reads the max-pool output (no activation in between)
+    pair = None
+    if s == 2 and net.fuse_backward and not net.overlap_wgrad:
+        # both weight gradients of the stage-entry convs from one pass over the block input
+        pair = bw.workspace("p", bi, None, ops.conv_wgrad_pair, xin, dz1, dz, cin, cout, out=bw.out(conv.weight, conv.bias, proj.weight))
+    if pair is not None:
+        bw.grads[bi, 1], bw.grads[bi, 0] = pair[:2], (pair[2], None)
+    else:
+        bw.wgrad(conv, xin, dz1, (bi, 1))
+        bw.wgrad(proj, xin, dz, (bi, 0))
+    if s == 2 and net.fuse_backward:        # both transposed convs + the mask in one pass over the compact dz maps
+        ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
+        dense_cx = cin if _first_stage_dense(bw, bi) else None
+        fused = ops.conv_dgrad_s2(dz1, dz, ws2, ops.cpad(cin), xin.shape[1:3], act=mask, dense_cx=dense_cx)
+        if fused is not None:
+            return fused
+    w1d, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
+    wdd, _ = net._packed(f"b{bi}.ds", L.PACK_DGRAD)
+    up = dict(zero_insert=True, out_hw=xin.shape[1:3]) if s == 2 else {}        # a stride-2 conv transposed: on the zero-inserted dz
+    addend = ops.conv(dz, wdd, None, ops.cpad(cin), ks=1, stride=1, pad=0, **up)
+    return ops.conv(dz1, w1d, None, ops.cpad(cin), ks=3, stride=1, pad=1, res=addend, act=mask, **up)
+
+
+def _stage_dgrad_chain(bw, first, depth, dz_out):
+    """Every 3x3 stride-1 data gradient of the stage in ONE launch (ops.conv_chain: whole images resident in LDS — the
+    80-channel stage at 256x256 tiles), plus the weight gradients they feed.  Returns (dz of the entry block's output, its
+    dz1) — or None when the stage / shape has no such kernel (then the stage is walked block by block)."""
+    net, dtype, blocks, saved = bw.net, bw.dtype, bw.blocks, bw.saved
+    last = first + depth - 1
+    if depth < 2 or depth > 3 or not net.fuse_backward or not (dtype == torch.bfloat16 or L.is_split(dtype)):
+        return None
+    ent = blocks[first]
+    if ent.stride != 2 or ent.downsample is None or any(b.stride != 1 or b.downsample is not None for b in blocks[first + 1:last + 1]):
+        return None
+    cout = ent.conv1.out_channels
+    n, h, w, cp = dz_out.shape
+    if (cp, h, w) not in ops.RESIDENT_SHAPES or ops.bwd_fused_workspace_bytes(n, h, w, cout, cout, 3, 1, dtype) is not None:
+        return None                         # widths with a fused dgrad+wgrad kernel keep it
+    convs, src = [], None                   # src: chain output that is the gradient entering the current block (None: dz_out)
+    for k in range(last, first, -1):
+        xin_k, o1_k, _ = saved["blocks"][k]
+        w2d_k, _ = net._packed(f"b{k}.c2", L.PACK_DGRAD)
+        w1d_k, _ = net._packed(f"b{k}.c1", L.PACK_DGRAD)
+        convs.append(dict(w=w2d_k, act=o1_k))                                            # dmid_k = lrelu'(o1) * conv2^T(dz_k)
+        convs.append(dict(w=w1d_k, res=dz_out if src is None else src, act=xin_k))       # dz_{k-1} = lrelu'(x) * (conv1^T(dmid_k) + dz_k)
+        src = len(convs) - 1
+    w2d_e, _ = net._packed(f"b{first}.c2", L.PACK_DGRAD)
+    convs.append(dict(w=w2d_e, act=saved["blocks"][first][1]))                           # the entry block's dz1
+    outs = ops.conv_chain(dz_out, convs)
+    if outs is None:
+        return None
+    dz_k = dz_out
+    for i, k in enumerate(range(last, first, -1)):
+        xin_k, o1_k, _ = saved["blocks"][k]
+        bw.wgrad(blocks[k].conv2, o1_k, dz_k, (k, 2))
+        bw.wgrad(blocks[k].conv1, xin_k, outs[2 * i], (k, 1))
+        dz_k = outs[2 * i + 1]
+    bw.wgrad(ent.conv2, saved["blocks"][first][1], dz_k, (first, 2))
+    return dz_k, outs[-1]
+
+
+def _stage_backward(bw, stage, dz):
+    """Backward of `stage` = (index of its first block, its blocks): the stage-wide data-gradient chain where there is one,
+    else block by block, last to first.  Returns the gradient of the stage's input."""
+    first, blks = stage
+    chain = _stage_dgrad_chain(bw, first, len(blks), dz)
+    if chain is not None:                   # what is left is the entry block, from its dz1 on
+        return _entry_block_backward(bw, first, *chain)
+    for bi in range(first + len(blks) - 1, first - 1, -1):
+        step = _identity_block_backward if blks[bi - first].downsample is None else _entry_block_backward
+        dz = step(bw, bi, dz)
+    return dz
+
+
+def _stem_backward(bw, dz):
+    """conv1's weight gradient from dz, the gradient of the max-pool output.  Returns the un-pooled stem gradient where it
+    was made on the way (the fused kernel never materialises it), else None."""
+    net, saved = bw.net, bw.saved
+    fused_stem = None
+    if net.fuse_backward:                   # pool backward + lrelu backward + stem wgrad in one pass (bf16 path)
+        src, src_kind = (saved["x"], saved["kind"]) if saved["xs"] is None else (saved["xs"], "s2d")
+        fused_stem = ops.stem_backward(src_kind, src, dz, saved["widx"], out=bw.out(net.conv1.weight, net.conv1.bias), ws_alloc=bw.stem_allocator())
+    if fused_stem is not None:
+        bw.grads["stem", 0] = fused_stem
+        return None
+    if _is_dense(dz, STEM_WIDTH):
+        raise RuntimeError("dense gradient layout without the fused stem backward")
+    dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
+    if saved["xs"] is None:
+        saved["xs"] = ops.stem_to_s2d(saved["kind"], saved["x"], dz.dtype)
+    bw.wgrad(net.conv1, saved["xs"], dstem, ("stem", 0), stem=True)
+    return dstem
+
+
 def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False, dx_reduce=None):
     """Gradients of every encoder parameter, in `encoder_params()` order.  want_dx=True: returns (those gradients, dx, sal)
     with the gradient of the tiles themselves behind the stem's weight gradient — `ops.maxpool_bwd` to the un-pooled stem
@@ -359,247 +652,33 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False
     pool-gradient scatter), so the parameter gradients are those of `net.dense_grads = False`, bit for bit.  Without want_dx
     nothing of this is packed or launched (`Attention.forward` detaches its input as the reference does,
     gbm/model.py:194-196)."""
-    blocks = list(net.blocks())
-    grads = {}
     if saved["x_src"] is not None and saved["x_src"]._version != saved["x_version"]:
         raise RuntimeError("the input tiles were modified in place between the encoder's forward and backward: conv1's gradient is "
                            "computed from them (no space-to-depth copy is kept).  Keep the tensor untouched until backward, or set "
                            "`net.cnn.module.keep_s2d = True` to have the forward keep its own copy (bf16: the space-to-depth records; "
                            "bf16x3: an fp32 clone of the tiles)")
-    last_out = saved["blocks"][-1][2]
-    dz, dwfc = ops.avgpool_fc_bwd(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], last_out,
-                                  STAGE_WIDTHS[-1],
-                                  out=net.fc.weight.grad if (net.direct_grad and allow_direct and net.fc.weight.grad is not None and
-                                                             all(p.grad is not None and p.grad.is_contiguous() for p in net.encoder_params())) else None)
-    # Weight gradients only consume (x, dz) and nothing downstream waits for them, so they run on side
-    # streams (round-robin, one slab workspace each) beside the sequential dgrad chain: the small late-layer
-    # and stride-2 launches do not fill 256 CUs alone.
-    main = torch.cuda.current_stream()
-    sides = net._side_streams()
-    use_side = net.overlap_wgrad
-    ws = [None] * (len(sides) + 1)
-    rr = [0]
-
-    # in-place accumulation into the parameters' .grad: opt-in (dist.FlatParams sets direct_grad; plain loss.backward() only),
-    # and only when autograd wants a gradient for every encoder parameter (allow_direct, from ctx.needs_input_grad)
-    direct = net.direct_grad and allow_direct and all(p.grad is not None and p.grad.is_contiguous() for p in net.encoder_params())
-    batch = None
-    if net.batch_reductions and not use_side:
-        if net._reduce_batch is None or net._reduce_batch.device != dfeats.device:
-            net._reduce_batch = ops.ReduceBatch(dfeats.device)
-        batch = net._reduce_batch
-
-    def gout(*params):
-        """Destination gradient tensors (the parameters' own .grad) when accumulating in place, else None."""
-        return tuple(None if p is None else p.grad for p in params) if direct else None
-
-    def wgrad(xin, dzz, cin, cout, key=None, **kw):
-        n, h, w, _ = xin.shape
-        _, ho, wo, _ = dzz.shape
-        need = ops.wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, kw["ks"], kw["stride"], kw["pad"],
-                                         kw.get("stem", False), xin.dtype)
-        if batch is not None:                # deferred reduction: a slab buffer of its own, alive until the batched launch
-            assert key is not None, "deferred reductions need one workspace per call site: pass key="
-            return ops.conv_wgrad(xin, dzz, cin, cout, workspace=batch.workspace(("w", key), need), **kw)
-        if not use_side:
-            ws[-1] = ops.workspace_for(ws[-1], need, xin.device)
-            return ops.conv_wgrad(xin, dzz, cin, cout, workspace=ws[-1], **kw)
-        k = rr[0] % len(sides)
-        rr[0] += 1
-        side = sides[k]
-        side.wait_stream(main)                       # dz was produced on the main stream
-        with torch.cuda.stream(side):
-            ws[k] = ops.workspace_for(ws[k], need, xin.device)   # launches on one stream are serialised: one buffer each
-            out = ops.conv_wgrad(xin, dzz, cin, cout, workspace=ws[k], **kw)
-        xin.record_stream(side)
-        dzz.record_stream(side)
-        return out
-
-    fws = None
-
-    def is_dense(t, c):
-        return t.shape[-1] == c and ops.cpad(c) != c
-
-    def fused_bwd(dzz, wd, xin, cin, cout, addend, mask, out, key=None):
-        nonlocal fws
-        n, h, w, _ = dzz.shape
-        dense = is_dense(dzz, cout)
-        need = ops.bwd_fused_workspace_bytes(n, h, w, cout, cin, 3, 1, dzz.dtype, dense)
-        if need is None:
-            if dense:
-                raise RuntimeError("dense gradient layout chosen for a shape without a fused backward kernel")
-            return None
-        if batch is not None:
-            return ops.conv_bwd_fused(dzz, wd, xin, cin, cout, addend=addend, mask=mask, workspace=batch.workspace(("f", key), need), out=out)
-        fws = ops.workspace_for(fws, need, dzz.device)
-        return ops.conv_bwd_fused(dzz, wd, xin, cin, cout, addend=addend, mask=mask, workspace=fws, out=out)
-
-    # weight-gradient producers record their slab reductions; leaving the block runs them all in one launch
-    def stage_dgrad_chain(bi, dz_out):
-        """Every 3x3 stride-1 data gradient of the stage that ENDS with block bi in ONE launch (ops.conv_chain: whole images
-        resident in LDS — the 80-channel stage at 256x256 tiles), plus the weight gradients they feed.  Returns
-        {block: "done"} for its identity blocks and {entry block: (dz of its output, dz1)} — or None when the stage / shape
-        has no such kernel (then the per-block path below runs)."""
-        li, j, depth = net.block_position(bi)
-        e = bi - depth + 1
-        if j != depth - 1 or depth < 2 or depth > 3 or not net.fuse_backward or not (dtype == torch.bfloat16 or L.is_split(dtype)):
-            return None
-        ent = blocks[e]
-        if ent.stride != 2 or ent.downsample is None or any(b.stride != 1 or b.downsample is not None for b in blocks[e + 1:bi + 1]):
-            return None
-        cout = ent.conv1.out_channels
-        n, h, w, cp = dz_out.shape
-        if (cp, h, w) not in ops.RESIDENT_SHAPES or ops.bwd_fused_workspace_bytes(n, h, w, cout, cout, 3, 1, dtype) is not None:
-            return None                         # widths with a fused dgrad+wgrad kernel keep it
-        convs, src = [], None                   # src: chain output that is the gradient entering the current block (None: dz_out)
-        for k in range(bi, e, -1):
-            xin_k, o1_k, _ = saved["blocks"][k]
-            w2d_k, _ = net._packed(f"b{k}.c2", L.PACK_DGRAD)
-            w1d_k, _ = net._packed(f"b{k}.c1", L.PACK_DGRAD)
-            convs.append(dict(w=w2d_k, act=o1_k))                                            # dmid_k = lrelu'(o1) * conv2^T(dz_k)
-            convs.append(dict(w=w1d_k, res=dz_out if src is None else src, act=xin_k))       # dz_{k-1} = lrelu'(x) * (conv1^T(dmid_k) + dz_k)
-            src = len(convs) - 1
-        _xin_e, o1_e, _ = saved["blocks"][e]
-        w2d_e, _ = net._packed(f"b{e}.c2", L.PACK_DGRAD)
-        convs.append(dict(w=w2d_e, act=o1_e))                                                # the entry block's dz1
-        outs = ops.conv_chain(dz_out, convs)
-        if outs is None:
-            return None
-        done = {}
-        dz_k = dz_out
-        for i, k in enumerate(range(bi, e, -1)):
-            xin_k, o1_k, _ = saved["blocks"][k]
-            dmid_k, dz_prev = outs[2 * i], outs[2 * i + 1]
-            grads[f"b{k}.c2"] = wgrad(o1_k, dz_k, cout, cout, key=(k, 2), ks=3, stride=1, pad=1, out=gout(blocks[k].conv2.weight, blocks[k].conv2.bias))
-            grads[f"b{k}.c1"] = wgrad(xin_k, dmid_k, cout, cout, key=(k, 1), ks=3, stride=1, pad=1, out=gout(blocks[k].conv1.weight, blocks[k].conv1.bias))
-            done[k] = "done"
-            dz_k = dz_prev
-        grads[f"b{e}.c2"] = wgrad(o1_e, dz_k, cout, cout, key=(e, 2), ks=3, stride=1, pad=1, out=gout(ent.conv2.weight, ent.conv2.bias))
-        done[e] = (dz_k, outs[-1])
-        return done
-
-    pre = {}                                    # blocks whose data gradients a stage-wide chain has already produced
-    with (batch if batch is not None else contextlib.nullcontext()):
-        for bi in range(len(blocks) - 1, -1, -1):
-            blk = blocks[bi]
-            xin, o1, _out = saved["blocks"][bi]
-            cin, cout, s = blk.conv1.in_channels, blk.conv1.out_channels, blk.stride
-            if bi not in pre:
-                chain = stage_dgrad_chain(bi, dz)
-                if chain is not None:
-                    pre.update(chain)
-            if pre.get(bi) == "done":
-                continue
-            w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
-            if bi in pre:                               # stage entry behind a chain: dz of its output and dz1 are there, dW2/db2 too
-                dz, dz1 = pre[bi]
-                fused = "chain"
-            else:
-                fused = fused_bwd(dz, w2d, o1, cout, cout, None, True, gout(blk.conv2.weight, blk.conv2.bias), key=(bi, 2)) if net.fuse_backward else None
-            if fused == "chain":
-                pass
-            elif fused is not None:                     # one pass: dz1 and dW2/db2
-                dz1, grads[f"b{bi}.c2"] = fused[0], (fused[1], fused[2])
-            elif is_dense(dz, cout):
-                raise RuntimeError("dense gradient layout without the fused backward")
-            else:
-                grads[f"b{bi}.c2"] = wgrad(o1, dz, cout, cout, key=(bi, 2), ks=3, stride=1, pad=1, out=gout(blk.conv2.weight, blk.conv2.bias))
-                if s == 1 and blk.downsample is None and net.fuse_backward:
-                    # 80 channels on 8x8 maps: the block's two transposed convs on the LDS-resident images, one launch:
-                    # dz1 = lrelu'(o1) * conv2^T(dz),  dz(prev) = lrelu'(x) * (conv1^T(dz1) + dz)
-                    w1d_, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
-                    chain = ops.conv_pair(dz, w2d, None, w1d_, None, actA=o1, resB=dz, actB=xin if bi > 0 else None)
-                    if chain is not None:
-                        dz1, dz_prev = chain
-                        grads[f"b{bi}.c1"] = wgrad(xin, dz1, cin, cout, key=(bi, 1), ks=3, stride=1, pad=1, out=gout(blk.conv1.weight, blk.conv1.bias))
-                        dz = dz_prev
-                        continue
-                dz1 = ops.conv(dz, w2d, None, ops.cpad(cout), ks=3, stride=1, pad=1, act=o1)
-            w1d, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
-            mask = xin if bi > 0 else None          # block 0 reads the max-pool output (no activation in between)
-            if s == 1 and blk.downsample is None and net.fuse_backward:
-                fused = fused_bwd(dz1, w1d, xin, cin, cout, dz, mask is not None, gout(blk.conv1.weight, blk.conv1.bias), key=(bi, 1))
-                if fused is not None:                   # one pass: previous block's dz and dW1/db1
-                    dz, grads[f"b{bi}.c1"] = fused[0], (fused[1], fused[2])
-                    continue
-            pair = None
-            if s == 2 and blk.downsample is not None and net.fuse_backward and not use_side:
-                # both weight gradients of the stage-entry convs from one pass over the block input
-                o = gout(blk.conv1.weight, blk.conv1.bias, blk.downsample[0].weight)
-                pws = batch.ws.get(("p", bi)) if batch is not None else ws[-1]
-                pair = ops.conv_wgrad_pair(xin, dz1, dz, cin, cout, workspace=pws, out=o)
-            if pair is not None:
-                if batch is not None:
-                    batch.ws[("p", bi)] = pair[3]           # kept until the batched reduction has run
-                else:
-                    ws[-1] = pair[3]
-                grads[f"b{bi}.c1"], grads[f"b{bi}.ds"] = (pair[0], pair[1]), (pair[2], None)
-            else:
-                grads[f"b{bi}.c1"] = wgrad(xin, dz1, cin, cout, key=(bi, 1), ks=3, stride=s, pad=1, out=gout(blk.conv1.weight, blk.conv1.bias))
-            if blk.downsample is not None:
-                if pair is None:
-                    grads[f"b{bi}.ds"] = wgrad(xin, dz, cin, cout, key=(bi, 0), ks=1, stride=s, pad=0, want_bias=False,
-                                               out=gout(blk.downsample[0].weight, None))
-                if s == 2 and net.fuse_backward:     # both transposed convs + the mask in one pass over the compact dz maps
-                    ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
-                    # the gradient chain of the first (20-channel) stage below this point runs on kernels that read the
-                    # dense layout, when every one of them exists for these shapes: the fused backward and the fused stem backward
-                    dense_cx = None
-                    if (net.dense_grads and not want_dx and cin == STEM_WIDTH and ops.cpad(cin) != cin and (dtype == torch.bfloat16 or L.is_split(dtype)) and bi > 0 and
-                            all(b.stride == 1 and b.downsample is None for b in blocks[:bi]) and
-                            ops.bwd_fused_workspace_bytes(xin.shape[0], xin.shape[1], xin.shape[2], cin, cin, 3, 1, dtype, True) is not None and
-                            ops.stem_bwd_dense_ok(saved["x"] if saved["xs"] is None else saved["xs"], dtype)):
-                        dense_cx = cin
-                    fused = ops.conv_dgrad_s2(dz1, dz, ws2, ops.cpad(cin), xin.shape[1:3], act=mask, dense_cx=dense_cx)
-                    if fused is not None:
-                        dz = fused
-                        continue
-                wdd, _ = net._packed(f"b{bi}.ds", L.PACK_DGRAD)
-                if s == 2:
-                    addend = ops.conv(dz, wdd, None, ops.cpad(cin), ks=1, stride=1, pad=0, zero_insert=True,
-                                      out_hw=xin.shape[1:3])
-                else:
-                    addend = ops.conv(dz, wdd, None, ops.cpad(cin), ks=1, stride=1, pad=0)
-            else:
-                addend = dz
-            if s == 2:
-                dz = ops.conv(dz1, w1d, None, ops.cpad(cin), ks=3, stride=1, pad=1, zero_insert=True,
-                              out_hw=xin.shape[1:3], res=addend, act=mask)
-            else:
-                dz = ops.conv(dz1, w1d, None, ops.cpad(cin), ks=3, stride=1, pad=1, res=addend, act=mask)
-        fused_stem = dstem = None
-        if net.fuse_backward:               # pool backward + lrelu backward + stem wgrad in one pass (bf16 path)
-            stem_ws = (lambda nb: batch.workspace(("s", 0), nb)) if batch is not None else None
-            src, src_kind = (saved["x"], saved["kind"]) if saved["xs"] is None else (saved["xs"], "s2d")
-            fused_stem = ops.stem_backward(src_kind, src, dz, saved["widx"], out=gout(net.conv1.weight, net.conv1.bias), ws_alloc=stem_ws)
-        if fused_stem is not None:
-            grads["stem"] = fused_stem
-        elif is_dense(dz, STEM_WIDTH):
-            raise RuntimeError("dense gradient layout without the fused stem backward")
-        else:
-            dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
-            if saved["xs"] is None:
-                saved["xs"] = ops.stem_to_s2d(saved["kind"], saved["x"], dz.dtype)
-            grads["stem"] = wgrad(saved["xs"], dstem, 3, STEM_WIDTH, key=("stem", 0), ks=4, stride=1, pad=2, stem=True,
-                                  out=gout(net.conv1.weight, net.conv1.bias))
-
-    if use_side:
-        for side in sides:
-            main.wait_stream(side)
+    bw = _Backward(net, saved, dtype, allow_direct, want_dx)
+    dz, dwfc = ops.avgpool_fc_bwd(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], saved["blocks"][-1][2],
+                                  STAGE_WIDTHS[-1], out=net.fc.weight.grad if bw.direct else None)
+    with bw.reductions(dfeats.device):
+        for stage in reversed(net.stages()):
+            dz = _stage_backward(bw, stage, dz)
+        dstem = _stem_backward(bw, dz)
+    bw.join()
     dx = sal = None
     if want_dx:
-        if is_dense(dz, STEM_WIDTH):
+        if _is_dense(dz, STEM_WIDTH):
             raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
         if dstem is None:                   # the fused stem backward never materialises it
             dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
         dx, sal = ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
-    flat = [grads["stem"][0], grads["stem"][1]]
-    for bi, blk in enumerate(blocks):
-        flat += [grads[f"b{bi}.c1"][0], grads[f"b{bi}.c1"][1], grads[f"b{bi}.c2"][0], grads[f"b{bi}.c2"][1]]
+    flat = list(bw.grads["stem", 0])
+    for bi, blk in enumerate(bw.blocks):
+        flat += [*bw.grads[bi, 1], *bw.grads[bi, 2]]
         if blk.downsample is not None:
-            flat.append(grads[f"b{bi}.ds"][0])
+            flat.append(bw.grads[bi, 0][0])
     flat.append(dwfc)
-    if direct:
+    if bw.direct:
         flat = [None] * len(flat)          # already accumulated into the parameters' .grad tensors
     return (flat, dx, sal) if want_dx else flat
 

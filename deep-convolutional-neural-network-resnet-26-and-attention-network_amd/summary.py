@@ -2,8 +2,8 @@
 
 The reference's training loop watches its own layers: `prime_activation_summary` on the classifier before every epoch
 (gbm/classify_combined.py:418) and a per-parameter weight mean / max written into `epoch_stats` after it (:484-485).
-Here every tensor such a summary needs is already in HBM in the layout the kernels wrote — `_encoder_forward_body` keeps the
-max-pool output, `(x, o1, out)` of every block, the pooled features and `feats` on every path and in every compute mode;
+Here every tensor such a summary needs is already in HBM in the layout the kernels wrote — the encoder's forward
+(`_encoder_forward_body`, a loop over the stages with one function per block kind) keeps the max-pool output, `(x, o1, out)` of every block, the pooled features and `feats` on every path and in every compute mode;
 parameters and gradients of a `FlatParams` sit in two flat fp32 buckets — so the summaries read them where they lie
 (`mil_tensor_stats_all`, csrc/tensor_stats.hip): channel-padded NHWC, bf16 or fp32, pad channels skipped, a whole table of
 tensors in two launches, eight fp64 numbers per tensor, no copy, no host synchronisation, and no influence on which

@@ -211,6 +211,9 @@ def test_forward_hooks_are_accepted_and_unmaterialised_children_refuse():
         hooks.refuse(enc.layer2[0], ["conv1", "conv2"])
     h4.remove()
     assert [enc.block_position(i) for i in (0, 2, 3, 11)] == [(0, 0, 3), (0, 2, 3), (1, 0, 3), (3, 2, 3)]
+    stages = enc.stages()
+    assert ([first for first, _ in stages] == [0, 3, 6, 9] and all(len(blks) == 3 for _, blks in stages) and
+            all(stages[k][1][0] is getattr(enc, f"layer{k + 1}")[0] for k in range(4)))
     with pytest.raises(RuntimeError):
         net.train().forward_tile_parallel(torch.zeros(4, 3, 32, 32))          # inference path only
 
