@@ -22,6 +22,7 @@ MIL_DT_F32, MIL_DT_BF16, MIL_DT_BF16_DGRAD, MIL_DT_F32S, MIL_DT_F32S_DGRAD = 0, 
 # as three bf16 MFMAs per k-step on hi/lo-split operands (MIL_DT_F32S in include/mil_hip.h)
 BF16X3 = "bf16x3"
 PACK_FWD, PACK_DGRAD, PACK_STEM, PACK_DGRAD_S2, PACK_STEM_DGRAD = 0, 1, 2, 3, 4
+FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pillow's own codes)
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -66,6 +67,8 @@ _SIGS = {
     "mil_maxpool_bwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_resize_plan": ([_i, _i, _c.POINTER(_i)], _i),
     "mil_resize_coeffs": ([_i, _i, _vp, _vp], _i),
+    "mil_resample_plan": ([_i, _i, _i, _c.POINTER(_i)], _i),
+    "mil_resample_coeffs": ([_i, _i, _i, _vp, _vp], _i),
     "mil_tile_preprocess": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_tile_preprocess_s2d": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_tile_preprocess_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
@@ -92,6 +95,7 @@ _SIGS = {
     "mil_stem_bwd_fused_u8_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_stem_bwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
     "mil_stem_dgrad": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mil_grad_cam": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_wide_packed_elems": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),

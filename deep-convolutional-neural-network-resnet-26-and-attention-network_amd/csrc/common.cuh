@@ -56,6 +56,10 @@ __device__ __forceinline__ void mil_split4(const f32x4_t& v, bf16x4_t& hi, bf16x
 // mil_stem_bwd_fused_nchw).
 #define MIL_DT_F32S_DGRAD 4
 
+// Resampling filters of mil_resample_plan / mil_resample_coeffs (the values of Pillow's Image.LANCZOS / Image.BILINEAR)
+#define MIL_FILTER_LANCZOS 1
+#define MIL_FILTER_BILINEAR 2
+
 // Channel padding used by every NHWC activation tensor (multiple of 8 elements = one 16-B bf16 piece).
 __host__ __device__ constexpr int mil_cpad(int c) { return (c + 7) / 8 * 8; }
 // Output-channel tile count (16-wide MFMA columns) <-> padded channel count.

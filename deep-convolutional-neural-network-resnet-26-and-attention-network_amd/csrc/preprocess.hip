@@ -271,24 +271,44 @@ __global__ __launch_bounds__(256) void tile_preprocess_kernel(PrepArgs a) {
     }
 }
 
-// Pillow's coefficient construction for a bilinear resize of a whole axis (host, float64 — same operation order).
-static int prep_ksize(int in_size, int out_size) {
-    double scale = (double)in_size / (double)out_size;
-    double filterscale = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(1.0 * filterscale) * 2 + 1;
+// Pillow's coefficient construction for a resize of a whole axis (host, float64 — same operation order as its
+// precompute_coeffs / normalize_coeffs_8bpc).  The filter is the triangle (MIL_FILTER_BILINEAR, support 1: what the tile
+// chain above resamples with) or the truncated sinc w(x) = sinc(x) sinc(x/3) on [-3, 3) (MIL_FILTER_LANCZOS, support 3: what
+// mil_grad_cam resizes its maps with).  Lanczos coefficients can be negative: the half-ulp bias of the fixed-point rounding
+// follows the coefficient's sign.
+static double prep_filter_support(int filter) { return filter == MIL_FILTER_LANCZOS ? 3.0 : 1.0; }
+
+static double prep_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
 }
 
-extern "C" int mil_resize_plan(int in_size, int out_size, int* ksize) {
-    if (in_size <= 0 || out_size <= 0 || !ksize) return MIL_ERR_ARG;
-    *ksize = prep_ksize(in_size, out_size);
+static double prep_filter(int filter, double x) {
+    if (filter == MIL_FILTER_LANCZOS) return (-3.0 <= x && x < 3.0) ? prep_sinc(x) * prep_sinc(x / 3) : 0.0;
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+static int prep_ksize(int in_size, int out_size, int filter = MIL_FILTER_BILINEAR) {
+    double scale = (double)in_size / (double)out_size;
+    double filterscale = scale < 1.0 ? 1.0 : scale;
+    return (int)ceil(prep_filter_support(filter) * filterscale) * 2 + 1;
+}
+
+static bool prep_filter_ok(int filter) { return filter == MIL_FILTER_BILINEAR || filter == MIL_FILTER_LANCZOS; }
+
+extern "C" int mil_resample_plan(int in_size, int out_size, int filter, int* ksize) {
+    if (in_size <= 0 || out_size <= 0 || !prep_filter_ok(filter) || !ksize) return MIL_ERR_ARG;
+    *ksize = prep_ksize(in_size, out_size, filter);
     return MIL_OK;
 }
 
-extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk) {
-    if (in_size <= 0 || out_size <= 0 || !bounds || !kk) return MIL_ERR_ARG;
+extern "C" int mil_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk) {
+    if (in_size <= 0 || out_size <= 0 || !prep_filter_ok(filter) || !bounds || !kk) return MIL_ERR_ARG;
     const double scale = (double)in_size / (double)out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
+    const double support = prep_filter_support(filter) * filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     const double ss = 1.0 / filterscale;
     double* w = new double[ksize];
@@ -301,9 +321,7 @@ extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
         xmax -= xmin;
         double ww = 0.0;
         for (int x = 0; x < xmax; ++x) {
-            double v = (x + xmin - center + 0.5) * ss;
-            if (v < 0.0) v = -v;
-            w[x] = v < 1.0 ? 1.0 - v : 0.0;
+            w[x] = prep_filter(filter, (x + xmin - center + 0.5) * ss);
             ww += w[x];
         }
         for (int x = 0; x < ksize; ++x) {
@@ -315,6 +333,14 @@ extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
     }
     delete[] w;
     return MIL_OK;
+}
+
+extern "C" int mil_resize_plan(int in_size, int out_size, int* ksize) {
+    return mil_resample_plan(in_size, out_size, MIL_FILTER_BILINEAR, ksize);
+}
+
+extern "C" int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk) {
+    return mil_resample_coeffs(in_size, out_size, MIL_FILTER_BILINEAR, bounds, kk);
 }
 
 // Windows of a larger source (mil_tile_preprocess_win*): the source convention of mil_roi_stats.

@@ -399,6 +399,7 @@ class _Backward:
         self.rr = 0                         # weight-gradient launches put on side streams so far
         self.ws = {}                        # the re-used buffers of a pass without deferred reductions
         self.batch = None
+        self.bare_input = None              # encoder_stage_gradient: the entry block whose input gradient is left un-masked
 
     def reductions(self, device):
         """Context of the pass's weight-gradient launches.  With `batch_reductions` the producers record their slab reductions
@@ -550,7 +551,9 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
         if dz1 is None:
             w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
             dz1 = ops.conv(dz, w2d, None, ops.cpad(cout), ks=3, stride=1, pad=1, act=o1)
-    mask = xin if bi > 0 else None          # block 0 reads the max-pool output (no activation in between)
+    # block 0 reads the max-pool output (no activation in between); bare_input: the gradient of the block's INPUT TENSOR is
+    # wanted — the output of the stage below — not that of the pre-activation map behind it
+    mask = xin if bi > 0 and bi != bw.bare_input else None
     pair = None
     if s == 2 and net.fuse_backward and not net.overlap_wgrad:
         # both weight gradients of the stage-entry convs from one pass over the block input
@@ -681,6 +684,33 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False
     if bw.direct:
         flat = [None] * len(flat)          # already accumulated into the parameters' .grad tensors
     return (flat, dx, sal) if want_dx else flat
+
+
+def encoder_stage_gradient(net, saved, dfeats, dtype, stage):
+    """Gradient of the OUTPUT of stage `stage` (1..4: layer1..layer4; `saved["blocks"][last block of the stage][2]`, the tensor
+    behind the block's LeakyReLU) for the feature gradient `dfeats` [T,80], in that tensor's padded NHWC layout and dtype: the
+    backward chain cut short.  `ops.avgpool_fc_bwd_data`, then `_stage_backward` for the stages above `stage`; the stem and the
+    stages below are not run.  The chain itself carries gradients of PRE-activation maps (each step multiplies by lrelu' of the
+    map it arrives at), so the last step of this walk — the pool gradient for stage 4, else the entry block of stage + 1 —
+    runs without that factor.  The gradient keeps the padded layout as under `want_dx`; parameter gradients met on the way are
+    dropped and never accumulated (`allow_direct=False`).  `encoder_backward` is not involved and does not change."""
+    if stage not in (1, 2, 3, 4):
+        raise ValueError(f"stage must be 1..4, got {stage!r}")
+    stages = net.stages()
+    wfc = net.fc.weight.detach()
+    top = saved["blocks"][-1][2]
+    if stage == 4:
+        return ops.avgpool_fc_bwd_data(dfeats.contiguous(), wfc, saved["pooled"], top, masked=False)
+    bw = _Backward(net, saved, dtype, False, True)
+    bw.bare_input = stages[stage][0]
+    dz = ops.avgpool_fc_bwd_data(dfeats.contiguous(), wfc, saved["pooled"], top)
+    with bw.reductions(dfeats.device):
+        for above in reversed(stages[stage:]):
+            dz = _stage_backward(bw, above, dz)
+    bw.join()
+    if _is_dense(dz, STAGE_WIDTHS[stage - 1]):
+        raise RuntimeError("a stage's gradient is returned in the padded layout")
+    return dz
 
 
 class _EncoderFn(torch.autograd.Function):

@@ -1,0 +1,119 @@
+"""Grad-CAM of a slide's tiles: which region of each tile drove the bag's class, at the resolution of a convolutional stage.
+
+The other method of the saliency toolkit the reference vendors (pytorch-cnn-visualizations-master/src: `gradcam.py`).  With the
+stock PyTorch model it takes a forward hook and a tensor hook on the target layer; here the stage's output is already kept by
+the forward (`saved["blocks"]`), its gradient is the hand-written backward chain cut short (`encoder_stage_gradient`: for
+`layer4` one pool-gradient launch, no convolution backward at all) and one kernel per bag turns the two into the toolkit's maps
+(`ops.grad_cam`, csrc/grad_cam.hip).  `TileSaliency` resolves pixels through a whole encoder backward; this costs a forward.
+"""
+import torch
+
+from . import _lib as L
+from . import ops
+from .encoder import STAGE_WIDTHS, ResNet, encoder_forward, encoder_stage_gradient
+from .head import BagLayout, head_apply
+from .preprocess import S2dTiles, U8Tiles
+
+LAYERS = ("layer1", "layer2", "layer3", "layer4")
+NORMALIZE = ("tile", "bag")
+
+
+class TileGradCam:
+    """`TileGradCam(model, layer="layer4")` for a `mil_amd.Attention` with the narrow ResNet-26.  The bag is evaluated as the
+    reference's `visualize()` evaluates a slide — eval mode: all tiles, no dropout — for the class `label`:
+
+      raw(tiles, label, offset=1.0)                   -> fp32 [T,h,w]: max(offset + sum_k w_k A_k, 0) at the stage's resolution,
+                                                         w_k the tile's mean gradient of channel k (gradcam.py:75-84;
+                                                         offset = 1.0 is the toolkit's `np.ones`)
+      maps(tiles, label, offset=1.0, normalize="tile") -> uint8 [T,H,W]: min-max normalised, quantised and resized to the tile
+                                                         with Pillow's LANCZOS filter, bit for bit what numpy and Pillow make of
+                                                         `raw` (gradcam.py:85-89) — the toolkit's bytes before its final `/255`.
+                                                         normalize="bag": one range for all tiles of the bag (their common
+                                                         minimum and maximum, taken on the device) instead of each tile's own,
+                                                         which keeps the tiles of a slide comparable
+
+    The class evidence is MINUS the bag's loss for `label`: the head's backward kernel differentiates the loss only, so the
+    gradient used is -d loss / d features.  The toolkit back-propagates the raw logit of the class; the two differ by the
+    soft-max's derivative (and the head's other loss terms), and the sign is what the ReLU sees: a region that lowers the loss
+    for `label` is positive evidence.
+    Maps of non-square tiles are [H,W] (the toolkit's own `resize((shape[2], shape[3]))` swaps the two; not copied).
+
+    `tiles`: what the encoder takes — an fp32 [T,3,H,W] stack, `U8Tiles`, or in the bf16 mode `S2dTiles`.  A call leaves the
+    model as it found it: the `training` flag is not touched, no parameter's `.grad` is created or changed, the torch RNG is not
+    drawn from and `direct_grad` accumulation is not triggered."""
+
+    def __init__(self, model, layer="layer4"):
+        from .model import Attention
+        if not isinstance(model, Attention):
+            raise ValueError("TileGradCam takes a mil_amd.Attention model")
+        if not isinstance(model.cnn.module, ResNet):
+            raise ValueError("TileGradCam needs the narrow ResNet-26 encoder: the wide encoder (alt_resnet) has no stage-gradient path")
+        if layer not in LAYERS:
+            raise ValueError(f"layer must be one of {LAYERS}, got {layer!r}")
+        self.model = model
+        self.layer = layer
+        self.stage = LAYERS.index(layer) + 1
+
+    def _check(self, tiles, label):
+        if not isinstance(tiles, (torch.Tensor, U8Tiles, S2dTiles)):
+            raise ValueError(f"tiles must be an fp32 [T,3,H,W] tensor, U8Tiles or S2dTiles, got {type(tiles).__name__}")
+        if tiles.dim() != 4 or tiles.shape[1] != 3:
+            raise ValueError(f"expected [T,3,H,W] tiles, got {tuple(tiles.shape)}")
+        if isinstance(tiles, torch.Tensor) and not tiles.is_floating_point():
+            raise ValueError(f"a tensor of tiles must be floating point (wrap uint8 images in U8Tiles), got {tiles.dtype}")
+        if isinstance(tiles, S2dTiles) and self.model.cnn.module.compute_dtype != torch.bfloat16:
+            raise ValueError("S2dTiles feed the bf16 compute mode only")
+        if tiles.shape[0] < 1:
+            raise ValueError("an empty bag has no class activation map")
+        label = int(label)
+        if not 0 <= label < self.model.C:
+            raise ValueError(f"label must be in [0, {self.model.C}), got {label}")
+        return label
+
+    def _stage_tensors(self, tiles, label):
+        """(the stage's output, the gradient of minus the loss with respect to it, its real channels, the tiles' (H, W))."""
+        model = self.model
+        net = model.cnn.module
+        dev = model.weight_mask.device
+        if dev.type != "cuda":
+            raise RuntimeError("Attention runs on an AMD GPU only (module parameters are not on a CUDA/HIP device)")
+        if isinstance(tiles, U8Tiles):
+            x = tiles.u8.to(dev)
+        elif isinstance(tiles, S2dTiles):
+            x = tiles.xs.detach().to(dev)
+        else:
+            x = tiles.detach().to(dev, torch.float32)
+        mode = net.compute_dtype
+        dtype = L.storage_dtype(mode)
+        layout = BagLayout.cached([x.shape[0]], dev)
+        y = torch.tensor([label], dtype=torch.long, device=dev)
+        cw = model.loss.weight
+        if cw is not None:
+            cw = torch.as_tensor(cw, dtype=torch.float32, device=dev).contiguous()
+        first, blks = net.stages()[self.stage - 1]
+        with L.f32_mma(L.mma_code(mode)):
+            with torch.no_grad():
+                feats, saved = encoder_forward(net, x, dtype)
+            H = feats.detach().requires_grad_()
+            loss = head_apply(H, layout, y, None, cw, [w.detach() for w in model.head_weights()], None, direct=False)[0]
+            (dH,) = torch.autograd.grad(loss.sum(), H)
+            with torch.no_grad():
+                grad = encoder_stage_gradient(net, saved, -dH, dtype, self.stage)
+        act = saved["blocks"][first + len(blks) - 1][2]
+        return act, grad, STAGE_WIDTHS[self.stage - 1], saved["tile_hw"]
+
+    def raw(self, tiles, label, offset=1.0):
+        label = self._check(tiles, label)
+        act, grad, c, hw = self._stage_tensors(tiles, label)
+        return ops.grad_cam(act, grad, c, hw, offset=offset, want_map=False)[0]
+
+    def maps(self, tiles, label, offset=1.0, normalize="tile"):
+        if normalize not in NORMALIZE:
+            raise ValueError(f"normalize must be one of {NORMALIZE}, got {normalize!r}")
+        label = self._check(tiles, label)
+        act, grad, c, hw = self._stage_tensors(tiles, label)
+        if normalize == "tile":
+            return ops.grad_cam(act, grad, c, hw, offset=offset, want_raw=False)[1]
+        raw = ops.grad_cam(act, grad, c, hw, offset=offset, want_map=False)[0]
+        rng = torch.stack((raw.amin(), raw.amax()))
+        return ops.grad_cam(act, grad, c, hw, offset=offset, value_range=rng, want_raw=False)[1]

@@ -647,6 +647,58 @@ def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None):
     return dx, sal
 
 
+_RESAMPLE_TABLES = {}
+
+
+def resample_tables(in_size, out_size, filt, device):
+    """(ksize, bounds [out,2], kk [out,ksize]) of `mil_resample_coeffs`: int32 tensors on `device` (any device: the tables
+    are made on the host), cached per (sizes, filter, device)."""
+    key = (int(in_size), int(out_size), int(filt), torch.device(device))
+    got = _RESAMPLE_TABLES.get(key)
+    if got is None:
+        ks = ctypes.c_int(0)
+        L.check(L.lib().mil_resample_plan(key[0], key[1], key[2], ctypes.byref(ks)), "mil_resample_plan")
+        bounds = torch.empty((key[1], 2), dtype=torch.int32)
+        kk = torch.empty((key[1], ks.value), dtype=torch.int32)
+        L.check(L.lib().mil_resample_coeffs(key[0], key[1], key[2], bounds.data_ptr(), kk.data_ptr()), "mil_resample_coeffs")
+        got = _RESAMPLE_TABLES[key] = (ks.value, bounds.to(key[3]), kk.to(key[3]))
+    return got
+
+
+def grad_cam(act, grad, c, tile_hw, *, offset=1.0, value_range=None, want_raw=True, want_map=True):
+    """Grad-CAM maps of n tiles (see mil_grad_cam): act, grad [n,h,w,cs] — a stage's output and the gradient of the class
+    evidence with respect to it, bf16 or fp32, c real channels — -> (raw [n,h,w] fp32, out [n,H,W] uint8) for tiles of
+    tile_hw = (H, W); None for the one not wanted.  value_range: a device fp32 tensor (lo, hi) that replaces every tile's own
+    minimum and maximum in the normalisation.  The Lanczos tables are cached per (h, H, w, W, device)."""
+    if act.dim() != 4 or act.shape != grad.shape or act.dtype != grad.dtype:
+        raise ValueError(f"act and grad must be two [n,h,w,cs] tensors of one dtype, got {tuple(act.shape)} {act.dtype} and "
+                         f"{tuple(grad.shape)} {grad.dtype}")
+    if not (want_raw or want_map):
+        raise ValueError("neither raw nor the map is wanted")
+    n, h, w, cs = act.shape
+    hh, ww = (int(v) for v in tile_hw)
+    code = L.dt_code(act.dtype)
+    _need(act, act.shape, act.dtype, "act")
+    _need(grad, act.shape, act.dtype, "grad")
+    if not 1 <= c <= cs or cs % 8:
+        raise ValueError(f"{c} real channels of {cs} stored (a multiple of 8)")
+    if h < 1 or w < 1 or hh < 1 or ww < 1:
+        raise ValueError(f"maps of {h}x{w} for tiles of {hh}x{ww}")
+    _need(value_range, (2,), torch.float32, "value_range")
+    dev = act.device
+    raw = torch.empty((n, h, w), dtype=torch.float32, device=dev) if want_raw else None
+    out = yb = yk = xb = xk = None
+    yks = xks = 0
+    if want_map:
+        out = torch.empty((n, hh, ww), dtype=torch.uint8, device=dev)
+        yks, yb, yk = resample_tables(h, hh, L.FILTER_LANCZOS, dev)
+        xks, xb, xk = resample_tables(w, ww, L.FILTER_LANCZOS, dev)
+    _launch("mil_grad_cam", ("grad_cam", n, h, w, cs, hh, ww, want_map), act.data_ptr(), grad.data_ptr(), n, h, w, c, cs, code,
+            float(offset), L.ptr(value_range), L.ptr(yb), L.ptr(yk), yks, L.ptr(xb), L.ptr(xk), xks, L.ptr(raw), L.ptr(out), hh, ww,
+            L.stream_ptr())
+    return raw, out
+
+
 def avgpool_fc_fwd(x, wfc, c, bias=None):
     n, h, w, cp = x.shape
     nf = wfc.shape[0]
@@ -657,6 +709,23 @@ def avgpool_fc_fwd(x, wfc, c, bias=None):
     L.check(L.lib().mil_avgpool_fc_fwd(x.data_ptr(), wfc.data_ptr(), L.ptr(bias), pooled.data_ptr(), feats.data_ptr(), n,
                                        h * w, cp, c, nf, L.dt_code(x.dtype), L.stream_ptr()), "mil_avgpool_fc_fwd")
     return pooled, feats
+
+
+def avgpool_fc_bwd_data(dfeats, wfc, pooled, act, masked=True, slope=LEAK):
+    """The data half of `avgpool_fc_bwd` alone: dz [n,h,w,cp] = (dfeats @ wfc) / (h w), times lrelu'(act) when `masked` — the
+    gradient of the pre-activation map the backward chain carries; masked=False: the gradient of `act` itself, the stage's
+    OUTPUT, which is what Grad-CAM reads.  No parameter gradient is computed."""
+    n, h, w, cp = act.shape
+    nf, c = wfc.shape
+    _need(dfeats, (n, nf), torch.float32, "dfeats")
+    _need(wfc, (nf, c), torch.float32, "fc.weight")
+    _need(act, act.shape, act.dtype, "act")
+    dz = torch.empty_like(act)
+    _need(pooled, (n, c), torch.float32, "pooled")        # (read by the weight-gradient half only, which a null dwfc leaves out)
+    L.check(L.lib().mil_avgpool_fc_bwd(dfeats.data_ptr(), wfc.data_ptr(), pooled.data_ptr(), act.data_ptr() if masked else None,
+                                       dz.data_ptr(), None, None, n, h * w, cp, c, nf, 0, slope, L.dt_code(act.dtype),
+                                       L.stream_ptr()), "mil_avgpool_fc_bwd")
+    return dz
 
 
 def avgpool_fc_bwd(dfeats, wfc, pooled, act, c, slope=LEAK, out=None, want_bias=False, out_bias=None):

@@ -186,6 +186,15 @@ int mil_maxpool_bwd(const void* gy, const uint8_t* widx, void* gx, int n, int H,
  * vflip) drawn by the caller (top/left in [0, 2*pad]) or null for the flat chain. */
 int mil_resize_plan(int in_size, int out_size, int* ksize);
 int mil_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk);
+/* The same tables for either of Pillow's filters: MIL_FILTER_BILINEAR (the triangle, support 1: exactly mil_resize_plan /
+ * mil_resize_coeffs) or MIL_FILTER_LANCZOS (w(x) = sinc(x) sinc(x/3) on [-3, 3), sinc(0) = 1, support 3 max(scale, 1): what
+ * Image.resize(..., Image.LANCZOS) — the toolkit's ANTIALIAS — builds).  Normalised in double, rounded to 22 bits as
+ * (int)(+-0.5 + k 2^22) with the sign of k: Lanczos coefficients can be negative.  Same layout: bounds [out*2] = (first source
+ * index, count), kk [out*ksize].  HOST functions.  Sizes below 1, another filter or a null pointer: MIL_ERR_ARG. */
+#define MIL_FILTER_LANCZOS 1  /* the values of Pillow's Image.LANCZOS / Image.BILINEAR */
+#define MIL_FILTER_BILINEAR 2
+int mil_resample_plan(int in_size, int out_size, int filter, int* ksize);
+int mil_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk);
 int mil_tile_preprocess(const uint8_t* rois, const int32_t* params, const int32_t* bounds_host, const int32_t* bounds_dev,
                         const int32_t* kk_dev, float* out, int T, int S, int pad, int R, void* stream);
 /* Same chain, output as the bf16 space-to-depth NHWC tensor xs [T,R/2,R/2,16] (channel = c*4 + dy*2 + dx, 12 real, 4 zero)
@@ -438,6 +447,30 @@ int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, const uint8_t
  * host before any GPU call. */
 int mil_stem_dgrad(const void* dstem, const void* wpack, float* dx_nchw, float* sal, int n, int H, int W, int reduce, int dtype,
                    void* stream);
+
+/* Grad-CAM per tile: the post-processing of `gradcam.py:75-89` of the same toolkit (pytorch-cnn-visualizations-master/src), from
+ * the output of a convolutional stage and the gradient of the class evidence with respect to it to the bytes the toolkit draws
+ * over the tile.  act, grad [n,h,w,cs] (bf16 under MIL_DT_BF16, fp32 under MIL_DT_F32 / MIL_DT_F32S; c real channels of cs
+ * stored, cs a multiple of 8; channels c..cs-1 are never used, whatever they hold).  Per tile t:
+ *     w_k        = (sum over the pixels of grad[t,.,.,k]) / (h w)
+ *     raw[t,i,j] = max(offset + sum_k w_k act[t,i,j,k], 0)        fp32 accumulation; offset = 1.0 is the toolkit's np.ones
+ * raw (nullable) [n,h,w] fp32 receives it.  With out (nullable) [n,H,W] uint8 the call goes on:
+ *     (mn, mx)   = the tile's own minimum and maximum of raw — or range[0], range[1] (range: a DEVICE float[2], nullable; raw is
+ *                  clamped into it for the quantisation, the stored raw is not); range[0] <= range[1]
+ *     q          = (uint8)(((raw - mn) / (mx - mn)) * 255.0f), IEEE fp32 with the correctly rounded division, truncated toward
+ *                  zero as np.uint8 truncates; a constant tile (mx == mn), where the toolkit divides by zero, is all zeros
+ *     out[t]     = q [h,w] resized to [H,W] by Pillow's two 8-bit passes (horizontal to uint8, then vertical to uint8; each from
+ *                  1 << 21, int32 accumulation, arithmetic shift by 22, clamp to [0,255]; a pass whose sizes are equal is skipped)
+ * with ybounds/ykk and xbounds/xkk the DEVICE copies of mil_resample_coeffs(h, H, MIL_FILTER_LANCZOS) and (w, W, ...), yksize /
+ * xksize what mil_resample_plan returns for them.  out is bit for bit what numpy and Pillow make of the same fp32 raw.
+ * One workgroup per tile, everything between the two tensors and the bytes in LDS; no atomics, no workspace: bit-repeatable.
+ * Null act / grad, both outputs null, out without its four tables, n < 0, h, w, H or W < 1, c < 1, c > cs, cs % 8 != 0, a ksize
+ * that is not mil_resample_plan's, another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch; a tile whose maps, strip and tables
+ * exceed the 160 KB of LDS (the largest supported: 128x128 -> 512x512), more than 256 16-byte pieces per pixel, one tile's tensor
+ * of 2 GiB or more, act / grad off the 16-byte grid: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+int mil_grad_cam(const void* act, const void* grad, int n, int h, int w, int c, int cs, int dtype, float offset,
+                 const float* range, const int32_t* ybounds, const int32_t* ykk, int yksize, const int32_t* xbounds,
+                 const int32_t* xkk, int xksize, float* raw, uint8_t* out, int H, int W, void* stream);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten + Linear(80,L,bias=False) (gbm/model.py:31-32,58-60).
  * x [n,hw,cp] -> pooled [n,c] fp32 (kept for backward), feats [n,nf] fp32 = pooled @ wfc^T (+ bias when given:
