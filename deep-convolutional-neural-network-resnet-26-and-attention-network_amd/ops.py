@@ -729,6 +729,10 @@ def avgpool_fc_bwd_data(dfeats, wfc, pooled, act, masked=True, slope=LEAK):
 
 
 def avgpool_fc_bwd(dfeats, wfc, pooled, act, c, slope=LEAK, out=None, want_bias=False, out_bias=None):
+    """`out` / `out_bias` given: the parameter gradients are ADDED to them (one accumulate flag for both, so with `want_bias` they
+    come together or not at all); otherwise fresh tensors are returned."""
+    if want_bias and (out is None) != (out_bias is None):
+        raise ValueError("avgpool_fc_bwd: with want_bias, give both out and out_bias (accumulate into both) or neither")
     n, h, w, cp = act.shape
     nf = wfc.shape[0]
     _need(dfeats, (n, nf), torch.float32, "dfeats")

@@ -317,6 +317,29 @@ def test_flat_adam_matches_torch_adam(golden_dir):
     assert torch.allclose(a["Mterm"], b["Mterm"], rtol=1e-6, atol=1e-7)
 
 
+def test_flat_adam_weight_decay_and_grad_scale_match_torch_adam(golden_dir):
+    """FlatAdam(weight_decay=0.01).step(grad_scale=0.5), as the training loop scales accumulated bags, == fp64
+    torch.optim.Adam(weight_decay=0.01) fed the same gradients halved, for three steps."""
+    import mil_amd
+    g = np.load(os.path.join(golden_dir, "eval_n8_64.npz"))
+    x, y = torch.tensor(g["x"]).cuda(), torch.tensor(g["y"]).cuda()
+    net = _model(golden_dir, torch.float32).eval()
+    flat = mil_amd.FlatParams(net)
+    opt = mil_amd.FlatAdam(flat, weight_decay=0.01)
+    ref_params = [p.detach().double().cpu().requires_grad_(True) for p in net.parameters()]
+    ref_opt = torch.optim.Adam(ref_params, lr=opt.lr, betas=opt.betas, eps=opt.eps, weight_decay=0.01)
+    for _ in range(3):
+        flat.zero_grad()
+        net(x, y)["loss"].backward()
+        for rp, p in zip(ref_params, net.parameters()):
+            rp.grad = p.grad.detach().double().cpu() * 0.5
+        opt.step(grad_scale=0.5)
+        ref_opt.step()
+        for rp, p in zip(ref_params, net.parameters()):
+            assert torch.allclose(p.detach().double().cpu(), rp.detach(), rtol=1e-5, atol=1e-7)
+    assert opt.t == 3
+
+
 def test_benchmark_sized_launch_properties(golden_dir, monkeypatch):
     """Size-independent checks at a launch size that takes the persistent kernels on its own (2 bags x 256 tiles
     @256x256, default tile-count threshold): every attention map sums to 1; features of a tile do not depend on
