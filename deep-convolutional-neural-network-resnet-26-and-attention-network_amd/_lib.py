@@ -87,6 +87,8 @@ _SIGS = {
     "mil_conv_wgrad_pair_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i, _i, _i, _i, _i], _i),
     "mil_conv_wgrad_pair": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_conv_dgrad_s2": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
+    "mil_conv_entry_bwd_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i, _i, _i, _i, _i], _i),
+    "mil_conv_entry_bwd": ([_vp] * 9 + [_sz] + [_i] * 8 + [_f, _i, _i, _vp], _i),
     "mil_stem_fwd_fused": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_stem_bwd_fused_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_stem_bwd_fused": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),

@@ -234,9 +234,9 @@ __device__ __forceinline__ void mil_poison_static(unsigned* w, unsigned words) {
 #define MIL_POISON_STATIC(arr) ((void)0)
 #endif
 
-// The only environment the library reads: five TEST knobs that drive small inputs through the large-launch paths, read on
+// The only environment the library reads: six TEST knobs that drive small inputs through the large-launch paths, read on
 // every call so that a test can set them in the middle of a process (MIL_PF_MIN_TILES, MIL_BUFFER_LIMIT_BYTES,
-// MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK; see include/mil_hip.h).
+// MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK, MIL_ENTRY_BWD; see include/mil_hip.h).
 #include <cstdlib>
 __host__ inline const char* mil_test_knob(const char* name) { return getenv(name); }
 

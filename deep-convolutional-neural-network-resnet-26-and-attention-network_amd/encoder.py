@@ -556,6 +556,15 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
     mask = xin if bi > 0 and bi != bw.bare_input else None
     pair = None
     if s == 2 and net.fuse_backward and not net.overlap_wgrad:
+        # data gradient and both weight gradients in one launch, where there is such a kernel (bf16, the 20 -> 40 and 40 -> 60
+        # entries): the same bits as the two launches below
+        ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
+        dense_cx = cin if _first_stage_dense(bw, bi) else None
+        one = bw.workspace("p", bi, None, ops.conv_entry_bwd, dz1, dz, ws2, xin, cin, cout, masked=mask is not None, dense_cx=dense_cx,
+                           out=bw.out(conv.weight, conv.bias, proj.weight))
+        if one is not None:
+            bw.grads[bi, 1], bw.grads[bi, 0] = one[1:3], (one[3], None)
+            return one[0]
         # both weight gradients of the stage-entry convs from one pass over the block input
         pair = bw.workspace("p", bi, None, ops.conv_wgrad_pair, xin, dz1, dz, cin, cout, out=bw.out(conv.weight, conv.bias, proj.weight))
     if pair is not None:

@@ -389,6 +389,36 @@ def conv_dgrad_s2(dz1, dz2, wpack, cx_p, out_hw, *, act=None, slope=LEAK, dense_
     return y
 
 
+def conv_entry_bwd(dz1, dz2, wpack, xin, cin, cout, *, masked=True, slope=LEAK, dense_cx=None, workspace=None, out=None):
+    """(dx, dW3, db3, dW1) of a stage-entry block's two stride-2 convs in one launch (see mil_conv_entry_bwd): dx as
+    conv_dgrad_s2 computes it (act = xin when masked) and the weight gradients as conv_wgrad_pair computes them, all bit for
+    bit — or None when the shape/dtype has no such kernel.  out = (dw3, db3, dw1) accumulates in place; dense_cx as in
+    conv_dgrad_s2."""
+    n, h, w, _ = dz1.shape
+    _, hh, ww, _ = xin.shape
+    if dz1.dtype != torch.bfloat16:
+        return None
+    dense = dense_cx is not None
+    code = L.dt_code(dz1.dtype, dense, mma=True)
+    _need(dz1, (n, h, w, cpad(cout)), dz1.dtype, "dz1")
+    _need(dz2, (n, h, w, cpad(cout)), dz1.dtype, "dz2")
+    _need(xin, (n, hh, ww, cpad(cin)), dz1.dtype, "xin")
+    need = ctypes.c_size_t(0)
+    rc = L.lib().mil_conv_entry_bwd_workspace(ctypes.byref(need), n, h, w, cout, hh, ww, cin, code)
+    if rc == 2:
+        return None
+    L.check(rc, "mil_conv_entry_bwd_workspace")
+    workspace = workspace_for(workspace, need.value, dz1.device)
+    dx = torch.empty((n, hh, ww, dense_cx if dense else cpad(cin)), dtype=dz1.dtype, device=dz1.device)
+    (dw3, db3, dw1), accumulate = _grad_out(out, (((cout, cin, 3, 3), "dw3"), ((cout,), "db3"), ((cout, cin, 1, 1), "dw1")), dz1.device)
+    if not _launch("mil_conv_entry_bwd", ("entry_bwd", cpad(cout), cpad(cin), n, hh, ww),
+                   dz1.data_ptr(), dz2.data_ptr(), wpack.data_ptr(), xin.data_ptr(), dx.data_ptr(), dw3.data_ptr(),
+                   db3.data_ptr(), dw1.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                   n, h, w, cout, hh, ww, cin, 1 if masked else 0, slope, accumulate, code, L.stream_ptr(), missing_ok=True):
+        return None
+    return dx, dw3, db3, dw1, workspace
+
+
 # ---- the stem: one description per feed ---------------------------------------------------------------------
 # The tiles reach the stem as fp32 [n,3,H,W] ("f32"), as the uint8 images they are ("u8", preprocess.U8Tiles) or as the bf16
 # space-to-depth tensor [n,H/2,W/2,16] ("s2d", preprocess.S2dTiles).  The kernels are one template family

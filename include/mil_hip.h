@@ -11,8 +11,9 @@
  *   - plain C: raw device pointers, ints, floats; `stream` is a hipStream_t passed as void*.
  *   - every function returns MIL_OK (0) or an error code; nothing allocates, nothing synchronises,
  *     no global state: work is enqueued on `stream`, buffers are caller-owned.
- *   - the only environment read: five test knobs, on every call (MIL_PF_MIN_TILES, MIL_BUFFER_LIMIT_BYTES,
- *     MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK), with which tests drive small inputs through the large-launch paths.
+ *   - the only environment read: six test knobs, on every call (MIL_PF_MIN_TILES, MIL_BUFFER_LIMIT_BYTES,
+ *     MIL_RES_GRID_CAP, MIL_BLOCK_STRIP, MIL_STEM_WALK, MIL_ENTRY_BWD), with which tests drive small inputs through the
+ *     large-launch paths and force either of two equivalent kernels.
  *   - activations are NHWC with channels padded to a multiple of 8 (20->24, 40, 60->64, 80; padded
  *     channels hold zeros); `dtype` selects the activation/weight-operand type:
  *         MIL_DT_F32  (0): exact-fp32 MFMA (v_mfma_f32_16x16x4_f32)  — the parity gate, bit-level
@@ -363,6 +364,22 @@ int mil_conv_wgrad_pair(const void* x, const void* dz1, const void* dz2, float* 
  * mil_conv_igemm calls with zero_insert). */
 int mil_conv_dgrad_s2(const void* dz1, const void* dz2, const void* wpack, const void* act, void* y, int n_img,
                       int h, int w, int cz_p, int H, int W, int cx_p, float slope, int dtype, void* stream);
+
+/* Backward of a stage-entry block's two stride-2 convs in ONE launch (bf16 path): the data gradient of mil_conv_dgrad_s2 and
+ * the weight gradients of mil_conv_wgrad_pair from one pass over dz1, dz2 and the block input,
+ *   dx  = lrelu'(xin) * ( conv3x3_s2^T(dz1) + conv1x1_s2^T(dz2) )        (masked = 0: no lrelu' factor)
+ *   dw3 [cout,cin,3,3], db3 [cout] from (xin, dz1);   dw1 [cout,cin,1,1] from (xin, dz2)
+ * Every result is bit-identical to those two entry points': dx by the same parity-class arithmetic; the weight gradients because
+ * the kernel sums the same dz tiles on the same workgroups in the same k-step order as mil_conv_wgrad_pair's kernel and ends in
+ * the same two fixed-order slab reductions (deferrable: mil_reduce_defer_begin).  wpack: MIL_PACK_DGRAD_S2 fragments, as for
+ * mil_conv_dgrad_s2; dz1/dz2 [n,h,w,cpad(cout)], xin and dx [n,H,W,cpad(cin)] (MIL_DT_BF16_DGRAD: dx [n,H,W,20]), h = (H-1)/2+1.
+ * bf16; (cin,cout) = (40,60) on maps with a side above 8 pixels, (20,40) above 16; everything else MIL_ERR_UNSUPPORTED (caller:
+ * mil_conv_wgrad_pair + mil_conv_dgrad_s2).  MIL_ENTRY_BWD=0 (a test knob) turns it off; MIL_RES_GRID_CAP caps its grid
+ * (the sums then take another order). */
+int mil_conv_entry_bwd_workspace(size_t* bytes, int n_img, int h, int w, int cout, int H, int W, int cin, int dtype);
+int mil_conv_entry_bwd(const void* dz1, const void* dz2, const void* wpack, const void* xin, void* dx, float* dw3,
+                       float* db3, float* dw1, void* workspace, size_t workspace_bytes, int n_img, int h, int w,
+                       int cout, int H, int W, int cin, int masked, float slope, int accumulate, int dtype, void* stream);
 
 /* Fused forward of the whole stem (bf16 path): space-to-depth + Conv2d(3,C,7,2,3) + bias + LeakyReLU +
  * MaxPool2d(3,2,1) in one pass over the fp32 NCHW tiles (gbm/model.py:24-26,51-53; alt_resnet.py:81-84,128-131
