@@ -68,12 +68,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((T::SPLIT && CINP <= 24 && NT <
     constexpr int COUTP = mil_nt_to_cp(NT);
     constexpr int PIXZ = mil_pix_pitch(COUTP, ESZ);
     constexpr int CG = CINP / 8;
-    constexpr int RG = KS * KS * CG;            // row groups of 8 input channels
-    constexpr int MT = (RG + 1) / 2;            // 16-row MFMA tiles over (tap, ci)
+    using Slab = MilWgradSlab<KS, CINP, NT, PROJ>;
+    constexpr int RG = Slab::RG;                // row groups of 8 input channels
+    constexpr int MT = Slab::MT;                // 16-row MFMA tiles over (tap, ci)
     constexpr int MT_S = (MT + MSPLIT - 1) / MSPLIT;
     constexpr int NTHR = 64 * NW;
     constexpr int MW = (MT_S + NW - 1) / NW;    // tiles per wave
-    constexpr int PM0 = 2 * CG, PM1 = (5 * CG - 1) / 2, PMN = PROJ ? PM1 - PM0 + 1 : 0;    // row tiles holding centre-tap rows
     // the explicit one-step-ahead operand prefetch (second operand register set): the persistent bf16 forms below 64 input
     // channels; the 64/80-channel forms sit at 232-256 VGPRs already
     constexpr bool WPIPE = T::DT == MIL_DT_BF16 && PF && CINP < 64;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((T::SPLIT && CINP <= 24 && NT <
         const int ml = wave + NW * i;
         const int mt = split * MT_S + ml;
         mvalid[i] = (ml < MT_S) && (mt < MT);
-        if (PROJ && mvalid[i] && mt >= PM0 && mt <= PM1) { proj_i = i; proj_mt = mt; }
+        if (mvalid[i] && Slab::feeds_proj(mt)) { proj_i = i; proj_mt = mt; }
         int rg, sub;
         if constexpr (T::TR16) { const int p = lane & 3; rg = 2 * mt + (p >> 1); sub = (p & 1) * 8; }
         else { const int row = lane & 15; rg = 2 * mt + (row >> 3); sub = (row & 7) * 4; }
@@ -354,45 +354,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? ((T::SPLIT && CINP <= 24 && NT <
     }
     MIL_STAMP_STORE(a.stamp, NW)
 
-    // one slab per workgroup column; row = (tap*CINP + ci), col = co; bias sums live in tile MT
-    constexpr int SLAB_COLS = NT * 16;
-    constexpr size_t SLAB_ELEMS = (size_t)(MT + 1 + PMN) * 16 * SLAB_COLS;
-    float* slab = a.slab + (size_t)blockIdx.x * SLAB_ELEMS;
-    const int gq = lane >> 4, col = lane & 15;
+    // one slab per workgroup column (layout: MilWgradSlab)
+    float* slab = a.slab + (size_t)blockIdx.x * Slab::ELEMS;
     // ZFOLD: columns 8-15 of the last column tile (the dz_lo products) onto columns 0-7
     auto unfold = [&](float v, int nt) {
         if (ZFOLD && nt == NT - 1) {
             const float up = __shfl_down(v, 8, 16);
-            return col < 8 ? v + up : 0.f;
+            return (lane & 15) < 8 ? v + up : 0.f;
         }
         return v;
     };
     if constexpr (PROJ) {
-        if (proj_i >= 0) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    slab[(size_t)((MT + 1 + proj_mt - PM0) * 16 + gq * 4 + e) * SLAB_COLS + nt * 16 + col] = unfold(accp[nt][e], nt);
-        }
+        if (proj_i >= 0) Slab::store(slab, Slab::proj_tile(proj_mt), accp, lane, unfold);
     }
 #pragma unroll
-    for (int i = 0; i < MW; ++i) {
-        if (!mvalid[i]) continue;
-        const int mt = split * MT_S + wave + NW * i;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                slab[(size_t)(mt * 16 + gq * 4 + e) * SLAB_COLS + nt * 16 + col] = unfold(acc[i][nt][e], nt);
-    }
-    if (bias_wave) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                slab[(size_t)(MT * 16 + gq * 4 + e) * SLAB_COLS + nt * 16 + col] = unfold(accb[nt][e], nt);
-    }
+    for (int i = 0; i < MW; ++i)
+        if (mvalid[i]) Slab::store(slab, split * MT_S + wave + NW * i, acc[i], lane, unfold);
+    if (bias_wave) Slab::store(slab, Slab::BIAS_TILE, accb, lane, unfold);
 }
 
 // The slab reductions themselves live in reduce.cuh (shared with conv_bwd_fused.hip and the batched launch).
@@ -460,15 +438,13 @@ extern "C" int mil_wgrad_reduce_all(const void* jobs_dev, const void* jobs_host,
 }
 
 // ---------------------------------------------------------------------------------------------
-struct WgradPlan { int grid_x; int msplit; size_t slab_elems; int slab_cols; int mt; int lds; int tile_px_log2; };
+struct WgradPlan { int grid_x; int msplit; size_t slab_elems; int lds; int tile_px_log2; };
 
 template <typename T, int KS, int CINP, int NT, int MSPLIT>
 static int plan_wgrad(ConvGeom& g, WgradPlan& pl, int* lds_z_off, bool proj = false) {
     constexpr int ESZ = T::ESZ;
     constexpr int PIXB = mil_pix_pitch(CINP, ESZ);
     constexpr int PIXZ = mil_pix_pitch(mil_nt_to_cp(NT), ESZ);
-    constexpr int RG = KS * KS * (CINP / 8);
-    constexpr int MT = (RG + 1) / 2;
     // 256-px tiles when the halo fits comfortably, else 64-px tiles (stride-2 layers, f32 wide layers)
     constexpr bool PF_OK = T::TR16 && (!T::SPLIT || CINP < 64 || (CINP == 64 || (CINP == 80 && MSPLIT >= 3)));            // bf16, and fp32 with split-precision products: the register-prefetch pipeline
     constexpr bool HALF = mil_wgrad_x3_half(T::SPLIT, KS, CINP, NT, MSPLIT, false);
@@ -491,20 +467,16 @@ static int plan_wgrad(ConvGeom& g, WgradPlan& pl, int* lds_z_off, bool proj = fa
             break;
         }
     }
-    pl.msplit = MSPLIT; pl.mt = MT; pl.slab_cols = NT * 16;
-    {
-        constexpr int CGc = CINP / 8;
-        const int pmn = proj ? (5 * CGc - 1) / 2 - 2 * CGc + 1 : 0;
-        pl.slab_elems = (size_t)(MT + 1 + pmn) * 16 * NT * 16;
-    }
-    pl.grid_x = 0;                                           // set by run_wgrad once the kernel (and its residency) is known
+    pl.msplit = MSPLIT;
+    pl.slab_elems = proj ? MilWgradSlab<KS, CINP, NT, true>::ELEMS : MilWgradSlab<KS, CINP, NT, false>::ELEMS;
+    pl.grid_x = 0;                                          // set by run_wgrad once the kernel (and its residency) is known
     return MIL_OK;
 }
 
 template <typename T, int KS, int CINP, int NT, int MSPLIT, bool PROJ = false>
 static int run_wgrad(const void* x, const void* dz, float* dw, float* db, void* ws, size_t ws_bytes, ConvGeom g,
                      int cout, int cin, int stem_mode, int accumulate, bool query, size_t* need, hipStream_t stream,
-                     const void* dz2 = nullptr, float* dw1 = nullptr) {
+                     const void* dz2 = nullptr, float* dw1 = nullptr, MilWgradPairPlan* plan = nullptr) {
     WgradPlan pl{};
     int lds_z_off = 0;
     int rc = plan_wgrad<T, KS, CINP, NT, MSPLIT>(g, pl, &lds_z_off, PROJ);
@@ -559,7 +531,11 @@ static int run_wgrad(const void* x, const void* dz, float* dw, float* db, void* 
         pl.grid_x = gx;
     }
     const size_t bytes = pl.slab_elems * pl.grid_x * nchunk * sizeof(float);
-    if (query) { *need = bytes; return MIL_OK; }
+    if (query) {
+        *need = bytes;
+        if (plan) *plan = MilWgradPairPlan{pl.grid_x * nchunk, g.tw_log2, g.th_log2, g.ti_log2};
+        return MIL_OK;
+    }
     if (ws_bytes < bytes || !ws) return MIL_ERR_ARG;
     for (int c = 0; c < nchunk; ++c) {          // a workgroup without tiles (short last chunk) still writes its all-zero slab
         WgradArgs<T> b = a;
@@ -588,39 +564,23 @@ static int run_wgrad(const void* x, const void* dz, float* dw, float* db, void* 
         }
 #endif
     }
-    pl.grid_x *= nchunk;                         // slabs to reduce
-    const int n_rows = KS * KS * CINP;
-    {
-        MilReduceJob j{};
-        j.slab = (const float*)ws; j.nslab = pl.grid_x; j.slab_elems = pl.slab_elems; j.slab_cols = pl.slab_cols; j.n_rows = n_rows;
-        j.dw = dw; j.db = db; j.cout = cout; j.cin = cin; j.ks = KS; j.kind = 0; j.cinp = CINP; j.stem_mode = stem_mode;
-        j.bias_row = pl.mt * 16; j.accumulate = accumulate;
-        mil_reduce_or_defer(j, stream);
-        MIL_CHECK_LAUNCH();
-        if constexpr (PROJ) {        // the projection's rows sit behind the bias tile: rows = input channel, one tap
-            MilReduceJob j1 = j;
-            j1.slab = (const float*)ws + (size_t)(pl.mt + 1) * 16 * pl.slab_cols;
-            j1.n_rows = CINP; j1.dw = dw1; j1.db = nullptr; j1.ks = 1; j1.stem_mode = 0; j1.bias_row = 0;
-            mil_reduce_or_defer(j1, stream);
-            MIL_CHECK_LAUNCH();
-        }
-    }
-    return MIL_OK;
+    // slabs to reduce: one set per chunk
+    return MilWgradSlab<KS, CINP, NT, PROJ>::reduce((const float*)ws, pl.grid_x * nchunk, dw, db, dw1, cout, cin, stem_mode, accumulate, stream);
 }
 
 // 3x3/s2 conv + 1x1/s2 projection of a stage-entry block: both weight gradients from one pass over the block input.
 template <typename T>
 static int dispatch_wgrad_pair(const void* x, const void* dz1, const void* dz2, float* dw3, float* db3, float* dw1, void* ws,
                                size_t ws_bytes, const ConvGeom& g, int cout, int cin, int accumulate, bool query, size_t* need,
-                               hipStream_t st) {
+                               hipStream_t st, MilWgradPairPlan* plan = nullptr) {
     if constexpr (T::DT != MIL_DT_BF16 && T::DT != MIL_DT_F32S) return MIL_ERR_UNSUPPORTED;
     const int cinp = mil_cpad(cin), coutp = mil_cpad(cout);
     if constexpr (T::SPLIT) {                    // split precision: the 20 -> 40 channel entry (the larger ones sit at their register cap)
         if (cinp == 24 && coutp == 40)
-            return run_wgrad<T, 3, 24, 3, 1, true>(x, dz1, dw3, db3, ws, ws_bytes, g, cout, cin, 0, accumulate, query, need, st, dz2, dw1);
+            return run_wgrad<T, 3, 24, 3, 1, true>(x, dz1, dw3, db3, ws, ws_bytes, g, cout, cin, 0, accumulate, query, need, st, dz2, dw1, plan);
         return MIL_ERR_UNSUPPORTED;
     } else {
-#define MIL_WGP(CI, NTV, MS) return run_wgrad<T, 3, CI, NTV, MS, true>(x, dz1, dw3, db3, ws, ws_bytes, g, cout, cin, 0, accumulate, query, need, st, dz2, dw1)
+#define MIL_WGP(CI, NTV, MS) return run_wgrad<T, 3, CI, NTV, MS, true>(x, dz1, dw3, db3, ws, ws_bytes, g, cout, cin, 0, accumulate, query, need, st, dz2, dw1, plan)
     if (cinp == 24 && coutp == 40) MIL_WGP(24, 3, 1);
     if (cinp == 40 && coutp == 64) MIL_WGP(40, 4, 1);
     // (64 -> 80: NOT paired.  The paired instantiation spilled 59 VGPRs at its 256-register cap and measured 124 us per launch
@@ -1235,16 +1195,22 @@ extern "C" int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, co
 
 static int wgrad_pair_entry(const void* x, const void* dz1, const void* dz2, float* dw3, float* db3, float* dw1, void* ws,
                             size_t ws_bytes, int n_img, int H, int W, int cin, int Ho, int Wo, int cout, int accumulate,
-                            int dtype, bool query, size_t* need, void* stream) {
+                            int dtype, bool query, size_t* need, void* stream, MilWgradPairPlan* plan = nullptr) {
     if (n_img < 0 || H <= 0 || W <= 0 || Ho != (H - 1) / 2 + 1 || Wo != (W - 1) / 2 + 1) return MIL_ERR_ARG;
     if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32S) return MIL_ERR_UNSUPPORTED;
     ConvGeom g{};
     g.n_img = n_img; g.H = H; g.W = W; g.Ho = Ho; g.Wo = Wo; g.ks = 3; g.stride = 2; g.pad = 1; g.zins = 0;
     if (dtype == MIL_DT_F32S)
         return dispatch_wgrad_pair<F32S>(x, dz1, dz2, dw3, db3, dw1, ws, ws_bytes, g, cout, cin, accumulate, query, need,
-                                         reinterpret_cast<hipStream_t>(stream));
+                                         reinterpret_cast<hipStream_t>(stream), plan);
     return dispatch_wgrad_pair<BF16>(x, dz1, dz2, dw3, db3, dw1, ws, ws_bytes, g, cout, cin, accumulate, query, need,
-                                     reinterpret_cast<hipStream_t>(stream));
+                                     reinterpret_cast<hipStream_t>(stream), plan);
+}
+
+int mil_wgrad_pair_plan(MilWgradPairPlan* plan, int n_img, int H, int W, int cin, int Ho, int Wo, int cout) {
+    size_t bytes = 0;
+    return wgrad_pair_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n_img, H, W, cin, Ho, Wo, cout, 0,
+                            MIL_DT_BF16, true, &bytes, nullptr, plan);
 }
 
 extern "C" int mil_conv_wgrad_pair_workspace(size_t* bytes, int n_img, int H, int W, int cin, int Ho, int Wo, int cout, int dtype) {

@@ -141,3 +141,62 @@ __host__ inline void mil_reduce_or_defer(const MilReduceJob& j, hipStream_t stre
     if (may_defer && mil_try_defer(j)) return;
     mil_launch_reduce(j, stream);
 }
+
+// ---- the fp32 slab one workgroup of a conv weight-gradient kernel writes (kind 0) -------------------------------------
+// [(MT + 1 + PMN) * 16 rows][NT * 16 columns]: row = tap * CINP + ci in MT row tiles of 16, col = co; the bias sums in row
+// tile MT; PROJ (stage-entry blocks: 3x3/s2 conv + 1x1/s2 projection on one input): the projection's rows — input channel,
+// one tap — behind the bias tile, as the PMN row tiles PM0..PM1 of the 3x3 filter that hold centre-tap rows.
+// wgrad_kernel and conv_entry_bwd_kernel write it, their launchers size the workspace and record the reductions from it.
+template <int KS, int CINP, int NT, bool PROJ>
+struct MilWgradSlab {
+    static constexpr int RG = KS * KS * (CINP / 8);             // row groups of 8 input channels, two per row tile
+    static constexpr int MT = (RG + 1) / 2;
+    static constexpr int PM0 = 2 * (CINP / 8), PM1 = (5 * (CINP / 8) - 1) / 2, PMN = PROJ ? PM1 - PM0 + 1 : 0;
+    static constexpr int COLS = NT * 16;
+    static constexpr size_t ELEMS = (size_t)(MT + 1 + PMN) * 16 * COLS;
+    static constexpr int BIAS_TILE = MT;
+    __host__ __device__ static constexpr bool feeds_proj(int mt) { return PROJ && mt >= PM0 && mt <= PM1; }
+    __host__ __device__ static constexpr int proj_tile(int mt) { return MT + 1 + mt - PM0; }
+
+    // One accumulator tile (MFMA D layout: lane (gq, col) holds rows 4*gq .. +3 of column col) -> row tile t of `slab`;
+    // fix(value, nt) is applied to every element (wgrad_kernel's ZFOLD unfold).
+    template <class Fix>
+    __device__ __forceinline__ static void store(float* slab, int t, const f32x4_t (&acc)[NT], int lane, Fix fix) {
+        const int gq = lane >> 4, col = lane & 15;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                slab[(size_t)(t * 16 + gq * 4 + e) * COLS + nt * 16 + col] = fix(acc[nt][e], nt);
+    }
+    __device__ __forceinline__ static void store(float* slab, int t, const f32x4_t (&acc)[NT], int lane) {
+        store(slab, t, acc, lane, [](float v, int) { return v; });
+    }
+
+    // The reductions of `nslab` slabs at `ws`: the KSxKS filter with its bias, then (PROJ) the projection's rows.  Producers
+    // that must give the same bits record through this one function: the batched reduction's block prefix is the order
+    // and the fields of the records.
+    __host__ static int reduce(const float* ws, int nslab, float* dw, float* db, float* dw1, int cout, int cin, int stem_mode,
+                               int accumulate, hipStream_t stream) {
+        MilReduceJob j{};
+        j.slab = ws; j.nslab = nslab; j.slab_elems = ELEMS; j.slab_cols = COLS; j.n_rows = KS * KS * CINP;
+        j.dw = dw; j.db = db; j.cout = cout; j.cin = cin; j.ks = KS; j.kind = 0; j.cinp = CINP; j.stem_mode = stem_mode;
+        j.bias_row = BIAS_TILE * 16; j.accumulate = accumulate;
+        mil_reduce_or_defer(j, stream);
+        MIL_CHECK_LAUNCH();
+        if constexpr (PROJ) {
+            MilReduceJob j1 = j;
+            j1.slab = ws + (size_t)proj_tile(PM0) * 16 * COLS;
+            j1.n_rows = CINP; j1.dw = dw1; j1.db = nullptr; j1.ks = 1; j1.stem_mode = 0; j1.bias_row = 0;
+            mil_reduce_or_defer(j1, stream);
+            MIL_CHECK_LAUNCH();
+        }
+        return MIL_OK;
+    }
+};
+
+// The paired bf16 weight-gradient launch (mil_conv_wgrad_pair) of a stage entry as it would run: its workgroups (= slabs)
+// and the dz tile of a workgroup step.  conv_entry_bwd_kernel computes the same bits only on the same grid and tiles, so
+// its launcher asks instead of assuming.  x [n,H,W,cpad(cin)], dz [n,Ho,Wo,cpad(cout)].  Defined in conv_wgrad.hip.
+struct MilWgradPairPlan { int grid, tw_log2, th_log2, ti_log2; };
+int mil_wgrad_pair_plan(MilWgradPairPlan* plan, int n_img, int H, int W, int cin, int Ho, int Wo, int cout);

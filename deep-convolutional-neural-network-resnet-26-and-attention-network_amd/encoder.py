@@ -555,11 +555,16 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
     # wanted — the output of the stage below — not that of the pre-activation map behind it
     mask = xin if bi > 0 and bi != bw.bare_input else None
     pair = None
+
+    def s2_operands():
+        """The packed stride-2 filter and the dense-layout rule of the two fused data gradients below.  Asked where one of
+        them is about to run, not before: `_first_stage_dense` queries the library, and those calls keep their place."""
+        return net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)[0], (cin if _first_stage_dense(bw, bi) else None)
+
     if s == 2 and net.fuse_backward and not net.overlap_wgrad:
         # data gradient and both weight gradients in one launch, where there is such a kernel (bf16, the 20 -> 40 and 40 -> 60
         # entries): the same bits as the two launches below
-        ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
-        dense_cx = cin if _first_stage_dense(bw, bi) else None
+        ws2, dense_cx = s2_operands()
         one = bw.workspace("p", bi, None, ops.conv_entry_bwd, dz1, dz, ws2, xin, cin, cout, masked=mask is not None, dense_cx=dense_cx,
                            out=bw.out(conv.weight, conv.bias, proj.weight))
         if one is not None:
@@ -573,8 +578,7 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
         bw.wgrad(conv, xin, dz1, (bi, 1))
         bw.wgrad(proj, xin, dz, (bi, 0))
     if s == 2 and net.fuse_backward:        # both transposed convs + the mask in one pass over the compact dz maps
-        ws2, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)
-        dense_cx = cin if _first_stage_dense(bw, bi) else None
+        ws2, dense_cx = s2_operands()
         fused = ops.conv_dgrad_s2(dz1, dz, ws2, ops.cpad(cin), xin.shape[1:3], act=mask, dense_cx=dense_cx)
         if fused is not None:
             return fused
