@@ -23,6 +23,7 @@ MIL_DT_F32, MIL_DT_BF16, MIL_DT_BF16_DGRAD, MIL_DT_F32S, MIL_DT_F32S_DGRAD = 0, 
 BF16X3 = "bf16x3"
 PACK_FWD, PACK_DGRAD, PACK_STEM, PACK_DGRAD_S2, PACK_STEM_DGRAD = 0, 1, 2, 3, 4
 FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pillow's own codes)
+ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per tile in mil_attr_finish's workspace
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -97,6 +98,9 @@ _SIGS = {
     "mil_stem_bwd_fused_u8_workspace": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_stem_bwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
     "mil_stem_dgrad": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mil_stem_dgrad_acc": ([_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp], _i),
+    "mil_path_point": ([_vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _c.c_uint64, _c.c_uint32, _i, _i, _i, _vp], _i),
+    "mil_attr_finish": ([_vp, _vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
     "mil_grad_cam": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -19,12 +19,58 @@
 #define SDG_KSTEPS 12
 #define SDG_CP 24
 
+// The ACC epilogue: the eight row pieces of dx this lane owns (rows 2 (r0 + m) + dy of colour channel g, columns 2 q, 2 q + 1):
+// all loads first (they overlap), then dx = dx + scale * acc as a product and a sum, and the stores.
+__device__ __forceinline__ void sdg_acc_store(float* __restrict__ dx, const f32x4_t (&acc)[4], float scale, int img, int g, int q, int r0,
+                                              int H, int W, int H2, int W2, bool w_even) {
+#pragma clang fp contract(off)          // (HIP's __fmul_rn / __fadd_rn are plain operators that contract into an fma)
+    const int x = 2 * q;
+    const bool two = x + 1 < W;
+    float old[4][2][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int r = r0 + m;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * r + dy;
+            old[m][dy][0] = old[m][dy][1] = 0.f;
+            if (g >= 3 || r >= H2 || q >= W2 || y >= H || x >= W) continue;
+            const float* o = dx + (((size_t)img * 3 + g) * H + y) * W + x;
+            if (two && w_even) {
+                const f32x2_t v = *reinterpret_cast<const f32x2_t*>(o);
+                old[m][dy][0] = v[0]; old[m][dy][1] = v[1];
+            } else {
+                old[m][dy][0] = o[0];
+                if (two) old[m][dy][1] = o[1];
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int r = r0 + m;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * r + dy;
+            if (g >= 3 || r >= H2 || q >= W2 || y >= H || x >= W) continue;
+            float* o = dx + (((size_t)img * 3 + g) * H + y) * W + x;
+            const float v0 = old[m][dy][0] + scale * acc[m][2 * dy];
+            const float v1 = old[m][dy][1] + scale * acc[m][2 * dy + 1];
+            if (two && w_even) *reinterpret_cast<f32x2_t*>(o) = f32x2_t{v0, v1};
+            else { o[0] = v0; if (two) o[1] = v1; }
+        }
+    }
+}
+
 // bf16: three workgroups per CU (146 VGPRs, no spill; four would spill 35).  The fp32 forms hold 96 registers of filter
 // fragments and run one workgroup per SIMD set (252-254 VGPRs, no spill).
-template <typename T>
+// ACC (mil_stem_dgrad_acc: the inner step of integrated gradients and SmoothGrad): dx is a running sum
+// and the store epilogue is dx = dx + scale * (this launch's gradient), a product and a sum with contraction off; no
+// `reduce` form.  An output element belongs to one workgroup and one lane, so the read-modify-write needs no atomics.  The
+// ACC = false instantiations compile to the code they were before the parameter existed (`scale` is never read there).
+template <typename T, bool ACC = false>
 __global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_kernel(const typename T::elem* __restrict__ dstem, const void* __restrict__ wpack,
                                                          float* __restrict__ dx, float* __restrict__ sal, int H, int W, int H2,
-                                                         int W2, int tiles_x, int tiles_y, int ntiles, int reduce) {
+                                                         int W2, int tiles_x, int tiles_y, int ntiles, int reduce, float scale) {
     constexpr int ESZ = T::ESZ;
     constexpr int REC = SDG_CP * ESZ;                       // bytes of a pixel record in HBM (and of its LDS image)
     constexpr int PITCH = mil_pix_pitch(SDG_CP, ESZ);       // 48 (bf16) / 112 bytes
@@ -108,6 +154,11 @@ __global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_
         }
         // depth-to-space store: register j of lane group g is dx[img][c = g][2r + (j >> 1)][2q + (j & 1)]
         const int q = tx * SDG_TS + col;
+        if constexpr (ACC) {
+            sdg_acc_store(dx, acc, scale, img, g, q, ty * SDG_TS + wave * 4, H, W, H2, W2, w_even);
+            __syncthreads();
+            continue;
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int r = ty * SDG_TS + wave * 4 + m;
@@ -143,16 +194,16 @@ __global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_
     }
 }
 
-template <typename T>
+template <typename T, bool ACC = false>
 static int launch_stem_dgrad(const void* dstem, const void* wpack, float* dx, float* sal, int n, int H, int W, int reduce,
-                             hipStream_t st) {
+                             hipStream_t st, float scale = 0.f) {
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
     const int tiles_x = (W2 + SDG_TS - 1) / SDG_TS, tiles_y = (H2 + SDG_TS - 1) / SDG_TS;
     const long long ntiles = (long long)n * tiles_x * tiles_y;
     if (ntiles > INT_MAX || (size_t)H2 * W2 * SDG_CP * T::ESZ >= 0x80000000ull) return MIL_ERR_UNSUPPORTED;
     const int grid = (int)(ntiles < 2048 ? ntiles : 2048);
-    hipLaunchKernelGGL(stem_dgrad_kernel<T>, dim3(grid), dim3(256), 0, st, (const typename T::elem*)dstem, wpack, dx, sal, H, W,
-                       H2, W2, tiles_x, tiles_y, (int)ntiles, reduce);
+    hipLaunchKernelGGL((stem_dgrad_kernel<T, ACC>), dim3(grid), dim3(256), 0, st, (const typename T::elem*)dstem, wpack, dx, sal, H, W,
+                       H2, W2, tiles_x, tiles_y, (int)ntiles, reduce, scale);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -167,4 +218,16 @@ extern "C" int mil_stem_dgrad(const void* dstem, const void* wpack, float* dx_nc
     if (dtype == MIL_DT_BF16) return launch_stem_dgrad<BF16>(dstem, wpack, dx_nchw, sal, n, H, W, reduce, st);
     if (dtype == MIL_DT_F32) return launch_stem_dgrad<F32>(dstem, wpack, dx_nchw, sal, n, H, W, reduce, st);
     return launch_stem_dgrad<F32S>(dstem, wpack, dx_nchw, sal, n, H, W, reduce, st);
+}
+
+// acc_nchw [n,3,H,W] fp32 += scale * dx, dx what mil_stem_dgrad(reduce = 0) writes for the same arguments: include/mil_hip.h.
+extern "C" int mil_stem_dgrad_acc(const void* dstem, const void* wpack, float* acc_nchw, float scale, int n, int H, int W, int dtype,
+                                  void* stream) {
+    if (!dstem || !wpack || !acc_nchw || n < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32 && dtype != MIL_DT_F32S) return MIL_ERR_ARG;
+    if (n == 0) return MIL_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MIL_DT_BF16) return launch_stem_dgrad<BF16, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
+    if (dtype == MIL_DT_F32) return launch_stem_dgrad<F32, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
+    return launch_stem_dgrad<F32S, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
 }

@@ -660,14 +660,18 @@ def _stem_backward(bw, dz):
     return dstem
 
 
-def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False, dx_reduce=None):
+def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False, dx_reduce=None, dx_acc=None):
     """Gradients of every encoder parameter, in `encoder_params()` order.  want_dx=True: returns (those gradients, dx, sal)
     with the gradient of the tiles themselves behind the stem's weight gradient — `ops.maxpool_bwd` to the un-pooled stem
     gradient, then `ops.stem_dgrad`: dx [T,3,H,W] fp32 (dx_reduce=None), or sal [T,H,W] = max_c |dx| and dx None
-    (dx_reduce="max_abs").  The gradient chain of the 20-channel stage then keeps its padded layout (the dense one has no
+    (dx_reduce="max_abs"); dx_acc=(acc, scale) (with want_dx; not with dx_reduce): `ops.stem_dgrad_acc` in place of
+    `ops.stem_dgrad` — acc [T,3,H,W] fp32 += scale * dx in the kernel's store epilogue, no dx tensor is made, dx and sal are
+    None (the inner step of `TileIntegratedGradients` / `TileSmoothGrad`).  The gradient chain of the 20-channel stage then keeps its padded layout (the dense one has no
     pool-gradient scatter), so the parameter gradients are those of `net.dense_grads = False`, bit for bit.  Without want_dx
     nothing of this is packed or launched (`Attention.forward` detaches its input as the reference does,
     gbm/model.py:194-196)."""
+    if dx_acc is not None and (dx_reduce is not None or not want_dx):
+        raise ValueError("dx_acc accumulates the three-channel gradient: it goes with want_dx=True and without dx_reduce")
     if saved["x_src"] is not None and saved["x_src"]._version != saved["x_version"]:
         raise RuntimeError("the input tiles were modified in place between the encoder's forward and backward: conv1's gradient is "
                            "computed from them (no space-to-depth copy is kept).  Keep the tensor untouched until backward, or set "
@@ -687,7 +691,10 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False
             raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
         if dstem is None:                   # the fused stem backward never materialises it
             dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
-        dx, sal = ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
+        if dx_acc is not None:
+            ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
+        else:
+            dx, sal = ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
     flat = list(bw.grads["stem", 0])
     for bi, blk in enumerate(bw.blocks):
         flat += [*bw.grads[bi, 1], *bw.grads[bi, 2]]

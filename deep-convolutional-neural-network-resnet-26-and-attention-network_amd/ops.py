@@ -677,6 +677,104 @@ def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None):
     return dx, sal
 
 
+def stem_dgrad_acc(dstem, wpack, hw, acc, scale):
+    """acc [n,3,H,W] fp32 += scale * dx in place (see mil_stem_dgrad_acc), dx what `stem_dgrad(dstem, wpack, hw)` returns: a
+    product and a sum per element, no temporary gradient tensor.  Returns acc."""
+    if dstem.dim() != 4:
+        raise ValueError(f"dstem must be [n,H2,W2,24], got {tuple(dstem.shape)}")
+    n = dstem.shape[0]
+    h, w = hw
+    code = L.dt_code(dstem.dtype, mma=True)
+    _need(dstem, (n, (h + 1) // 2, (w + 1) // 2, 24), dstem.dtype, "dstem")
+    elems = ctypes.c_size_t(0)
+    L.check(L.lib().mil_packed_weight_elems(ctypes.byref(elems), 20, 3, 7, L.PACK_STEM_DGRAD), "mil_packed_weight_elems")
+    _need(wpack, (elems.value,), dstem.dtype, "wpack")
+    if acc is None:
+        raise ValueError("acc: the running sum [n,3,H,W] fp32 is the caller's")
+    _need(acc, (n, 3, h, w), torch.float32, "acc")
+    _launch("mil_stem_dgrad_acc", ("stem_dgrad_acc", n, h, w), dstem.data_ptr(), wpack.data_ptr(), acc.data_ptr(), float(scale), n, h,
+            w, code, L.stream_ptr())
+    return acc
+
+
+def _tile_stack(tiles, name="tiles"):
+    """(the contiguous CUDA tensor behind fp32 tiles or `U8Tiles`, is_u8) for the path-attribution kernels."""
+    from .preprocess import U8Tiles
+    x = tiles.u8 if isinstance(tiles, U8Tiles) else tiles
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{name} must be fp32 [T,3,H,W] or U8Tiles, got {tuple(getattr(x, 'shape', ()))}")
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{name} must be fp32 [T,3,H,W] or U8Tiles, got {x.dtype}")
+    if x.dtype == torch.uint8 and not isinstance(tiles, U8Tiles):
+        raise ValueError(f"{name}: uint8 images come wrapped in U8Tiles")
+    _need(x, x.shape, x.dtype, name)
+    return x, x.dtype == torch.uint8
+
+
+def _base3(base):
+    """Three per-channel floats from a scalar or a sequence of three."""
+    vals = [float(base)] * 3 if isinstance(base, (int, float)) else [float(v) for v in base]
+    if len(vals) != 3:
+        raise ValueError(f"base: a scalar or three per-channel values, got {len(vals)}")
+    return vals
+
+
+def path_point(tiles, alpha, base, *, noise_level=0.0, value_range=None, seed=0, sample=0, out=None):
+    """base[c] + alpha * (tiles - base[c]) + sigma * noise as fp32 [T,3,H,W] (see mil_path_point): tiles an fp32 stack or
+    `U8Tiles`; base a scalar or three per-channel values; sigma = noise_level * (value_range[1] - value_range[0]) with
+    value_range a device fp32 tensor (lo, hi), or noise_level itself without one; the noise of element i is a function of
+    (seed, sample, i) only (Philox4x32-10 + Box-Muller) and torch's generator is not involved.  `out`: the caller's tensor."""
+    b = _base3(base)
+    noise_level = float(noise_level)
+    if not noise_level >= 0.0:
+        raise ValueError(f"noise_level must be >= 0, got {noise_level}")
+    seed, sample = int(seed), int(sample)
+    if not 0 <= seed < 1 << 64 or not 0 <= sample < 1 << 32:
+        raise ValueError(f"seed must fit 64 bits and sample 32, got {seed} and {sample}")
+    x, is_u8 = _tile_stack(tiles)
+    n, _, h, w = x.shape
+    _need(value_range, (2,), torch.float32, "value_range")
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=x.device)
+    _need(out, (n, 3, h, w), torch.float32, "out")
+    _launch("mil_path_point", ("path_point", n, h, w, is_u8, noise_level != 0.0), x.data_ptr(), int(is_u8), out.data_ptr(), *b,
+            float(alpha), noise_level, L.ptr(value_range), seed, sample, n, h, w, L.stream_ptr())
+    return out
+
+
+ATTR_MAP_MODES = ("sum", "max", "grad_max")       # mil_attr_finish's map_mode 0, 1, 2
+
+
+def attr_finish(acc, tiles, base, *, want_attr=True, want_map=False, map_mode="sum", want_sums=False):
+    """From an accumulated gradient acc [T,3,H,W] fp32 to (attr, map, tile_sum) (see mil_attr_finish; None for what is not
+    wanted): attr = (tiles - base[c]) * acc; map [T,H,W] = |sum_c attr| ("sum"), max_c |attr| ("max") or max_c |acc|
+    ("grad_max": reads no tiles, which may then be None); tile_sum [T] = the sum of attr per tile in a fixed order."""
+    if map_mode not in ATTR_MAP_MODES:
+        raise ValueError(f"map_mode must be one of {ATTR_MAP_MODES}, got {map_mode!r}")
+    if not (want_attr or want_map or want_sums):
+        raise ValueError("nothing is wanted")
+    if not isinstance(acc, torch.Tensor) or acc.dim() != 4 or acc.shape[1] != 3:
+        raise ValueError(f"acc must be fp32 [T,3,H,W], got {tuple(getattr(acc, 'shape', ()))}")
+    _need(acc, acc.shape, torch.float32, "acc")
+    n, _, h, w = acc.shape
+    x, is_u8 = None, False
+    if tiles is not None:
+        x, is_u8 = _tile_stack(tiles)
+        if x.shape != acc.shape:
+            raise ValueError(f"tiles {tuple(x.shape)} and acc {tuple(acc.shape)} differ")
+    elif want_attr or want_sums or map_mode != "grad_max":
+        raise ValueError("only the 'grad_max' map is made without tiles")
+    b = _base3(base)
+    dev = acc.device
+    attr = torch.empty_like(acc) if want_attr else None
+    amap = torch.empty((n, h, w), dtype=torch.float32, device=dev) if want_map else None
+    sums = torch.empty((n,), dtype=torch.float32, device=dev) if want_sums else None
+    ws = torch.empty((n, L.ATTR_SLICES), dtype=torch.float32, device=dev) if want_sums else None
+    _launch("mil_attr_finish", ("attr_finish", n, h, w, is_u8, want_attr, want_map, want_sums), acc.data_ptr(), L.ptr(x), int(is_u8),
+            *b, L.ptr(attr), L.ptr(amap), ATTR_MAP_MODES.index(map_mode), L.ptr(sums), L.ptr(ws), n, h, w, L.stream_ptr())
+    return attr, amap, sums
+
+
 _RESAMPLE_TABLES = {}
 
 

@@ -465,6 +465,45 @@ int mil_stem_bwd_fused_u8(const uint8_t* x_u8, const void* g_pool, const uint8_t
 int mil_stem_dgrad(const void* dstem, const void* wpack, float* dx_nchw, float* sal, int n, int H, int W, int reduce, int dtype,
                    void* stream);
 
+/* The accumulating form of mil_stem_dgrad(reduce = 0), the inner step of integrated gradients and SmoothGrad:
+ *     acc_nchw [n,3,H,W] fp32 = acc_nchw + scale * dx
+ * with dx what mil_stem_dgrad writes for the same dstem / wpack / dtype, from the same accumulators: each element is read, updated
+ * as __fadd_rn(old, __fmul_rn(scale, dx)) — a product and a sum, never a fused multiply-add — and written back by the one lane that
+ * owns it.  No temporary gradient tensor, no atomics, no workspace: bit-repeatable, and bit for bit `acc + scale * dx` in fp32.
+ * There is no `reduce` form.  Null dstem / wpack / acc_nchw, n < 0, H or W < 1, another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no
+ * launch; one image's dstem of 2 GiB or more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+int mil_stem_dgrad_acc(const void* dstem, const void* wpack, float* acc_nchw, float scale, int n, int H, int W, int dtype,
+                       void* stream);
+
+/* A point of a straight path from a baseline colour to the tiles, optionally with Gaussian noise — the input of one step of
+ * integrated gradients (`integrated_gradients.py`) or SmoothGrad (`smooth_grad.py`) of the same toolkit:
+ *     out[t,c,y,x] = base[c] + alpha * (v - base[c]) + sigma * n(seed, sample, i)          out [n,3,H,W] fp32
+ * tiles [n,3,H,W]: fp32 (is_u8 == 0; v the value) or uint8 (is_u8 == 1; v the decoded value of mil_u8_decode_table, so the result
+ * is bit for bit that of the decoded fp32 tensor).  The differences, products and sums are single correctly rounded fp32 operations,
+ * none fused.  sigma = noise_level * (range[1] - range[0]) with range a DEVICE float[2], or noise_level itself when range is NULL;
+ * noise_level == 0: no generator runs and the third term is absent.  n(seed, sample, i), i the linear element index: Philox4x32-10
+ * (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85) with key (seed low, seed high) and counter
+ * (i >> 2 low, i >> 2 high, sample, 0) gives r0..r3; u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24, elements 4 (i >> 2) and + 1
+ * get sqrt(-2 ln u1) cospi(2 u2) and sqrt(-2 ln u1) sinpi(2 u2), elements + 2 and + 3 the same of (r2, r3): a value depends on
+ * (seed, sample, i) only.  Null tiles / out, is_u8 outside {0,1}, n < 0, H or W < 1, noise_level < 0 or NaN, alpha NaN: MIL_ERR_ARG;
+ * n == 0: MIL_OK, no launch; H W of 2^31 or more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+int mil_path_point(const void* tiles, int is_u8, float* out, float base0, float base1, float base2, float alpha, float noise_level,
+                   const float* range, unsigned long long seed, unsigned sample, int n, int H, int W, void* stream);
+
+/* From an accumulated mean gradient acc [n,3,H,W] fp32 to what is shown; any subset of the three outputs (NULL: not made):
+ *     attr [n,3,H,W]  = (v - base[c]) * acc                   one difference and one product per element, not fused
+ *     map [n,H,W]       map_mode 0: |(a0 + a1) + a2|, a_c = attr of channel c        1: max_c |a_c|
+ *                       map_mode 2: max_c |acc_c| — reads no tiles (tiles may be NULL when it is the only output)
+ *     tile_sum [n]    = the sum of attr over the tile, in a fixed order: each of MIL_ATTR_SLICES workgroups per tile sums its pixels
+ *                       ((a0 + a1) + a2 per pixel) into ws [n * MIL_ATTR_SLICES] fp32, a second small launch adds a tile's partial
+ *                       sums in slice order.  No atomics: two calls give the same bits
+ * tiles as for mil_path_point.  Null acc, no output, tiles NULL where they are read, tile_sum without ws, is_u8 outside {0,1},
+ * map_mode outside {0,1,2}, n < 0, H or W < 1: MIL_ERR_ARG; n == 0: MIL_OK, no launch; 3 H W of 2^31 or more:
+ * MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+#define MIL_ATTR_SLICES 32
+int mil_attr_finish(const float* acc, const void* tiles, int is_u8, float base0, float base1, float base2, float* attr, float* map,
+                    int map_mode, float* tile_sum, float* ws, int n, int H, int W, void* stream);
+
 /* Grad-CAM per tile: the post-processing of `gradcam.py:75-89` of the same toolkit (pytorch-cnn-visualizations-master/src), from
  * the output of a convolutional stage and the gradient of the class evidence with respect to it to the bytes the toolkit draws
  * over the tile.  act, grad [n,h,w,cs] (bf16 under MIL_DT_BF16, fp32 under MIL_DT_F32 / MIL_DT_F32S; c real channels of cs
