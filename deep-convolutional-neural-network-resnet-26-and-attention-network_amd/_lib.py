@@ -101,6 +101,10 @@ _SIGS = {
     "mil_stem_dgrad_acc": ([_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp], _i),
     "mil_path_point": ([_vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _c.c_uint64, _c.c_uint32, _i, _i, _i, _vp], _i),
     "mil_attr_finish": ([_vp, _vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
+    "mil_map_quantile_workspace": ([_c.POINTER(_sz), _i, _i], _i),
+    "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),
+    "mil_attr_render": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "mil_cam_overlay": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "mil_grad_cam": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -775,6 +775,109 @@ def attr_finish(acc, tiles, base, *, want_attr=True, want_map=False, map_mode="s
     return attr, amap, sums
 
 
+QUANTILE_GROUPS = ("tile", "bag")
+RENDER_MODES = ("grayscale", "colour", "pos_neg")     # mil_attr_render's mode 0, 1, 2
+MapStats = collections.namedtuple("MapStats", "stats p group")
+MapStats.__doc__ = """What `map_quantile` returns: stats [G,4] fp32 = (min, max, s[lo], s[hi]) and p [G] fp64 per group (G = T for
+group "tile", 1 for "bag"), on the device."""
+
+
+def _attr_tensor(x, name, ranks=(3, 4)):
+    """(T, channels, H, W) of an fp32 attribution tensor: a gradient [T,3,H,W] or a map [T,H,W]."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise ValueError(f"{name} must be an fp32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() not in ranks or (x.dim() == 4 and x.shape[1] != 3):
+        want = " or ".join({3: "[T,H,W]", 4: "[T,3,H,W]"}[r] for r in sorted(ranks, reverse=True))
+        raise ValueError(f"{name} must be fp32 {want}, got {tuple(x.shape)}")
+    t, h, w = x.shape[0], x.shape[-2], x.shape[-1]
+    if t < 1 or h < 1 or w < 1:
+        raise ValueError(f"{name}: an empty bag (or empty tiles) has nothing to rank or render, got {tuple(x.shape)}")
+    return t, (3 if x.dim() == 4 else 1), h, w
+
+
+def _check_stats(st, x, t):
+    if not isinstance(st, MapStats) or st.group not in QUANTILE_GROUPS:
+        raise ValueError("stats: what ops.map_quantile returned")
+    g = t if st.group == "tile" else 1
+    if tuple(st.stats.shape) != (g, 4) or tuple(st.p.shape) != (g,):
+        raise ValueError(f"stats of {st.stats.shape[0]} groups for {g} (group {st.group!r}, {t} tiles)")
+    _need(x, x.shape, torch.float32, "x")
+    _need(st.stats, (g, 4), torch.float32, "stats.stats")
+    _need(st.p, (g,), torch.float64, "stats.p")
+    if st.stats.device != x.device:
+        raise ValueError("stats and the tensor they are applied to are on different devices")
+
+
+def map_quantile(x, q=99.0, group="tile", *, raw=False):
+    """Per-group order statistics of an attribution tensor (see mil_map_quantile) as `MapStats`: the minimum, the maximum, the
+    two order statistics that bracket the q-th percentile and the percentile itself in fp64, bit for bit
+    `np.percentile(values.astype(np.float64), q)`.  x: a gradient [T,3,H,W] (ranked: (|g0| + |g1|) + |g2|, or with raw=True
+    every element of the gradient as it is) or a map [T,H,W]; group "tile" or "bag".  No host synchronisation."""
+    q = float(q)
+    if not (0.0 < q <= 100.0):
+        raise ValueError(f"q must be in (0, 100], got {q}")
+    if group not in QUANTILE_GROUPS:
+        raise ValueError(f"group must be one of {QUANTILE_GROUPS}, got {group!r}")
+    t, c, h, w = _attr_tensor(x, "x")
+    _need(x, x.shape, torch.float32, "x")
+    if raw and c == 3:
+        c, h = 1, 3 * h
+    bag = group == "bag"
+    groups = 1 if bag else t
+    need = ctypes.c_size_t(0)
+    L.check(L.lib().mil_map_quantile_workspace(ctypes.byref(need), t, int(bag)), "mil_map_quantile_workspace")
+    ws = torch.empty(need.value // 4, dtype=torch.int32, device=x.device)
+    stats = torch.empty((groups, 4), dtype=torch.float32, device=x.device)
+    p = torch.empty((groups,), dtype=torch.float64, device=x.device)
+    _launch("mil_map_quantile", ("map_quantile", t, c, h, w, q, bag), x.data_ptr(), t, c, h, w, q, int(bag), ws.data_ptr(), need.value,
+            stats.data_ptr(), p.data_ptr(), L.stream_ptr())
+    return MapStats(stats, p, group)
+
+
+def attr_render(x, stats, mode="grayscale"):
+    """An attribution tensor and its `MapStats` to the toolkit's bytes (see mil_attr_render): "grayscale" — a gradient [T,3,H,W]
+    or a map [T,H,W] to uint8 [T,H,W], clipped between the group's minimum and its percentile; "colour" — a gradient to uint8
+    [T,H,W,3], min-max over the group; "pos_neg" — (positive, negative) saliency, two uint8 [T,H,W,3].  The statistics of
+    "colour" and "pos_neg" are those of `map_quantile(x, 100, group, raw=True)`."""
+    if mode not in RENDER_MODES:
+        raise ValueError(f"mode must be one of {RENDER_MODES}, got {mode!r}")
+    t, c, h, w = _attr_tensor(x, "x", ranks=(3, 4) if mode == "grayscale" else (4,))
+    _check_stats(stats, x, t)
+    dev = x.device
+    shape = (t, h, w) if mode == "grayscale" else (t, h, w, 3)
+    out0 = torch.empty(shape, dtype=torch.uint8, device=dev)
+    out1 = torch.empty(shape, dtype=torch.uint8, device=dev) if mode == "pos_neg" else None
+    _launch("mil_attr_render", ("attr_render", t, c, h, w, mode), x.data_ptr(), t, c, h, w, RENDER_MODES.index(mode),
+            int(stats.group == "bag"), stats.stats.data_ptr(), stats.p.data_ptr(), out0.data_ptr(), L.ptr(out1), L.stream_ptr())
+    return (out0, out1) if mode == "pos_neg" else out0
+
+
+def cam_overlay(tiles, map_u8, lut, alpha_byte):
+    """(heat, on_image), two uint8 [T,H,W,3] (see mil_cam_overlay): the colour table `lut` (uint8 [256,3]) looked up at the map
+    bytes `map_u8` [T,H,W], and Pillow's alpha_composite of that with alpha `alpha_byte` (0..255) over the `U8Tiles`."""
+    from .preprocess import U8Tiles
+    if not isinstance(tiles, U8Tiles):
+        raise ValueError(f"tiles must be U8Tiles, got {type(tiles).__name__}")
+    x = tiles.u8
+    t, _, h, w = x.shape
+    if not isinstance(map_u8, torch.Tensor) or map_u8.dtype != torch.uint8 or tuple(map_u8.shape) != (t, h, w):
+        raise ValueError(f"map_u8 must be uint8 {(t, h, w)}, got {getattr(map_u8, 'dtype', None)} {tuple(getattr(map_u8, 'shape', ()))}")
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError("lut must be a uint8 [256,3] tensor")
+    if int(alpha_byte) != alpha_byte or not 0 <= alpha_byte <= 255:
+        raise ValueError(f"alpha_byte must be an integer in [0, 255], got {alpha_byte}")
+    if t < 1 or h < 1 or w < 1:
+        raise ValueError(f"an empty bag has nothing to draw on, got {tuple(x.shape)}")
+    _need(x, x.shape, torch.uint8, "tiles")
+    _need(map_u8, (t, h, w), torch.uint8, "map_u8")
+    _need(lut, (256, 3), torch.uint8, "lut")
+    heat = torch.empty((t, h, w, 3), dtype=torch.uint8, device=x.device)
+    on_image = torch.empty((t, h, w, 3), dtype=torch.uint8, device=x.device)
+    _launch("mil_cam_overlay", ("cam_overlay", t, h, w), x.data_ptr(), map_u8.data_ptr(), lut.data_ptr(), int(alpha_byte), t, h, w,
+            heat.data_ptr(), on_image.data_ptr(), L.stream_ptr())
+    return heat, on_image
+
+
 _RESAMPLE_TABLES = {}
 
 

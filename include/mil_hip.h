@@ -504,6 +504,49 @@ int mil_path_point(const void* tiles, int is_u8, float* out, float base0, float 
 int mil_attr_finish(const float* acc, const void* tiles, int is_u8, float base0, float base1, float base2, float* attr, float* map,
                     int map_mode, float* tile_sum, float* ws, int n, int H, int W, void* stream);
 
+/* Order statistics of attribution maps: what `convert_to_grayscale` of the same toolkit's misc_functions.py takes with np.min and
+ * np.percentile(., 99).  x [n,channels,H,W] fp32: channels == 3 ranks gray = (|g0| + |g1|) + |g2| (fp32, numpy's axis-0 order),
+ * channels == 1 ranks the map itself.  A group is one tile (bag == 0; n groups of H W values) or the whole bag (bag == 1; one group
+ * of n H W values).  With N the values of a group, vi = (N - 1) * (q / 100) in fp64 (numpy's linear method), lo = floor(vi),
+ * hi = min(lo + 1, N - 1), t = vi - lo and s the group's values in ascending order:
+ *     stats[g] = (min, max, s[lo], s[hi])     fp32, bit for bit
+ *     p[g]     = s[lo] + (s[hi] - s[lo]) * t when t < 0.5, s[hi] - (s[hi] - s[lo]) * (1 - t) otherwise; fp64, each operation rounded
+ *                on its own — bit for bit np.percentile(values.astype(np.float64), q)
+ * An exact radix select over the order-preserving 32-bit key of a value, in three digit passes (11, 11, 10 bits) of a histogram
+ * launch and a select launch each; q == 100 needs the first histogram only.  Values order by IEEE value; -0.0 counts as (and is
+ * returned as) +0.0; a NaN orders by its bits, above +inf or, with the sign bit set, below -inf.  Counts are integers merged with
+ * integer atomics: two calls give the same bits.  workspace: mil_map_quantile_workspace(n, bag) bytes — MIL_QUANTILE_WS_WORDS
+ * 32-bit words per tile, or for a bag MIL_QUANTILE_BAG_TABLES copies of them (tile t adds to copy t % 16, so that not every
+ * workgroup adds to the same words; the select launch sums the copies); the call clears it itself.  Null x / workspace / stats / p, n < 1, H or W < 1,
+ * channels outside {1,3}, bag outside {0,1}, q outside (0, 100] or NaN, a workspace too small: MIL_ERR_ARG; a tile of more
+ * than 2^30 values or a group of 2^31 or more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+#define MIL_QUANTILE_WS_WORDS 4104
+#define MIL_QUANTILE_BAG_TABLES 16
+int mil_map_quantile_workspace(size_t* bytes, int n, int bag);
+int mil_map_quantile(const float* x, int n, int channels, int H, int W, double q, int bag, void* workspace, size_t workspace_bytes,
+                     float* stats, double* p, void* stream);
+
+/* Attribution tensors to the toolkit's bytes, from x and the statistics of mil_map_quantile (group of tile t: bag ? 0 : t):
+ *     mode 0  grayscale (convert_to_grayscale + format_np_output): x [n,channels,H,W], channels 3 (gray as above) or 1 (the map);
+ *             out0 [n,H,W] = trunc(255 * clip((double(gray) - double(min)) / (p - double(min)), 0, 1)), fp64; p == min: zeros
+ *     mode 1  colour (save_gradient_images): x [n,3,H,W]; out0 [n,H,W,3] = trunc(((g - min) / (max - min)) * 255) in fp32, each
+ *             operation rounded; max == min: zeros.  The statistics are those of the gradient as a map (channels 1, 3 H rows)
+ *     mode 2  positive / negative (get_positive_negative_saliency + save_gradient_images): out0 [n,H,W,3] =
+ *             trunc((max(0, g) / max) * 255), out1 [n,H,W,3] = trunc((max(0, -g) / (-min)) * 255), fp32; max <= 0 / min >= 0: zeros
+ * Pointwise, 16-byte loads and 4-byte stores where H W % 4 == 0 and the pointers allow, scalar accesses otherwise.  Null x / stats /
+ * out0, mode 0 without p, mode 2 without out1, channels the mode does not take, mode outside {0,1,2}, bag outside {0,1}, n < 0,
+ * H or W < 1: MIL_ERR_ARG; n == 0: MIL_OK, no launch; H W of 2^31 or more: MIL_ERR_UNSUPPORTED — decided on the host. */
+int mil_attr_render(const float* x, int n, int channels, int H, int W, int mode, int bag, const float* stats, const double* p,
+                    uint8_t* out0, uint8_t* out1, void* stream);
+
+/* apply_colormap_on_image of the same file: heat [n,H,W,3] = lut[map] (lut [256,3] uint8, map [n,H,W] uint8) and on_image
+ * [n,H,W,3] = Pillow's Image.alpha_composite of heat with alpha byte `alpha` over the opaque tile (tiles [n,3,H,W] uint8 planar):
+ *     tmp = 64 * (src * alpha + dst * (255 - alpha)) + (0x80 << 6);   out = (((tmp >> 8) + tmp) >> 8) >> 6
+ * per channel.  Either output may be NULL.  Null tiles / map / lut, both outputs null, alpha outside [0,255], n < 0, H or W < 1:
+ * MIL_ERR_ARG; n == 0: MIL_OK, no launch; H W of 2^31 or more: MIL_ERR_UNSUPPORTED — decided on the host. */
+int mil_cam_overlay(const uint8_t* tiles, const uint8_t* map, const uint8_t* lut, int alpha, int n, int H, int W, uint8_t* heat,
+                    uint8_t* on_image, void* stream);
+
 /* Grad-CAM per tile: the post-processing of `gradcam.py:75-89` of the same toolkit (pytorch-cnn-visualizations-master/src), from
  * the output of a convolutional stage and the gradient of the class evidence with respect to it to the bytes the toolkit draws
  * over the tile.  act, grad [n,h,w,cs] (bf16 under MIL_DT_BF16, fp32 under MIL_DT_F32 / MIL_DT_F32S; c real channels of cs
