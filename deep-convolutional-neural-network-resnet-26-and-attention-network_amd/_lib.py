@@ -105,6 +105,7 @@ _SIGS = {
     "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),
     "mil_attr_render": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "mil_cam_overlay": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "mil_attr_mosaic": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_grad_cam": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),

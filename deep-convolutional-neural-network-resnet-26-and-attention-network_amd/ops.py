@@ -878,6 +878,48 @@ def cam_overlay(tiles, map_u8, lut, alpha_byte):
     return heat, on_image
 
 
+def attr_mosaic(maps, out_pos, n, lut, alpha_byte, alpha_by_value=False, heat=None, on_tissue=None):
+    """Per-tile maps resampled into the n x n blocks of thumbnail pixels at `out_pos` (int32 [T,2] of (row, col), on the device)
+    of the caller's canvases `heat` and / or `on_tissue` (uint8 [Ht,Wt,3]; see mil_attr_mosaic): maps uint8 [T,Hm,Wm] are
+    coloured through `lut` (uint8 [256,3]), maps uint8 [T,Hm,Wm,3] are the colours themselves (`lut` may be None).  `heat`
+    receives the colours, `on_tissue` their alpha_composite with `alpha_byte` (0..255; with `alpha_by_value` scaled by the map's
+    value, one-channel maps only) over what it holds.  Blocks must not overlap; the part of a block outside the canvas is not
+    stored, pixels no block owns keep their bytes.  Returns (heat, on_tissue)."""
+    if not isinstance(maps, torch.Tensor) or maps.dtype != torch.uint8 or maps.dim() not in (3, 4) or (maps.dim() == 4 and maps.shape[3] != 3):
+        raise ValueError(f"maps must be uint8 [T,Hm,Wm] or [T,Hm,Wm,3], got {getattr(maps, 'dtype', type(maps).__name__)} "
+                         f"{tuple(getattr(maps, 'shape', ()))}")
+    t, hm, wm = (int(v) for v in maps.shape[:3])
+    channels = 1 if maps.dim() == 3 else 3
+    if hm < 1 or wm < 1:
+        raise ValueError(f"empty maps {tuple(maps.shape)}")
+    if int(n) != n or n < 1:
+        raise ValueError(f"n must be a positive integer, got {n}")
+    if int(alpha_byte) != alpha_byte or not 0 <= alpha_byte <= 255:
+        raise ValueError(f"alpha_byte must be an integer in [0, 255], got {alpha_byte}")
+    if alpha_by_value and channels == 3:
+        raise ValueError("alpha_by_value needs one-channel maps: a colour picture has no value to scale the alpha by")
+    if channels == 1 and lut is None:
+        raise ValueError("one-channel maps need a uint8 [256,3] colour table")
+    canvas = heat if heat is not None else on_tissue
+    if canvas is None:
+        raise ValueError("neither heat nor on_tissue: nothing to draw on")
+    if not isinstance(canvas, torch.Tensor) or canvas.dim() != 3 or canvas.shape[2] != 3 or canvas.shape[0] < 1 or canvas.shape[1] < 1:
+        raise ValueError(f"a canvas is uint8 [Ht,Wt,3], got {tuple(getattr(canvas, 'shape', ()))}")
+    if not isinstance(out_pos, torch.Tensor):
+        raise ValueError(f"out_pos must be an int32 [{t},2] tensor on the device, got {type(out_pos).__name__}")
+    _need(maps, maps.shape, torch.uint8, "maps")
+    _need(out_pos, (t, 2), torch.int32, "out_pos")
+    _need(lut, (256, 3), torch.uint8, "lut")
+    _need(heat, canvas.shape, torch.uint8, "heat")
+    _need(on_tissue, canvas.shape, torch.uint8, "on_tissue")
+    if any(x is not None and x.device != maps.device for x in (out_pos, lut, heat, on_tissue)):
+        raise ValueError("maps, out_pos, lut and the canvases must be on one device")
+    _launch("mil_attr_mosaic", ("attr_mosaic", t, hm, wm, channels, int(n)), maps.data_ptr(), channels, t, hm, wm, int(n), out_pos.data_ptr(),
+            L.ptr(lut), int(alpha_byte), int(bool(alpha_by_value)), L.ptr(heat), L.ptr(on_tissue), int(canvas.shape[0]),
+            int(canvas.shape[1]), L.stream_ptr())
+    return heat, on_tissue
+
+
 _RESAMPLE_TABLES = {}
 
 

@@ -127,6 +127,18 @@ class SlideBag:
         renderer = AttentionMapRenderer(self.roi_size, scale, **renderer_args)
         return renderer.render(self.slide, self.coords, visualize_terms(output)["A1"], output["Fterm"] if features else None)
 
+    def attribution_maps(self, maps, scale, **mosaic_args):
+        """The slide mosaic of per-tile attribution maps over this bag's windows, uint8 [2, H//scale, W//scale, 3] on the
+        slide's device (`AttributionMosaic.render`): panel 0 the maps on white, panel 1 the maps over the tissue.  maps: uint8
+        [T,Hm,Wm] or [T,Hm,Wm,3], one per kept window in the order of `coords` — what `AttributionRenderer` or
+        `TileGradCam.maps` made of the tiles of the FLAT chain (`get_inference_data` / `get_validation_data`).  Train tiles
+        are cropped and flipped: their pixels do not lie where the window lies, and their maps do not belong here.
+        `mosaic_args`: cmap / alpha / alpha_by_value of `AttributionMosaic`."""
+        if self.coords is None:
+            raise RuntimeError("call build() first")
+        from .attr_mosaic import AttributionMosaic
+        return AttributionMosaic(self.roi_size, scale, **mosaic_args).render(self.slide, self.coords, maps)
+
     def rois(self, indices):
         """The chosen kept windows as pixels, uint8 [n,S,S,3] on the slide's device — materialised on request only."""
         if self.coords is None:

@@ -547,6 +547,33 @@ int mil_attr_render(const float* x, int n, int channels, int H, int W, int mode,
 int mil_cam_overlay(const uint8_t* tiles, const uint8_t* map, const uint8_t* lut, int alpha, int n, int H, int W, uint8_t* heat,
                     uint8_t* on_image, void* stream);
 
+/* Slide mosaic of per-tile attribution maps: the uint8 maps or pictures of the T kept windows resampled into the blocks of
+ * thumbnail pixels the windows own, coloured and composited over the tissue.  maps: channels == 1, uint8 [T,Hm,Wm] (what
+ * mil_attr_render's mode 0 or mil_grad_cam write), coloured through lut, uint8 [256,3]; channels == 3, uint8 [T,Hm,Wm,3]
+ * interleaved (modes 1 and 2, mil_cam_overlay's heat), used as the colour itself (lut may be NULL).  Window t owns the n x n block
+ * of output pixels whose top-left one is (out_pos[t][0], out_pos[t][1]) (row, col; DEVICE int32 [T,2]) — mil_heatmap_render's
+ * convention with n = S / D; the part of a block outside [Ht,Wt] is not stored, blocks of two windows must not overlap (the
+ * caller's to ensure), pixels no window owns are not touched.  heat and on_tissue: uint8 [Ht,Wt,3], either may be NULL;
+ * on_tissue is read and written in place (the caller has put the tissue thumbnail there), every output pixel by the one thread
+ * that owns it.  All integer.  For owned pixel (a,b), 0 <= a,b < n, and channel c:
+ *     wy[k] = max(0, min((a+1)*Hm, (k+1)*n) - max(a*Hm, k*n))      k = 0..Hm-1   (sums to Hm)
+ *     wx[l] = max(0, min((b+1)*Wm, (l+1)*n) - max(b*Wm, l*n))      l = 0..Wm-1   (sums to Wm)
+ *     v[c]  = (sum_k sum_l wy[k]*wx[l]*maps[t,k,l,c] + Hm*Wm/2) / (Hm*Wm)
+ * the area (box) average of the map over the pixel's footprint, rounded half up: the k x k box mean with mil_heatmap_render's
+ * rounding for Hm = k*n, the identity for Hm == n, pixel replication for n = k*Hm, fractional coverage otherwise.  Then
+ *     src[c]    = lut[v][c] (channels == 1) or v[c] (channels == 3);      heat = src
+ *     on_tissue = Pillow's alpha_composite as mil_cam_overlay states it, over the byte dst already there:
+ *                 tmp = 64 * (src * a + dst * (255 - a)) + (0x80 << 6);   out = (((tmp >> 8) + tmp) >> 8) >> 6
+ *                 a = alpha, or with alpha_by_value (channels == 1 only) a = (alpha * v + 127) / 255
+ * The sums are 32-bit: 255*Hm*Wm + Hm*Wm/2 < 2^32 for Hm*Wm <= 2^24, above that MIL_ERR_UNSUPPORTED.  Two forms of one kernel
+ * give the same bytes: a thread per owned pixel, or — where ceil(Hm/n) * ceil(Wm/n) >= 64 — a wave per owned pixel with a
+ * shuffle reduction.  Null maps / out_pos, both outputs null, lut null with channels == 1, channels outside {1,3}, alpha outside
+ * [0,255], alpha_by_value outside {0,1} or set with channels == 3, T < 0, Hm, Wm, n, Ht or Wt < 1: MIL_ERR_ARG; T == 0: MIL_OK,
+ * no launch — all decided on the host before any GPU call.  Any T (launches of 65535 windows), any n.  No atomics on global
+ * memory, no workspace: bit-repeatable. */
+int mil_attr_mosaic(const uint8_t* maps, int channels, int T, int Hm, int Wm, int n, const int32_t* out_pos, const uint8_t* lut,
+                    int alpha, int alpha_by_value, uint8_t* heat, uint8_t* on_tissue, int Ht, int Wt, void* stream);
+
 /* Grad-CAM per tile: the post-processing of `gradcam.py:75-89` of the same toolkit (pytorch-cnn-visualizations-master/src), from
  * the output of a convolutional stage and the gradient of the class evidence with respect to it to the bytes the toolkit draws
  * over the tile.  act, grad [n,h,w,cs] (bf16 under MIL_DT_BF16, fp32 under MIL_DT_F32 / MIL_DT_F32S; c real channels of cs
