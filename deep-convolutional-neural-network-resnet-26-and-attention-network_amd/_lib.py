@@ -24,6 +24,7 @@ BF16X3 = "bf16x3"
 PACK_FWD, PACK_DGRAD, PACK_STEM, PACK_DGRAD_S2, PACK_STEM_DGRAD = 0, 1, 2, 3, 4
 FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pillow's own codes)
 ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per tile in mil_attr_finish's workspace
+SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per tile in mil_stage_seed's workspace
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -101,7 +102,9 @@ _SIGS = {
     "mil_stem_dgrad_acc": ([_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp], _i),
     "mil_path_point": ([_vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _c.c_uint64, _c.c_uint32, _i, _i, _i, _vp], _i),
     "mil_attr_finish": ([_vp, _vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
-    "mil_map_quantile_workspace": ([_c.POINTER(_sz), _i, _i], _i),
+    "mil_stage_seed": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
+    "mil_pixel_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i] + [_f] * 9 + [_vp], _i),
+    "mil_map_quantile_workspace":([_c.POINTER(_sz), _i, _i], _i),
     "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),
     "mil_attr_render": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "mil_cam_overlay": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),

@@ -1,0 +1,222 @@
+// Activation maximisation: the two elementwise ends of a gradient-ascent step on the PIXELS (cnn_layer_visualization.py,
+// deep_dream.py, generate_class_specific_samples.py of the reference's vendored pytorch-cnn-visualizations-master/src).  Between
+// them runs the encoder: a forward cut short at a stage and the data-gradient-only walk back to the tiles; DESIGN.md section 3.43.
+//
+//   stage_seed_kernel<T>          J_t = mean_{y,x} act[t,y,x,ch_t] (partial sums) and dz, the gradient of -J_t in the form the
+//                                 backward chain carries: -(1/(h w)) * lrelu'(act) at channel ch_t, zero everywhere else
+//   stage_seed_sum_kernel         a tile's partial sums added in slice order, divided by h w: objective [T]
+//   pixel_step_kernel<RULE, PROJ> one SGD or Adam step on x [T,3,H,W] fp32 in place, the projection of the new image (none,
+//                                 clamp to [-1,1], or the round trip through bytes) and its bytes, in one pass
+//
+// Every product, quotient, difference and sum that reaches an output is a single correctly rounded fp32 operation (fv_mul, fv_add,
+// fv_sub below carry no `contract` flag; __fdiv_rn, fv_sqrt): numpy's fp32 arithmetic gives the same bits.  Both are streaming
+// kernels: 16-byte loads and stores where the pointers allow, no LDS beyond four words of the block sum, no atomics, every sum in
+// a fixed order.
+#include "common.cuh"
+#include <climits>
+
+__device__ __forceinline__ float fv_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float fv_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float fv_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// The correctly rounded square root: llvm.sqrt.f32, which hipcc lowers to the refined sequence unless it is told otherwise
+// (-fhip-fp32-correctly-rounded-divide-sqrt, its default; the Makefile passes no fast-math flag).  HIP's own __fsqrt_rn is
+// __ocml_native_sqrt_f32 in this toolchain — the bare v_sqrt_f32, one ulp — and does not give numpy's bits.
+__device__ __forceinline__ float fv_sqrt(float a) { return __builtin_sqrtf(a); }
+
+#define FV_THREADS 256
+#define MIL_SEED_SLICES 16              // include/mil_hip.h: partial sums per tile of mil_stage_seed
+
+// Workgroup t * MIL_SEED_SLICES + s owns the pixels [s per, (s + 1) per) of tile t.  A work item is one 8-channel group of one
+// pixel: it writes the group's eight dz values and, when it is the group of the tile's channel, reads that ONE activation.  A
+// channel outside [0, C) selects nothing (dz all zero, J = 0): no address is formed from it.  part [T][MIL_SEED_SLICES]: the sum of
+// the workgroup's activations — per thread in work-item order, then the butterfly over the wave's lanes and the four waves in
+// order: one summation tree per (h w, CP), whatever the grid does.
+template <typename T>
+__global__ __launch_bounds__(FV_THREADS) void stage_seed_kernel(const typename T::elem* __restrict__ act, const int* __restrict__ channels,
+                                                               typename T::elem* __restrict__ dz, float* __restrict__ part, int hw, int per,
+                                                               int CP, int C, float neg_inv, float slope) {
+    __shared__ float red[FV_THREADS / 64];
+    MIL_POISON_STATIC(red);
+    const int tid = threadIdx.x, s = blockIdx.x % MIL_SEED_SLICES;
+    const size_t t = blockIdx.x / MIL_SEED_SLICES;
+    const int p0 = s * per < hw ? s * per : hw, p1 = p0 + per < hw ? p0 + per : hw;
+    const int NG = CP >> 3;
+    const int ch = channels[t];
+    const int cg_t = (ch >= 0 && ch < C) ? ch >> 3 : -1, cj = ch & 7;
+    float sum = 0.f;
+    for (int idx = tid; idx < (p1 - p0) * NG; idx += FV_THREADS) {
+        const int i = idx / NG, cg = idx - i * NG;
+        const size_t off = (t * hw + p0 + i) * CP + cg * 8;
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (cg == cg_t) {
+            const float a = (float)act[off + cj];
+            sum = fv_add(sum, a);
+            const float g = fv_mul(neg_inv, lrelu_grad(a, slope));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = j == cj ? g : 0.f;
+        }
+        store8<T>(dz + off, v);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum = fv_add(sum, __shfl_xor(sum, d));
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) part[t * MIL_SEED_SLICES + s] = fv_add(fv_add(fv_add(red[0], red[1]), red[2]), red[3]);
+}
+
+__global__ __launch_bounds__(FV_THREADS) void stage_seed_sum_kernel(const float* __restrict__ part, float* __restrict__ objective, int n, float hw) {
+    const int t = blockIdx.x * FV_THREADS + threadIdx.x;
+    if (t >= n) return;
+    float s = 0.f;
+    for (int k = 0; k < MIL_SEED_SLICES; ++k) s = fv_add(s, part[(size_t)t * MIL_SEED_SLICES + k]);
+    objective[t] = __fdiv_rn(s, hw);
+}
+
+// rint(clip(x / 2 + 0.5, 0, 1) * 255): x / 2 is exact, the sum and the product are rounded once each, the rounding to an integer is
+// half-to-even (np.round).  A NaN encodes as 0.
+__device__ __forceinline__ unsigned fv_encode(float x) {
+    float y = fv_add(fv_mul(x, 0.5f), 0.5f);
+    y = y > 0.f ? (y > 1.f ? 1.f : y) : 0.f;
+    return (unsigned)rintf(fv_mul(y, 255.0f));
+}
+
+struct PixelStepArgs {
+    float lr, wd, beta1, omb1, beta2, omb2, bc1, sqrt_bc2, eps;
+};
+
+// One thread = the four elements 4 q .. 4 q + 3 of the linear index (fewer in the last group).  vec: every pointer is on its
+// 16-byte (u8_out: 4-byte) grid, so a whole group is one aligned load and store per tensor; the last, short group goes element by
+// element.  RULE 0: SGD, 1: Adam.  PROJ 0: none, 1: clamp to [-1, 1], 2: table[encode(x)], the round trip through bytes.
+template <int RULE, int PROJ>
+__global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, uint8_t* __restrict__ u8_out,
+                                                               const float* __restrict__ table, PixelStepArgs a, unsigned long long total,
+                                                               int vec) {
+    const unsigned long long q = (unsigned long long)blockIdx.x * FV_THREADS + threadIdx.x;
+    const unsigned long long i0 = q * 4;
+    if (i0 >= total) return;
+    const int cnt = total - i0 < 4 ? (int)(total - i0) : 4;
+    const bool whole = vec && cnt == 4;
+    float xv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (whole) {
+        const f32x4_t rx = *reinterpret_cast<const f32x4_t*>(x + i0), rg = *reinterpret_cast<const f32x4_t*>(g + i0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { xv[j] = rx[j]; gv[j] = rg[j]; }
+        if constexpr (RULE == 1) {
+            const f32x4_t rm = *reinterpret_cast<const f32x4_t*>(m + i0), rv = *reinterpret_cast<const f32x4_t*>(v + i0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { mv[j] = rm[j]; vv[j] = rv[j]; }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < cnt) {
+                xv[j] = x[i0 + j]; gv[j] = g[i0 + j];
+                if constexpr (RULE == 1) { mv[j] = m[i0 + j]; vv[j] = v[i0 + j]; }
+            }
+    }
+    unsigned codes = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float gd = fv_add(gv[j], fv_mul(a.wd, xv[j]));
+        float xn;
+        if constexpr (RULE == 0) {
+            xn = fv_sub(xv[j], fv_mul(a.lr, gd));
+        } else {
+            mv[j] = fv_add(fv_mul(a.beta1, mv[j]), fv_mul(a.omb1, gd));
+            vv[j] = fv_add(fv_mul(a.beta2, vv[j]), fv_mul(fv_mul(a.omb2, gd), gd));
+            const float denom = fv_add(__fdiv_rn(fv_sqrt(vv[j]), a.sqrt_bc2), a.eps);
+            xn = fv_sub(xv[j], __fdiv_rn(fv_mul(__fdiv_rn(a.lr, a.bc1), mv[j]), denom));
+        }
+        if constexpr (PROJ == 1) xn = xn < -1.f ? -1.f : (xn > 1.f ? 1.f : xn);
+        unsigned code = 0;
+        if (PROJ == 2 || u8_out) code = fv_encode(xn);
+        if constexpr (PROJ == 2) xn = table[code];
+        xv[j] = xn;
+        codes |= code << (8 * j);
+    }
+    if (whole) {
+        *reinterpret_cast<f32x4_t*>(x + i0) = f32x4_t{xv[0], xv[1], xv[2], xv[3]};
+        if constexpr (RULE == 1) {
+            *reinterpret_cast<f32x4_t*>(m + i0) = f32x4_t{mv[0], mv[1], mv[2], mv[3]};
+            *reinterpret_cast<f32x4_t*>(v + i0) = f32x4_t{vv[0], vv[1], vv[2], vv[3]};
+        }
+        if (u8_out) *reinterpret_cast<unsigned*>(u8_out + i0) = codes;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < cnt) {
+                x[i0 + j] = xv[j];
+                if constexpr (RULE == 1) { m[i0 + j] = mv[j]; v[i0 + j] = vv[j]; }
+                if (u8_out) u8_out[i0 + j] = (uint8_t)((codes >> (8 * j)) & 255u);
+            }
+    }
+}
+
+// include/mil_hip.h has the contracts.  Every status but MIL_ERR_LAUNCH is decided here, before any GPU call.
+extern "C" int mil_stage_seed(const void* act, const int* channels, float* objective, void* dz, float* ws, int n, int h, int w, int cp,
+                              int c, float slope, int dtype, void* stream) {
+    if (!act || !channels || !objective || !dz || !ws || n < 0 || h < 1 || w < 1 || cp < 8 || (cp & 7) || c < 1 || c > cp) return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32) return MIL_ERR_ARG;
+    if (n == 0) return MIL_OK;
+    const unsigned long long hw = (unsigned long long)h * w;
+    if (hw >= (1ull << 24) || hw * (unsigned long long)cp > 0x7fffffffull || n > INT_MAX / MIL_SEED_SLICES) return MIL_ERR_UNSUPPORTED;
+    const int per = (int)((hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES);
+    const float neg_inv = -(1.0f / (float)hw);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)n * MIL_SEED_SLICES);
+    if (dtype == MIL_DT_BF16)
+        hipLaunchKernelGGL(stage_seed_kernel<BF16>, grid, dim3(FV_THREADS), 0, st, (const __bf16*)act, channels, (__bf16*)dz, ws, (int)hw, per, cp, c,
+                           neg_inv, slope);
+    else
+        hipLaunchKernelGGL(stage_seed_kernel<F32>, grid, dim3(FV_THREADS), 0, st, (const float*)act, channels, (float*)dz, ws, (int)hw, per, cp, c,
+                           neg_inv, slope);
+    MIL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stage_seed_sum_kernel, dim3((n + FV_THREADS - 1) / FV_THREADS), dim3(FV_THREADS), 0, st, ws, objective, n, (float)hw);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+template <int RULE>
+static void launch_pixel_step(int project, dim3 grid, hipStream_t st, float* x, const float* g, float* m, float* v, uint8_t* u8_out,
+                              const float* table, const PixelStepArgs& a, unsigned long long total, int vec) {
+    if (project == 0)
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 0>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+    else if (project == 1)
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 1>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+    else
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 2>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+}
+
+extern "C" int mil_pixel_step(float* x, const float* g, float* m, float* v, unsigned char* u8_out, const float* table, size_t total,
+                              int rule, int project, float lr, float weight_decay, float beta1, float one_minus_beta1, float beta2,
+                              float one_minus_beta2, float bc1, float sqrt_bc2, float eps, void* stream) {
+    if (!x || !g || rule < 0 || rule > 1 || project < 0 || project > 2) return MIL_ERR_ARG;
+    if (rule == 1 && (!m || !v || !(bc1 > 0.f) || !(sqrt_bc2 > 0.f) || !(eps >= 0.f))) return MIL_ERR_ARG;
+    if (project == 2 && !table) return MIL_ERR_ARG;
+    if (!(lr == lr) || !(weight_decay == weight_decay)) return MIL_ERR_ARG;
+    if (total == 0) return MIL_OK;
+    const unsigned long long blocks = (((unsigned long long)total + 3) / 4 + FV_THREADS - 1) / FV_THREADS;
+    if (blocks > INT_MAX) return MIL_ERR_UNSUPPORTED;
+    uintptr_t grid16 = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g);
+    if (rule == 1) grid16 |= reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+    const int vec = !(grid16 & 15) && !(reinterpret_cast<uintptr_t>(u8_out) & 3);
+    const PixelStepArgs a{lr, weight_decay, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, sqrt_bc2, eps};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (rule == 0)
+        launch_pixel_step<0>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
+    else
+        launch_pixel_step<1>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}

@@ -237,8 +237,12 @@ class ResNet(nn.Module):
         return _EncoderFn.apply(self, x, *self.encoder_params())
 
 
-def encoder_forward(net, x, dtype):
-    """Runs the kernels; returns (feats [T,80] fp32, saved-state dict for the backward)."""
+def encoder_forward(net, x, dtype, upto=None):
+    """Runs the kernels; returns (feats [T,80] fp32, saved-state dict for the backward).  upto = 1..4: the forward cut short behind
+    stage `upto` — the stages above it, the average pool and the fc layer do not run, feats is None, `saved["blocks"]` holds the
+    blocks that ran (bit for bit those of the full forward) and an attached `ActivationSummary` is not called."""
+    if upto is not None and upto not in (1, 2, 3, 4):
+        raise ValueError(f"upto must be None or 1..4, got {upto!r}")
     net.refresh_packed(dtype)
     x = x.contiguous()                  # the tensor the kernels read — and, without a kept s2d copy, the one the backward re-reads
     kind = ops.stem_feed_kind(x, dtype)
@@ -275,7 +279,7 @@ def encoder_forward(net, x, dtype):
     saved = {"kind": kind, "xs": xs, "x": x if xs is None else None, "x_src": x if (xs is None or kind == "s2d") else None,
              "x_version": x._version, "stem_hw": stem_hw, "widx": widx, "blocks": [],
              "tile_hw": (2 * x.shape[1], 2 * x.shape[2]) if kind == "s2d" else tuple(x.shape[2:])}
-    return _encoder_forward_body(net, pool, saved, dtype, hk)
+    return _encoder_forward_body(net, pool, saved, dtype, hk, upto)
 
 
 class _Forward:
@@ -349,17 +353,20 @@ def _entry_block_forward(fw, first, stage, t):
     return fw.keep(first, blk, t, o1, out), 1
 
 
-def _encoder_forward_body(net, pool, saved, dtype, hk):
-    """Everything behind the stem: the residual stages, the average pool and the fc layer."""
+def _encoder_forward_body(net, pool, saved, dtype, hk, upto=None):
+    """Everything behind the stem: the residual stages, the average pool and the fc layer — or, with `upto`, the first `upto`
+    stages alone (stages are the cut points: the stage-wide forward chains never span two)."""
     fw = _Forward(net, saved, hk)
     t = pool
-    for first, stage in net.stages():
+    for first, stage in net.stages()[:upto]:
         fw.stage_in = t
         ran = 0
         if stage[0].downsample is not None:
             t, ran = _entry_block_forward(fw, first, stage, t)
         for j in range(ran, len(stage)):
             t = _identity_block_forward(fw, first + j, stage[j], t)
+    if upto is not None:
+        return None, saved
     pooled, feats = ops.avgpool_fc_fwd(t, net.fc.weight.detach(), STAGE_WIDTHS[-1])
     saved["pooled"] = pooled
     if hk is not None:
@@ -384,8 +391,11 @@ class _Backward:
     """One backward pass: what its steps read (the net, the saved activations, the storage dtype), the gradients they leave
     in `grads` under (block, 1 | 2 | 0 for conv1 | conv2 | the projection) or ("stem", 0), and the workspace policy."""
 
-    def __init__(self, net, saved, dtype, allow_direct, want_dx):
+    def __init__(self, net, saved, dtype, allow_direct, want_dx, want_wgrad=True):
         self.net, self.saved, self.dtype, self.want_dx = net, saved, dtype, want_dx
+        # False: a walk that is after the data gradient alone (encoder_pixel_gradient).  The stand-alone weight-gradient launches
+        # are skipped; the one-pass kernels that make the data gradient still run, and what they leave in `grads` is dropped
+        self.want_wgrad = want_wgrad
         self.blocks = list(net.blocks())
         self.grads = {}
         # in-place accumulation into the parameters' .grad: opt-in (dist.FlatParams sets direct_grad; plain loss.backward() only),
@@ -452,7 +462,9 @@ class _Backward:
 
     def wgrad(self, conv, xin, dzz, key, stem=False):
         """dW and db of `conv` from its input and the gradient of its output, left in grads[key].  stem: conv1, which runs as
-        a 4x4 stride-1 conv on the space-to-depth tensor."""
+        a 4x4 stride-1 conv on the space-to-depth tensor.  Not launched without `want_wgrad`."""
+        if not self.want_wgrad:
+            return
         n, h, w, _ = xin.shape
         _, ho, wo, _ = dzz.shape
         cin, cout, bias = conv.in_channels, conv.out_channels, conv.bias
@@ -561,7 +573,7 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
         them is about to run, not before: `_first_stage_dense` queries the library, and those calls keep their place."""
         return net._packed(f"b{bi}.c1", L.PACK_DGRAD_S2)[0], (cin if _first_stage_dense(bw, bi) else None)
 
-    if s == 2 and net.fuse_backward and not net.overlap_wgrad:
+    if s == 2 and net.fuse_backward and not net.overlap_wgrad and bw.want_wgrad:
         # data gradient and both weight gradients in one launch, where there is such a kernel (bf16, the 20 -> 40 and 40 -> 60
         # entries): the same bits as the two launches below
         ws2, dense_cx = s2_operands()
@@ -731,6 +743,51 @@ def encoder_stage_gradient(net, saved, dfeats, dtype, stage):
     if _is_dense(dz, STAGE_WIDTHS[stage - 1]):
         raise RuntimeError("a stage's gradient is returned in the padded layout")
     return dz
+
+
+def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=None, dx_reduce=None, dx_acc=None):
+    """The gradient of the TILES alone, (dx, sal) as `ops.stem_dgrad` returns them: the data-gradient-only walk from a seed to the
+    pixels.  The seed is either `dz`, the gradient of the pre-activation map behind the output of stage `stage` (1..4; what
+    `ops.stage_seed` makes, in that tensor's padded NHWC layout and dtype) for a forward that ran at least that far
+    (`encoder_forward(upto=stage)`), or `dfeats` [T,80], which goes through `ops.avgpool_fc_bwd_data` — the very launch of
+    `ops.avgpool_fc_bwd`'s data half — into stage 4.  Then `_stage_backward` for the stages at and below the seed with
+    `want_wgrad=False`: no `ops.conv_wgrad`, no `conv_wgrad_pair` / `conv_entry_bwd`, no `stem_backward`; the one-pass kernels
+    that make a data gradient still run and their weight gradients are dropped.  Then `ops.maxpool_bwd` and `ops.stem_dgrad`
+    (dx_reduce) or `ops.stem_dgrad_acc` (dx_acc), as `encoder_backward` runs them under want_dx: dx is bit for bit that
+    function's.  Padded gradient layout, `allow_direct=False`: no `.grad` is read or written."""
+    if (dz is None) == (dfeats is None):
+        raise ValueError("the seed is either dz (with its stage) or dfeats")
+    if dx_acc is not None and dx_reduce is not None:
+        raise ValueError("dx_acc accumulates the three-channel gradient: it goes without dx_reduce")
+    stages = net.stages()
+    if dfeats is not None:
+        if stage is not None:
+            raise ValueError("dfeats enters behind the fc layer: it takes no stage")
+        stage = len(stages)
+        if "pooled" not in saved:
+            raise ValueError("dfeats needs the whole forward (encoder_forward without upto)")
+    elif stage not in (1, 2, 3, 4):
+        raise ValueError(f"stage must be 1..4, got {stage!r}")
+    first, blks = stages[stage - 1]
+    if len(saved["blocks"]) < first + len(blks):
+        raise ValueError(f"the forward stopped below stage {stage}")
+    top = saved["blocks"][first + len(blks) - 1][2]
+    if dfeats is not None:
+        dz = ops.avgpool_fc_bwd_data(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], top)
+    elif dz.shape != top.shape or dz.dtype != top.dtype:
+        raise ValueError(f"dz must be like the output of stage {stage}, {tuple(top.shape)} {top.dtype}, got {tuple(dz.shape)} {dz.dtype}")
+    bw = _Backward(net, saved, dtype, False, True, want_wgrad=False)
+    with bw.reductions(dz.device):
+        for below in reversed(stages[:stage]):
+            dz = _stage_backward(bw, below, dz)
+    bw.join()
+    if _is_dense(dz, STEM_WIDTH):
+        raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
+    dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
+    if dx_acc is not None:
+        ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
+        return None, None
+    return ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
 
 
 class _EncoderFn(torch.autograd.Function):

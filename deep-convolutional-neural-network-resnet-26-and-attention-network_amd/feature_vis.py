@@ -1,0 +1,250 @@
+"""Activation maximisation: tiles optimised on the device so that a filter fires or a class is predicted.
+
+The family of the saliency toolkit the reference vendors (pytorch-cnn-visualizations-master/src) that optimises the PIXELS:
+`cnn_layer_visualization.py` — the one toolkit class the reference's driver imports by name (gbm/classify.py:30) — runs gradient
+ascent on a random image so that one filter of one layer fires, `deep_dream.py` does the same from a real image, and
+`generate_class_specific_samples.py` ascends a class score with the image re-quantised to bytes every step.  With the stock model
+each is a Python loop of optimiser steps around a hooked forward, one image at a time.  Here a step is the encoder's forward cut
+short at the stage (`encoder_forward(upto=)`), one launch that reads the objective and writes the seed of the backward pass
+(`ops.stage_seed`), the data-gradient-only walk to the pixels (`encoder_pixel_gradient`: no weight-gradient launch) and one
+launch that takes the optimiser step, projects the image and encodes it (`ops.pixel_step`); one tile carries one filter each, so
+all channels of a stage are optimised in one batch.  DESIGN.md section 3.43.
+"""
+from collections import namedtuple
+
+import torch
+
+from . import _lib as L
+from . import ops
+from .encoder import STAGE_WIDTHS, ResNet, encoder_forward, encoder_pixel_gradient
+from .head import head_apply
+from .preprocess import S2dTiles, U8Tiles
+from .saliency import bag_setup
+
+OPTIMIZERS = ops.PIXEL_RULES
+LAYERS = ("layer1", "layer2", "layer3", "layer4")
+
+FeatureVisResult = namedtuple("FeatureVisResult", ["u8", "x", "trace"])
+FeatureVisResult.__doc__ = """What an optimisation returns: `u8`, the final images as `U8Tiles` (the toolkit's `recreate_image` at this
+project's mean and std of 0.5); `x`, the same images as the fp32 [T,3,H,W] stack that was optimised; `trace` fp32 [steps, T], the
+objective of the image each step STARTED from (the filter's mean activation; minus the bag's loss for `classes`)."""
+
+
+def _stage_of(layer):
+    """1..4 for "layer1".."layer4" or the integer itself."""
+    if isinstance(layer, str):
+        if layer not in LAYERS:
+            raise ValueError(f"layer must be one of {LAYERS} or 1..4, got {layer!r}")
+        return LAYERS.index(layer) + 1
+    if layer not in (1, 2, 3, 4) or isinstance(layer, bool):
+        raise ValueError(f"layer must be one of {LAYERS} or 1..4, got {layer!r}")
+    return int(layer)
+
+
+def _count(v, name, least=1):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < least:
+        raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
+    return int(v)
+
+
+def _size(size):
+    try:
+        h, w = (_count(v, "size") for v in size)
+    except TypeError:
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    return h, w
+
+
+def _channel_list(channels, c, ntiles=None):
+    """One channel in [0, c) per tile as a list of ints; None: all channels of the stage; an int: that channel for every tile."""
+    if channels is None:
+        if ntiles is not None:
+            raise ValueError("channels: one per tile, or one int for all tiles")
+        channels = range(c)
+    elif isinstance(channels, int) and not isinstance(channels, bool):
+        channels = [channels] * (1 if ntiles is None else ntiles)
+    elif isinstance(channels, torch.Tensor):
+        channels = channels.tolist()
+    try:
+        out = [int(k) for k in channels]
+        exact = all(int(k) == k and not isinstance(k, bool) for k in channels)
+    except (TypeError, ValueError):
+        raise ValueError(f"channels must be integers, got {channels!r}") from None
+    if not out or not exact:
+        raise ValueError(f"channels must be a non-empty list of integers, got {list(channels)!r}")
+    if ntiles is not None and len(out) != ntiles:
+        raise ValueError(f"{len(out)} channels for {ntiles} tiles")
+    bad = [k for k in out if not 0 <= k < c]
+    if bad:
+        raise ValueError(f"channels must lie in [0, {c}), got {bad}")
+    return out
+
+
+def _init_range(init):
+    try:
+        lo, hi = (int(v) for v in init)
+    except (TypeError, ValueError):
+        raise ValueError(f"init must be (lo, hi), a range of byte values, got {init!r}") from None
+    if not 0 <= lo < hi <= 256:
+        raise ValueError(f"init must satisfy 0 <= lo < hi <= 256, got {init!r}")
+    return lo, hi
+
+
+def _check_stack(tiles):
+    if isinstance(tiles, S2dTiles):
+        raise ValueError("S2dTiles hold bf16-rounded space-to-depth records: feature visualisation takes the fp32 stack or U8Tiles")
+    if not isinstance(tiles, (torch.Tensor, U8Tiles)):
+        raise ValueError(f"tiles must be an fp32 [T,3,H,W] tensor or U8Tiles, got {type(tiles).__name__}")
+    if tiles.dim() != 4 or tiles.shape[1] != 3:
+        raise ValueError(f"expected [T,3,H,W] tiles, got {tuple(tiles.shape)}")
+    if isinstance(tiles, torch.Tensor) and not tiles.is_floating_point():
+        raise ValueError(f"a tensor of tiles must be floating point (wrap uint8 images in U8Tiles), got {tiles.dtype}")
+    if tiles.shape[0] < 1:
+        raise ValueError("no tiles")
+
+
+class FeatureVisualizer:
+    """`FeatureVisualizer(model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none")` —
+    the defaults are the toolkit's `Adam([image], lr=0.1, weight_decay=1e-6)` (cnn_layer_visualization.py:45).  `model`: a
+    `mil_amd.Attention` with the narrow ResNet-26, or that `ResNet` itself for the filter methods.
+
+      filters(layer, channels=None, size=(256, 256), steps=30, init=(150, 180), seed=0)
+          one tile per channel (None: every channel of the stage), each optimised from random bytes so that its channel of
+          `layer`'s output has a large mean: `cnn_layer_visualization.py`.  The start bytes are `torch.randint(lo, hi)` of a CPU
+          generator seeded with `seed` — the toolkit's `uniform(150, 180)`; the global generators are not drawn from and the
+          bytes are the same on every machine.
+      dream(tiles, layer, channels, steps=250)
+          the same objective started from real tiles (an fp32 stack or `U8Tiles`, left untouched): `deep_dream.py`.  `channels`:
+          an int or one per tile.
+      classes(label, ntiles, size=(256, 256), steps=150, init=(0, 256), seed=0)
+          a bag of `ntiles` >= 2 generated tiles that minimises the bag's loss for `label`, the head evaluated as
+          `TileSaliency` evaluates it (eval mode).  `FeatureVisualizer(model, "sgd", lr=6, weight_decay=0, project="u8")` with
+          init=(0, 256) is `generate_class_specific_samples.py`: plain SGD at lr 6 on an image that is re-created as bytes and
+          re-read every step (there the objective is minus the class logit, here the bag's loss).
+      objective(tiles, layer, channels) -> fp32 [T]: the mean of each tile's channel, one truncated forward.
+
+    The optimising methods return a `FeatureVisResult` (u8, x, trace).  The target is the stage's output BEHIND its last
+    LeakyReLU — the tensor the forward keeps, and what a forward hook on the reference's `layerN` would see.  project: "none"
+    (the layer visualisation), "clamp" (to [-1, 1]) or "u8" (the class-specific method's round trip through bytes).  A step is
+    four groups of launches with no host synchronisation between them; all three compute modes and every tile size the encoder
+    takes.  A call leaves the model as it found it, as `TileSaliency` does: the `training` flag, every `.grad`, the torch RNG
+    states and a `FlatParams` bucket are not touched."""
+
+    def __init__(self, model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none"):
+        from . import alt_resnet
+        from .model import Attention
+        if isinstance(model, Attention):
+            net = model.cnn.module
+        elif isinstance(model, (ResNet, alt_resnet.ResNet)):
+            net = model
+        else:
+            raise ValueError("FeatureVisualizer takes a mil_amd.Attention model or its narrow ResNet encoder")
+        if not isinstance(net, ResNet):
+            raise ValueError("FeatureVisualizer needs the narrow ResNet-26 encoder: the wide encoder (alt_resnet) has no stem data-gradient kernel")
+        if project not in ops.PIXEL_PROJECTIONS:
+            raise ValueError(f"project must be one of {ops.PIXEL_PROJECTIONS}, got {project!r}")
+        try:
+            betas = tuple(float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError(f"betas must be two numbers, got {betas!r}") from None
+        if len(betas) != 2:
+            raise ValueError(f"betas must be two numbers, got {betas!r}")
+        ops.pixel_step_scalars(optimizer, lr, weight_decay, betas, eps, 1)
+        self.model = model if isinstance(model, Attention) else None
+        self.net = net
+        self.optimizer, self.lr, self.weight_decay, self.betas, self.eps = optimizer, float(lr), float(weight_decay), betas, float(eps)
+        self.project = project
+
+    # ---- pieces ------------------------------------------------------------------------------------------------------------
+    def _device(self):
+        dev = self.net.conv1.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("FeatureVisualizer runs on an AMD GPU only (module parameters are not on a CUDA/HIP device)")
+        return dev
+
+    def _start(self, ntiles, size, init, seed):
+        """Random start bytes [ntiles,3,H,W] from a generator of their own, as the fp32 stack they decode to, on the device."""
+        gen = torch.Generator().manual_seed(int(seed))
+        u8 = torch.randint(init[0], init[1], (ntiles, 3, size[0], size[1]), generator=gen, dtype=torch.uint8)
+        return U8Tiles(u8.to(self._device())).float()
+
+    def _step(self, x, g, state, k, last, u8):
+        ops.pixel_step(x, g, state, rule=self.optimizer, lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
+                       step=k + 1, project=self.project, u8_out=u8 if last else None)
+
+    def _state(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x)) if self.optimizer == "adam" else None
+
+    def _ascend(self, x, stage, chans, steps):
+        """`steps` steps on x (fp32 on the device, optimised in place) for channel chans[t] of stage `stage`."""
+        net, mode = self.net, self.net.compute_dtype
+        dtype = L.storage_dtype(mode)
+        c = STAGE_WIDTHS[stage - 1]
+        ch = torch.tensor(chans, dtype=torch.int32).to(x.device)
+        trace = torch.empty((steps, x.shape[0]), dtype=torch.float32, device=x.device)
+        u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        state = self._state(x)
+        with torch.no_grad(), L.f32_mma(L.mma_code(mode)):
+            for k in range(steps):
+                _feats, saved = encoder_forward(net, x, dtype, upto=stage)
+                _j, dz = ops.stage_seed(saved["blocks"][-1][2], ch, c, objective=trace[k])
+                g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
+                self._step(x, g, state, k, k == steps - 1, u8)
+        return FeatureVisResult(U8Tiles(u8), x, trace)
+
+    # ---- methods -----------------------------------------------------------------------------------------------------------
+    def filters(self, layer, channels=None, size=(256, 256), steps=30, init=(150, 180), seed=0):
+        stage = _stage_of(layer)
+        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1])
+        size, steps, init = _size(size), _count(steps, "steps"), _init_range(init)
+        return self._ascend(self._start(len(chans), size, init, seed), stage, chans, steps)
+
+    def dream(self, tiles, layer, channels, steps=250):
+        stage = _stage_of(layer)
+        _check_stack(tiles)
+        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
+        steps = _count(steps, "steps")
+        dev = self._device()
+        x = tiles.to(dev).float() if isinstance(tiles, U8Tiles) else tiles.detach().to(dev, torch.float32, copy=True).contiguous()
+        return self._ascend(x, stage, chans, steps)
+
+    def objective(self, tiles, layer, channels):
+        stage = _stage_of(layer)
+        _check_stack(tiles)
+        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
+        dev = self._device()
+        net, mode = self.net, self.net.compute_dtype
+        x = tiles.u8.to(dev) if isinstance(tiles, U8Tiles) else tiles.detach().to(dev, torch.float32)
+        ch = torch.tensor(chans, dtype=torch.int32).to(dev)
+        with torch.no_grad(), L.f32_mma(L.mma_code(mode)):
+            _feats, saved = encoder_forward(net, x, L.storage_dtype(mode), upto=stage)
+            return ops.stage_seed(saved["blocks"][-1][2], ch, STAGE_WIDTHS[stage - 1])[0]
+
+    def classes(self, label, ntiles, size=(256, 256), steps=150, init=(0, 256), seed=0):
+        model = self.model
+        if model is None:
+            raise ValueError("classes() optimises the bag's loss: it needs the mil_amd.Attention model, not the bare encoder")
+        if isinstance(label, bool) or not isinstance(label, int) or not 0 <= label < model.C:
+            raise ValueError(f"label must be in [0, {model.C}), got {label!r}")
+        ntiles = _count(ntiles, "ntiles", 2)
+        size, steps, init = _size(size), _count(steps, "steps"), _init_range(init)
+        x = self._start(ntiles, size, init, seed)
+        net, mode = self.net, self.net.compute_dtype
+        dtype = L.storage_dtype(mode)
+        layout, y, cw = bag_setup(model, ntiles, int(label))
+        weights = [w.detach() for w in model.head_weights()]
+        trace = torch.empty((steps, ntiles), dtype=torch.float32, device=x.device)
+        u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        state = self._state(x)
+        with L.f32_mma(L.mma_code(mode)):
+            for k in range(steps):
+                with torch.no_grad():
+                    feats, saved = encoder_forward(net, x, dtype)
+                H = feats.detach().requires_grad_(True)
+                loss = head_apply(H, layout, y, None, cw, weights, None, direct=False)[0]
+                (dH,) = torch.autograd.grad(loss.sum(), H)
+                with torch.no_grad():
+                    trace[k] = -loss.detach()
+                    g, _sal = encoder_pixel_gradient(net, saved, dtype, dfeats=dH)
+                    self._step(x, g, state, k, k == steps - 1, u8)
+        return FeatureVisResult(U8Tiles(u8), x, trace)

@@ -775,8 +775,93 @@ def attr_finish(acc, tiles, base, *, want_attr=True, want_map=False, map_mode="s
     return attr, amap, sums
 
 
+def stage_seed(act, channels, c, *, objective=None, dz=None, slope=LEAK):
+    """Objective and seed gradient of activation maximisation at a stage output (see mil_stage_seed): act [T,h,w,cpad(c)] — the
+    stage's output as the forward keeps it, bf16 or fp32 — and channels, int32 [T] on the device, one channel in [0, c) per tile
+    -> (objective fp32 [T] = the mean of each tile's channel, dz like act = the gradient of MINUS that mean with respect to the
+    pre-activation map: -(1/(h w)) lrelu'(act) at the tile's channel, zero elsewhere).  `objective` / `dz`: the caller's own
+    output tensors (checked) — a row of a trace, for one."""
+    if not isinstance(act, torch.Tensor) or act.dim() != 4:
+        raise ValueError(f"act must be [T,h,w,cp], got {tuple(getattr(act, 'shape', ()))}")
+    n, h, w, cp = act.shape
+    c = int(c)
+    if cp != cpad(c) or c < 1:
+        raise ValueError(f"{c} real channels go with {cpad(c)} stored ones, got {cp}")
+    if h < 1 or w < 1:
+        raise ValueError(f"maps of {h}x{w}")
+    code = L.dt_code(act.dtype)
+    _need(act, act.shape, act.dtype, "act")
+    if not isinstance(channels, torch.Tensor):
+        raise ValueError("channels must be an int32 [T] tensor on the device")
+    _need(channels, (n,), torch.int32, "channels")
+    if objective is None:
+        objective = torch.empty((n,), dtype=torch.float32, device=act.device)
+    _need(objective, (n,), torch.float32, "objective")
+    if dz is None:
+        dz = torch.empty_like(act)
+    _need(dz, act.shape, act.dtype, "dz")
+    ws = torch.empty((n, L.SEED_SLICES), dtype=torch.float32, device=act.device)
+    _launch("mil_stage_seed", ("stage_seed", n, h, w, cp), act.data_ptr(), channels.data_ptr(), objective.data_ptr(), dz.data_ptr(),
+            ws.data_ptr(), n, h, w, cp, c, slope, code, L.stream_ptr())
+    return objective, dz
+
+
+PIXEL_RULES = ("sgd", "adam")                     # mil_pixel_step's rule 0, 1
+PIXEL_PROJECTIONS = ("none", "clamp", "u8")       # mil_pixel_step's project 0, 1, 2
+
+
+def pixel_step_scalars(rule, lr, weight_decay, betas, eps, step):
+    """The nine fp32 scalars of mil_pixel_step — (lr, wd, beta1, 1 - beta1, beta2, 1 - beta2, bc1, sqrt(bc2), eps) — checked;
+    the differences, powers and the root are taken in double here and rounded once by the call."""
+    if rule not in PIXEL_RULES:
+        raise ValueError(f"rule must be one of {PIXEL_RULES}, got {rule!r}")
+    lr, wd, eps = float(lr), float(weight_decay), float(eps)
+    b1, b2 = (float(b) for b in betas)
+    if lr != lr or not wd >= 0.0:
+        raise ValueError(f"lr must be a number and weight_decay >= 0, got {lr} and {wd}")
+    if int(step) != step or step < 1:
+        raise ValueError(f"step counts from 1, got {step!r}")
+    if rule == "adam" and not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps >= 0.0):
+        raise ValueError(f"betas must lie in [0, 1) and eps be >= 0, got {betas!r} and {eps}")
+    bc1, bc2 = 1.0 - b1 ** int(step), 1.0 - b2 ** int(step)
+    return lr, wd, b1, 1.0 - b1, b2, 1.0 - b2, bc1, bc2 ** 0.5, eps
+
+
+def pixel_step(x, g, state=None, *, rule="adam", lr=0.1, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, step=1, project="none",
+               u8_out=None):
+    """One optimiser step on the images x [T,3,H,W] fp32 for the gradient g, in place and in one pass (see mil_pixel_step).
+    rule="sgd": `torch.optim.SGD` without momentum; rule="adam": `torch.optim.Adam` with its coupled L2 decay, `state` = (m, v),
+    two fp32 tensors like x that are updated in place, `step` counting from 1.  project: "none", "clamp" (to [-1, 1]) or "u8"
+    (the round trip x <- decode(encode(x)) through the table `U8Tiles.float()` looks up).  u8_out: a uint8 tensor like x that
+    receives encode(x) = rint(clip(x / 2 + 0.5, 0, 1) * 255) of the value stored.  Returns x."""
+    if project not in PIXEL_PROJECTIONS:
+        raise ValueError(f"project must be one of {PIXEL_PROJECTIONS}, got {project!r}")
+    scalars = pixel_step_scalars(rule, lr, weight_decay, betas, eps, step)
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"x must be fp32 [T,3,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    m = v = None
+    if rule == "adam":
+        if state is None or len(state) != 2 or state[0] is None or state[1] is None:
+            raise ValueError("rule='adam' keeps two moments: state = (m, v), fp32 tensors like x")
+        m, v = state
+    elif state is not None:
+        raise ValueError("rule='sgd' keeps no state")
+    _need(x, x.shape, torch.float32, "x")
+    _need(g, x.shape, torch.float32, "g")
+    _need(m, x.shape, torch.float32, "m")
+    _need(v, x.shape, torch.float32, "v")
+    _need(u8_out, x.shape, torch.uint8, "u8_out")
+    table = None
+    if project == "u8":
+        from .preprocess import U8Tiles
+        table = U8Tiles.decode_table(x.device)
+    _launch("mil_pixel_step", ("pixel_step", x.numel(), rule, project, u8_out is not None), x.data_ptr(), g.data_ptr(), L.ptr(m), L.ptr(v),
+            L.ptr(u8_out), L.ptr(table), x.numel(), PIXEL_RULES.index(rule), PIXEL_PROJECTIONS.index(project), *scalars, L.stream_ptr())
+    return x
+
+
 QUANTILE_GROUPS = ("tile", "bag")
-RENDER_MODES = ("grayscale", "colour", "pos_neg")     # mil_attr_render's mode 0, 1, 2
+RENDER_MODES =("grayscale", "colour", "pos_neg")     # mil_attr_render's mode 0, 1, 2
 MapStats = collections.namedtuple("MapStats", "stats p group")
 MapStats.__doc__ = """What `map_quantile` returns: stats [G,4] fp32 = (min, max, s[lo], s[hi]) and p [G] fp64 per group (G = T for
 group "tile", 1 for "bag"), on the device."""

@@ -85,16 +85,21 @@ class U8Tiles:
 
     _decode_tables = {}
 
-    def float(self):
-        """The fp32 [T,3,H,W] tensor the handle stands for: `((u8.float() / 255) - 0.5) / 0.5` as the CPU computes it (IEEE
-        division — the definition of the decode).  The 256 values are computed once, on the host, and looked up on the
-        handle's device: a GPU's own elementwise division need not round as the host's does."""
-        dev = self.u8.device
+    @staticmethod
+    def decode_table(device):
+        """The 256 fp32 values of the decode on `device`: computed once, on the host, and cached per device."""
+        dev = torch.device(device)
         tab = U8Tiles._decode_tables.get(dev)
         if tab is None:
             tab = (((torch.arange(256, dtype=torch.uint8).float() / 255) - 0.5) / 0.5).to(dev)
             U8Tiles._decode_tables[dev] = tab
-        return tab[self.u8.to(torch.int32)]
+        return tab
+
+    def float(self):
+        """The fp32 [T,3,H,W] tensor the handle stands for: `((u8.float() / 255) - 0.5) / 0.5` as the CPU computes it (IEEE
+        division — the definition of the decode).  The 256 values are computed once, on the host, and looked up on the
+        handle's device: a GPU's own elementwise division need not round as the host's does."""
+        return U8Tiles.decode_table(self.u8.device)[self.u8.to(torch.int32)]
 
     def __len__(self):
         return self.u8.shape[0]

@@ -504,6 +504,42 @@ int mil_path_point(const void* tiles, int is_u8, float* out, float base0, float 
 int mil_attr_finish(const float* acc, const void* tiles, int is_u8, float base0, float base1, float base2, float* attr, float* map,
                     int map_mode, float* tile_sum, float* ws, int n, int H, int W, void* stream);
 
+/* Activation maximisation (`cnn_layer_visualization.py`, `deep_dream.py`, `generate_class_specific_samples.py` of the same toolkit):
+ * the objective "one channel of a stage's output, averaged over the map" and the seed of its backward pass.
+ *     act [n,h,w,cp]  a stage's output as the forward keeps it (behind the block's LeakyReLU), MIL_DT_BF16 or MIL_DT_F32, c real channels
+ *     channels [n]    DEVICE int32, one channel per tile, 0 <= channels[t] < c (a value outside selects nothing: J = 0, dz = 0; no
+ *                     address is formed from it)
+ *     objective [n]   J_t = (sum over y,x of act[t,y,x,channels[t]]) / (h w), fp32
+ *     dz [n,h,w,cp]   the gradient of the LOSS -J_t with respect to the PRE-activation map, the form the backward chain carries:
+ *                     dz[t,y,x,k] = (-(1 / (h w))) * (act > 0 ? 1 : slope) for k == channels[t], 0 for every other k (padding included);
+ *                     1 / (h w) is one fp32 division on the host, the product one fp32 multiplication, rounded to bf16 where dz is bf16
+ * Every element of dz and objective is written; neither is read.  The sum has a fixed order: each of MIL_SEED_SLICES workgroups per
+ * tile sums its pixels into ws [n * MIL_SEED_SLICES] fp32, a second small launch adds a tile's partial sums in slice order and divides
+ * by h w (one correctly rounded division).  No atomics: two calls give the same bits.  Null pointers, n < 0, h or w < 1, cp not a
+ * positive multiple of 8, c outside [1, cp], another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch; h w of 2^24 or more or one map
+ * of 2^31 elements or more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+#define MIL_SEED_SLICES 16
+int mil_stage_seed(const void* act, const int* channels, float* objective, void* dz, float* ws, int n, int h, int w, int cp, int c,
+                   float slope, int dtype, void* stream);
+
+/* One optimiser step on an image stack, in place, in one pass: x, g, m, v fp32 with `total` elements each.  With g' = g + wd * x:
+ *     rule 0 (torch.optim.SGD, no momentum):   x <- x - lr * g'                                  (m, v not read, may be NULL)
+ *     rule 1 (torch.optim.Adam, coupled decay): m <- beta1 * m + one_minus_beta1 * g'
+ *                                               v <- beta2 * v + (one_minus_beta2 * g') * g'
+ *                                               x <- x - ((lr / bc1) * m) / (sqrt(v) / sqrt_bc2 + eps)
+ * with bc1 = 1 - beta1^step, sqrt_bc2 = sqrt(1 - beta2^step), one_minus_beta = 1 - beta formed by the caller in double and passed as
+ * fp32.  Then the projection of the new x:  project 0: none;  1: clamp to [-1, 1];  2: x <- table[encode(x)], the round trip through
+ * bytes, table a DEVICE float[256] (the values of mil_u8_decode_table).  u8_out (NULL: not made) [total] = encode(x) of the value
+ * stored, encode(x) = rint(clip(x / 2 + 0.5, 0, 1) * 255), half to even (np.round).  Every product, quotient, sum and difference
+ * is a single correctly rounded fp32 operation in the order written, none fused: the same expressions in numpy fp32 give the same
+ * bits.  16-byte accesses where every pointer is on its 16-byte (u8_out: 4-byte) grid, element by element otherwise and in a last
+ * short group.  Null x / g, rule or project outside their range, rule 1 without m and v or with bc1 or sqrt_bc2 <= 0 or eps < 0,
+ * project 2 without table, lr or wd NaN: MIL_ERR_ARG; total == 0: MIL_OK, no launch; more than 2^31 - 1 workgroups of 1024 elements:
+ * MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+int mil_pixel_step(float* x, const float* g, float* m, float* v, unsigned char* u8_out, const float* table, size_t total, int rule,
+                   int project, float lr, float weight_decay, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float bc1, float sqrt_bc2, float eps, void* stream);
+
 /* Order statistics of attribution maps: what `convert_to_grayscale` of the same toolkit's misc_functions.py takes with np.min and
  * np.percentile(., 99).  x [n,channels,H,W] fp32: channels == 3 ranks gray = (|g0| + |g1|) + |g2| (fp32, numpy's axis-0 order),
  * channels == 1 ranks the map itself.  A group is one tile (bag == 0; n groups of H W values) or the whole bag (bag == 1; one group
