@@ -13,6 +13,7 @@
 // top.  A NaN orders by its bits: above +inf with the sign bit clear, below -inf with it set.  All counts are integers and
 // are merged with integer atomics, so two calls give the same bits.
 #include "common.cuh"
+#include "rounded.cuh"
 #include <climits>
 
 #define AQ_THREADS 256
@@ -28,40 +29,6 @@
 #define AQ_MAX 4                          // largest key, and the complement of the smallest (both start at zero)
 #define AQ_NMIN 5
 
-// single correctly rounded operations that a neighbouring product or sum may not fuse with
-__device__ __forceinline__ float ar_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float ar_sub(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ float ar_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float ar_div(float a, float b) {
-#pragma clang fp contract(off)
-    return a / b;
-}
-__device__ __forceinline__ double ar_dadd(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ double ar_dsub(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ double ar_dmul(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double ar_ddiv(double a, double b) {
-#pragma clang fp contract(off)
-    return a / b;
-}
-
 __device__ __forceinline__ unsigned aq_key(float v) {
     unsigned u = __float_as_uint(v);
     if (u == 0x80000000u) u = 0u;
@@ -72,7 +39,7 @@ __device__ __forceinline__ float aq_unkey(unsigned k) {
 }
 
 // convert_to_grayscale's np.sum(np.abs(g), axis=0): (|g0| + |g1|) + |g2|
-__device__ __forceinline__ float ar_gray(float g0, float g1, float g2) { return ar_add(ar_add(fabsf(g0), fabsf(g1)), fabsf(g2)); }
+__device__ __forceinline__ float ar_gray(float g0, float g1, float g2) { return rn_add(rn_add(fabsf(g0), fabsf(g1)), fabsf(g2)); }
 
 // Four consecutive pixels p .. p + 3 (cnt of them inside the tile) of plane `plane`; whole: one aligned 16-byte load.
 __device__ __forceinline__ void ar_load4(const float* __restrict__ x, size_t plane, int hw, int p, int cnt, bool whole, float (&v)[4]) {
@@ -240,8 +207,8 @@ __global__ __launch_bounds__(AQ_THREADS) void aq_select_kernel(unsigned* __restr
     S[AQ_PLO] = klo; S[AQ_PHI] = khi; S[AQ_RLO] = found[1]; S[AQ_RHI] = found[3];
     if (pass != 2) return;
     const float slo = aq_unkey(klo), shi = aq_unkey(khi);
-    const double d = ar_dsub((double)shi, (double)slo);
-    const double p = tfrac < 0.5 ? ar_dadd((double)slo, ar_dmul(d, tfrac)) : ar_dsub((double)shi, ar_dmul(d, ar_dsub(1.0, tfrac)));
+    const double d = rn_dsub((double)shi, (double)slo);
+    const double p = tfrac < 0.5 ? rn_dadd((double)slo, rn_dmul(d, tfrac)) : rn_dsub((double)shi, rn_dmul(d, rn_dsub(1.0, tfrac)));
     float* st = stats + (size_t)blockIdx.x * 4;
     st[0] = aq_unkey(~knmin); st[1] = aq_unkey(kmax); st[2] = slo; st[3] = shi;
     pout[blockIdx.x] = p;
@@ -312,13 +279,13 @@ __global__ __launch_bounds__(AQ_THREADS) void attr_render_kernel(const float* __
     if constexpr (MODE == 0) {
         float v[4];
         ar_values4<C>(x, t, hw, p, cnt, whole, v);
-        const double dmn = (double)mn, den = ar_dsub(pq[g], dmn);
+        const double dmn = (double)mn, den = rn_dsub(pq[g], dmn);
         unsigned b[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            double r = ar_ddiv(ar_dsub((double)v[j], dmn), den);
+            double r = rn_ddiv(rn_dsub((double)v[j], dmn), den);
             r = r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);                       // np.clip; a NaN passes and converts to 0
-            b[j] = den == 0.0 ? 0u : ((unsigned)(int)ar_dmul(255.0, r) & 255u);
+            b[j] = den == 0.0 ? 0u : ((unsigned)(int)rn_dmul(255.0, r) & 255u);
         }
         ar_store_gray(out0, at, b, cnt, whole);
     } else {
@@ -327,12 +294,12 @@ __global__ __launch_bounds__(AQ_THREADS) void attr_render_kernel(const float* __
         for (int c = 0; c < 3; ++c) ar_load4(x, t * 3 + c, hw, p, cnt, whole, gch[c]);
         unsigned b0[3][4], b1[3][4];
         if constexpr (MODE == 1) {
-            const float span = ar_sub(mx, mn);
+            const float span = rn_sub(mx, mn);
 #pragma unroll
             for (int c = 0; c < 3; ++c)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    b0[c][j] = span == 0.f ? 0u : ar_byte(ar_mul(ar_div(ar_sub(gch[c][j], mn), span), 255.f));
+                    b0[c][j] = span == 0.f ? 0u : ar_byte(rn_mul(rn_div(rn_sub(gch[c][j], mn), span), 255.f));
             ar_store_rgb(out0, at, b0, cnt, whole);
         } else {
             const float nmn = -mn;
@@ -342,8 +309,8 @@ __global__ __launch_bounds__(AQ_THREADS) void attr_render_kernel(const float* __
                 for (int j = 0; j < 4; ++j) {
                     const float v = gch[c][j];
                     // np.maximum(0, g) and np.maximum(0, -g)
-                    b0[c][j] = mx > 0.f ? ar_byte(ar_mul(ar_div(v > 0.f ? v : 0.f, mx), 255.f)) : 0u;
-                    b1[c][j] = nmn > 0.f ? ar_byte(ar_mul(ar_div(-v > 0.f ? -v : 0.f, nmn), 255.f)) : 0u;
+                    b0[c][j] = mx > 0.f ? ar_byte(rn_mul(rn_div(v > 0.f ? v : 0.f, mx), 255.f)) : 0u;
+                    b1[c][j] = nmn > 0.f ? ar_byte(rn_mul(rn_div(-v > 0.f ? -v : 0.f, nmn), 255.f)) : 0u;
                 }
             ar_store_rgb(out0, at, b0, cnt, whole);
             ar_store_rgb(out1, at, b1, cnt, whole);

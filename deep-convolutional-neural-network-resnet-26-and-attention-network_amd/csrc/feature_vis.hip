@@ -8,30 +8,13 @@
 //   pixel_step_kernel<RULE, PROJ> one SGD or Adam step on x [T,3,H,W] fp32 in place, the projection of the new image (none,
 //                                 clamp to [-1,1], or the round trip through bytes) and its bytes, in one pass
 //
-// Every product, quotient, difference and sum that reaches an output is a single correctly rounded fp32 operation (fv_mul, fv_add,
-// fv_sub below carry no `contract` flag; __fdiv_rn, fv_sqrt): numpy's fp32 arithmetic gives the same bits.  Both are streaming
+// Every product, quotient, difference and sum that reaches an output is a single correctly rounded fp32 operation (rn_mul, rn_add,
+// rn_sub of rounded.cuh carry no `contract` flag; __fdiv_rn, rn_sqrt): numpy's fp32 arithmetic gives the same bits.  Both are streaming
 // kernels: 16-byte loads and stores where the pointers allow, no LDS beyond four words of the block sum, no atomics, every sum in
 // a fixed order.
 #include "common.cuh"
+#include "rounded.cuh"
 #include <climits>
-
-__device__ __forceinline__ float fv_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float fv_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float fv_sub(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
-// The correctly rounded square root: llvm.sqrt.f32, which hipcc lowers to the refined sequence unless it is told otherwise
-// (-fhip-fp32-correctly-rounded-divide-sqrt, its default; the Makefile passes no fast-math flag).  HIP's own __fsqrt_rn is
-// __ocml_native_sqrt_f32 in this toolchain — the bare v_sqrt_f32, one ulp — and does not give numpy's bits.
-__device__ __forceinline__ float fv_sqrt(float a) { return __builtin_sqrtf(a); }
 
 #define FV_THREADS 256
 #define MIL_SEED_SLICES 16              // include/mil_hip.h: partial sums per tile of mil_stage_seed
@@ -60,34 +43,34 @@ __global__ __launch_bounds__(FV_THREADS) void stage_seed_kernel(const typename T
         float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (cg == cg_t) {
             const float a = (float)act[off + cj];
-            sum = fv_add(sum, a);
-            const float g = fv_mul(neg_inv, lrelu_grad(a, slope));
+            sum = rn_add(sum, a);
+            const float g = rn_mul(neg_inv, lrelu_grad(a, slope));
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = j == cj ? g : 0.f;
         }
         store8<T>(dz + off, v);
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum = fv_add(sum, __shfl_xor(sum, d));
+    for (int d = 32; d > 0; d >>= 1) sum = rn_add(sum, __shfl_xor(sum, d));
     if ((tid & 63) == 0) red[tid >> 6] = sum;
     __syncthreads();
-    if (tid == 0) part[t * MIL_SEED_SLICES + s] = fv_add(fv_add(fv_add(red[0], red[1]), red[2]), red[3]);
+    if (tid == 0) part[t * MIL_SEED_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
 }
 
 __global__ __launch_bounds__(FV_THREADS) void stage_seed_sum_kernel(const float* __restrict__ part, float* __restrict__ objective, int n, float hw) {
     const int t = blockIdx.x * FV_THREADS + threadIdx.x;
     if (t >= n) return;
     float s = 0.f;
-    for (int k = 0; k < MIL_SEED_SLICES; ++k) s = fv_add(s, part[(size_t)t * MIL_SEED_SLICES + k]);
+    for (int k = 0; k < MIL_SEED_SLICES; ++k) s = rn_add(s, part[(size_t)t * MIL_SEED_SLICES + k]);
     objective[t] = __fdiv_rn(s, hw);
 }
 
 // rint(clip(x / 2 + 0.5, 0, 1) * 255): x / 2 is exact, the sum and the product are rounded once each, the rounding to an integer is
 // half-to-even (np.round).  A NaN encodes as 0.
 __device__ __forceinline__ unsigned fv_encode(float x) {
-    float y = fv_add(fv_mul(x, 0.5f), 0.5f);
+    float y = rn_add(rn_mul(x, 0.5f), 0.5f);
     y = y > 0.f ? (y > 1.f ? 1.f : y) : 0.f;
-    return (unsigned)rintf(fv_mul(y, 255.0f));
+    return (unsigned)rintf(rn_mul(y, 255.0f));
 }
 
 struct PixelStepArgs {
@@ -128,15 +111,15 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
     unsigned codes = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float gd = fv_add(gv[j], fv_mul(a.wd, xv[j]));
+        const float gd = rn_add(gv[j], rn_mul(a.wd, xv[j]));
         float xn;
         if constexpr (RULE == 0) {
-            xn = fv_sub(xv[j], fv_mul(a.lr, gd));
+            xn = rn_sub(xv[j], rn_mul(a.lr, gd));
         } else {
-            mv[j] = fv_add(fv_mul(a.beta1, mv[j]), fv_mul(a.omb1, gd));
-            vv[j] = fv_add(fv_mul(a.beta2, vv[j]), fv_mul(fv_mul(a.omb2, gd), gd));
-            const float denom = fv_add(__fdiv_rn(fv_sqrt(vv[j]), a.sqrt_bc2), a.eps);
-            xn = fv_sub(xv[j], __fdiv_rn(fv_mul(__fdiv_rn(a.lr, a.bc1), mv[j]), denom));
+            mv[j] = rn_add(rn_mul(a.beta1, mv[j]), rn_mul(a.omb1, gd));
+            vv[j] = rn_add(rn_mul(a.beta2, vv[j]), rn_mul(rn_mul(a.omb2, gd), gd));
+            const float denom = rn_add(__fdiv_rn(rn_sqrt(vv[j]), a.sqrt_bc2), a.eps);
+            xn = rn_sub(xv[j], __fdiv_rn(rn_mul(__fdiv_rn(a.lr, a.bc1), mv[j]), denom));
         }
         if constexpr (PROJ == 1) xn = xn < -1.f ? -1.f : (xn > 1.f ? 1.f : xn);
         unsigned code = 0;

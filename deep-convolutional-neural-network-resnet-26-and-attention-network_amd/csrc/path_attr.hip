@@ -8,8 +8,8 @@
 //   attr_sum_kernel          the 32 partial sums of a tile added in slice order: tile_sum [T]
 //
 // v is the fp32 tile value or mil_u8_decode(code) of a uint8 tile (u8_feed.cuh: bit for bit `U8Tiles.float()`).  Every
-// product, difference and sum that reaches an output is a single correctly rounded fp32 operation (pa_sub, pa_mul,
-// pa_add below, compiled with contraction off: no product meets a sum in a fused multiply-add), so torch's fp32 arithmetic
+// product, difference and sum that reaches an output is a single correctly rounded fp32 operation (rn_sub, rn_mul,
+// rn_add of rounded.cuh, compiled with contraction off: no product meets a sum in a fused multiply-add), so torch's fp32 arithmetic
 // on the CPU gives the same bits.
 //
 // The noise is counter-based: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
@@ -20,22 +20,8 @@
 // four words of the block sum, no atomics, every sum in a fixed order.
 #include "common.cuh"
 #include "u8_feed.cuh"
+#include "rounded.cuh"
 #include <climits>
-
-// HIP's own __fmul_rn / __fadd_rn are plain operators compiled with contraction allowed: a product feeding a sum becomes one
-// v_fma_f32.  These three carry no `contract` flag.
-__device__ __forceinline__ float pa_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float pa_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float pa_sub(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
 
 #define PA_THREADS 256
 #define MIL_ATTR_SLICES 32              // include/mil_hip.h: partial sums per tile of mil_attr_finish
@@ -56,12 +42,12 @@ __device__ __forceinline__ void pa_philox4x32_10(unsigned c0, unsigned c1, unsig
 // Two standard normals from two words: u1 = ((a >> 8) + 1) 2^-24 in (0, 1], u2 = (b >> 8) 2^-24 in [0, 1); both exact in fp32,
 // as is 2 u2.  u1 == 1: log = 0, the radius and both normals are zeros.
 __device__ __forceinline__ void pa_box_muller(unsigned a, unsigned b, float& n0, float& n1) {
-    const float u1 = pa_mul((float)((a >> 8) + 1u), 0x1p-24f), u2 = pa_mul((float)(b >> 8), 0x1p-24f);
-    const float rad = __fsqrt_rn(pa_mul(-2.0f, logf(u1)));
+    const float u1 = rn_mul((float)((a >> 8) + 1u), 0x1p-24f), u2 = rn_mul((float)(b >> 8), 0x1p-24f);
+    const float rad = __fsqrt_rn(rn_mul(-2.0f, logf(u1)));
     float s, c;
-    sincospif(pa_mul(2.0f, u2), &s, &c);
-    n0 = pa_mul(rad, c);
-    n1 = pa_mul(rad, s);
+    sincospif(rn_mul(2.0f, u2), &s, &c);
+    n0 = rn_mul(rad, c);
+    n1 = rn_mul(rad, s);
 }
 
 // One thread = the four elements 4 q .. 4 q + 3 of the linear index (fewer in the last group).  vec: both pointers are on the
@@ -108,18 +94,18 @@ __global__ __launch_bounds__(PA_THREADS) void path_point_kernel(const void* __re
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float b = c == 0 ? b0 : (c == 1 ? b1 : b2);
-        p[j] = pa_add(b, pa_mul(alpha, pa_sub(v[j], b)));
+        p[j] = rn_add(b, rn_mul(alpha, rn_sub(v[j], b)));
         if (++rem == hw) { rem = 0; c = c == 2 ? 0 : c + 1; }
     }
     if (noise_level != 0.f) {
-        const float sigma = range ? pa_mul(noise_level, pa_sub(range[1], range[0])) : noise_level;
+        const float sigma = range ? rn_mul(noise_level, rn_sub(range[1], range[0])) : noise_level;
         unsigned r[4];
         pa_philox4x32_10((unsigned)q, (unsigned)(q >> 32), sample, 0u, k0, k1, r);
         float n[4];
         pa_box_muller(r[0], r[1], n[0], n[1]);
         pa_box_muller(r[2], r[3], n[2], n[3]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) p[j] = pa_add(p[j], pa_mul(sigma, n[j]));
+        for (int j = 0; j < 4; ++j) p[j] = rn_add(p[j], rn_mul(sigma, n[j]));
     }
     if (whole) {
         *reinterpret_cast<f32x4_t*>(out + i0) = f32x4_t{p[0], p[1], p[2], p[3]};
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(PA_THREADS) void attr_finish_kernel(const float* __
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a[c][j] = need_x ? pa_mul(pa_sub(v[j], base[c]), g[c][j]) : 0.f;
+            for (int j = 0; j < 4; ++j) a[c][j] = need_x ? rn_mul(rn_sub(v[j], base[c]), g[c][j]) : 0.f;
             if (attr) {
                 if (whole) {
                     *reinterpret_cast<f32x4_t*>(attr + at) = f32x4_t{a[c][0], a[c][1], a[c][2], a[c][3]};
@@ -202,11 +188,11 @@ __global__ __launch_bounds__(PA_THREADS) void attr_finish_kernel(const float* __
         float m[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float tot = pa_add(pa_add(a[0][j], a[1][j]), a[2][j]);
+            const float tot = rn_add(rn_add(a[0][j], a[1][j]), a[2][j]);
             if (mode == 0) m[j] = fabsf(tot);
             else if (mode == 1) m[j] = fmaxf(fmaxf(fabsf(a[0][j]), fabsf(a[1][j])), fabsf(a[2][j]));
             else m[j] = fmaxf(fmaxf(fabsf(g[0][j]), fabsf(g[1][j])), fabsf(g[2][j]));
-            if (j < cnt) sum = pa_add(sum, tot);
+            if (j < cnt) sum = rn_add(sum, tot);
         }
         if (map) {
             const size_t at = t * (size_t)hw + p;
@@ -221,17 +207,17 @@ __global__ __launch_bounds__(PA_THREADS) void attr_finish_kernel(const float* __
     }
     if (!part) return;
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum = pa_add(sum, __shfl_xor(sum, d));
+    for (int d = 32; d > 0; d >>= 1) sum = rn_add(sum, __shfl_xor(sum, d));
     if ((tid & 63) == 0) red[tid >> 6] = sum;
     __syncthreads();
-    if (tid == 0) part[t * MIL_ATTR_SLICES + s] = pa_add(pa_add(pa_add(red[0], red[1]), red[2]), red[3]);
+    if (tid == 0) part[t * MIL_ATTR_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
 }
 
 __global__ __launch_bounds__(PA_THREADS) void attr_sum_kernel(const float* __restrict__ part, float* __restrict__ tile_sum, int n) {
     const int t = blockIdx.x * PA_THREADS + threadIdx.x;
     if (t >= n) return;
     float s = 0.f;
-    for (int k = 0; k < MIL_ATTR_SLICES; ++k) s = pa_add(s, part[(size_t)t * MIL_ATTR_SLICES + k]);
+    for (int k = 0; k < MIL_ATTR_SLICES; ++k) s = rn_add(s, part[(size_t)t * MIL_ATTR_SLICES + k]);
     tile_sum[t] = s;
 }
 

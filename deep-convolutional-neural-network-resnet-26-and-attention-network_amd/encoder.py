@@ -672,6 +672,51 @@ def _stem_backward(bw, dz):
     return dstem
 
 
+# ---- the pieces of a backward walk, shared by encoder_backward, encoder_stage_gradient and encoder_pixel_gradient ----------
+def _check_dx_args(want_dx, dx_reduce, dx_acc):
+    if dx_acc is not None and (dx_reduce is not None or not want_dx):
+        raise ValueError("dx_acc accumulates the three-channel gradient: it goes with the tiles' gradient (want_dx=True) and without dx_reduce")
+
+
+def _pool_gradient(net, saved, dfeats, masked=True):
+    """The seed of a walk that drops the fc layer's gradient: from dfeats [T,80] to the gradient behind stage 4."""
+    return ops.avgpool_fc_bwd_data(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], saved["blocks"][-1][2], masked=masked)
+
+
+def _walk(bw, stages, dz, stem=False):
+    """`stages` backwards, last to first, from the gradient `dz` behind the last of them — and with `stem` conv1's weight
+    gradient — inside the pass's reduction context; then the join of the side streams.  Returns (the gradient of the first
+    stage's input, what `_stem_backward` returned or None)."""
+    dstem = None
+    with bw.reductions(dz.device):
+        for stage in reversed(stages):
+            dz = _stage_backward(bw, stage, dz)
+        if stem:
+            dstem = _stem_backward(bw, dz)
+    bw.join()
+    return dz, dstem
+
+
+def _padded(dz, c, why):
+    if _is_dense(dz, c):
+        raise RuntimeError(why)
+    return dz
+
+
+def _tiles_gradient(bw, dz, dstem, dx_reduce, dx_acc):
+    """The tail of a walk under want_dx, from dz, the gradient of the max-pool output, to the tiles: `ops.maxpool_bwd` unless the
+    un-pooled stem gradient `dstem` is at hand (the fused stem backward never materialises it), then `ops.stem_dgrad` -> (dx, sal)
+    or, with dx_acc, `ops.stem_dgrad_acc` -> (None, None)."""
+    net, saved = bw.net, bw.saved
+    _padded(dz, STEM_WIDTH, "the tiles' gradient needs the padded layout of the pooled stem gradient")
+    if dstem is None:
+        dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
+    if dx_acc is not None:
+        ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(bw.dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
+        return None, None
+    return ops.stem_dgrad(dstem, net.stem_dgrad_packed(bw.dtype), saved["tile_hw"], reduce=dx_reduce)
+
+
 def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False, dx_reduce=None, dx_acc=None):
     """Gradients of every encoder parameter, in `encoder_params()` order.  want_dx=True: returns (those gradients, dx, sal)
     with the gradient of the tiles themselves behind the stem's weight gradient — `ops.maxpool_bwd` to the un-pooled stem
@@ -682,8 +727,7 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False
     pool-gradient scatter), so the parameter gradients are those of `net.dense_grads = False`, bit for bit.  Without want_dx
     nothing of this is packed or launched (`Attention.forward` detaches its input as the reference does,
     gbm/model.py:194-196)."""
-    if dx_acc is not None and (dx_reduce is not None or not want_dx):
-        raise ValueError("dx_acc accumulates the three-channel gradient: it goes with want_dx=True and without dx_reduce")
+    _check_dx_args(want_dx, dx_reduce, dx_acc)
     if saved["x_src"] is not None and saved["x_src"]._version != saved["x_version"]:
         raise RuntimeError("the input tiles were modified in place between the encoder's forward and backward: conv1's gradient is "
                            "computed from them (no space-to-depth copy is kept).  Keep the tensor untouched until backward, or set "
@@ -692,21 +736,8 @@ def encoder_backward(net, saved, dfeats, dtype, allow_direct=True, want_dx=False
     bw = _Backward(net, saved, dtype, allow_direct, want_dx)
     dz, dwfc = ops.avgpool_fc_bwd(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], saved["blocks"][-1][2],
                                   STAGE_WIDTHS[-1], out=net.fc.weight.grad if bw.direct else None)
-    with bw.reductions(dfeats.device):
-        for stage in reversed(net.stages()):
-            dz = _stage_backward(bw, stage, dz)
-        dstem = _stem_backward(bw, dz)
-    bw.join()
-    dx = sal = None
-    if want_dx:
-        if _is_dense(dz, STEM_WIDTH):
-            raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
-        if dstem is None:                   # the fused stem backward never materialises it
-            dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
-        if dx_acc is not None:
-            ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
-        else:
-            dx, sal = ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
+    dz, dstem = _walk(bw, net.stages(), dz, stem=True)
+    dx, sal = _tiles_gradient(bw, dz, dstem, dx_reduce, dx_acc) if want_dx else (None, None)
     flat = list(bw.grads["stem", 0])
     for bi, blk in enumerate(bw.blocks):
         flat += [*bw.grads[bi, 1], *bw.grads[bi, 2]]
@@ -725,24 +756,16 @@ def encoder_stage_gradient(net, saved, dfeats, dtype, stage):
     stages below are not run.  The chain itself carries gradients of PRE-activation maps (each step multiplies by lrelu' of the
     map it arrives at), so the last step of this walk — the pool gradient for stage 4, else the entry block of stage + 1 —
     runs without that factor.  The gradient keeps the padded layout as under `want_dx`; parameter gradients met on the way are
-    dropped and never accumulated (`allow_direct=False`).  `encoder_backward` is not involved and does not change."""
+    dropped and never accumulated (`allow_direct=False`)."""
     if stage not in (1, 2, 3, 4):
         raise ValueError(f"stage must be 1..4, got {stage!r}")
-    stages = net.stages()
-    wfc = net.fc.weight.detach()
-    top = saved["blocks"][-1][2]
     if stage == 4:
-        return ops.avgpool_fc_bwd_data(dfeats.contiguous(), wfc, saved["pooled"], top, masked=False)
+        return _pool_gradient(net, saved, dfeats, masked=False)
+    stages = net.stages()
     bw = _Backward(net, saved, dtype, False, True)
     bw.bare_input = stages[stage][0]
-    dz = ops.avgpool_fc_bwd_data(dfeats.contiguous(), wfc, saved["pooled"], top)
-    with bw.reductions(dfeats.device):
-        for above in reversed(stages[stage:]):
-            dz = _stage_backward(bw, above, dz)
-    bw.join()
-    if _is_dense(dz, STAGE_WIDTHS[stage - 1]):
-        raise RuntimeError("a stage's gradient is returned in the padded layout")
-    return dz
+    dz, _dstem = _walk(bw, stages[stage:], _pool_gradient(net, saved, dfeats))
+    return _padded(dz, STAGE_WIDTHS[stage - 1], "a stage's gradient is returned in the padded layout")
 
 
 def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=None, dx_reduce=None, dx_acc=None):
@@ -752,13 +775,12 @@ def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=Non
     (`encoder_forward(upto=stage)`), or `dfeats` [T,80], which goes through `ops.avgpool_fc_bwd_data` — the very launch of
     `ops.avgpool_fc_bwd`'s data half — into stage 4.  Then `_stage_backward` for the stages at and below the seed with
     `want_wgrad=False`: no `ops.conv_wgrad`, no `conv_wgrad_pair` / `conv_entry_bwd`, no `stem_backward`; the one-pass kernels
-    that make a data gradient still run and their weight gradients are dropped.  Then `ops.maxpool_bwd` and `ops.stem_dgrad`
-    (dx_reduce) or `ops.stem_dgrad_acc` (dx_acc), as `encoder_backward` runs them under want_dx: dx is bit for bit that
-    function's.  Padded gradient layout, `allow_direct=False`: no `.grad` is read or written."""
+    that make a data gradient still run and their weight gradients are dropped.  Then `_tiles_gradient`, the tail that
+    `encoder_backward` runs under want_dx: dx is bit for bit that function's.  Padded gradient layout, `allow_direct=False`: no
+    `.grad` is read or written."""
     if (dz is None) == (dfeats is None):
         raise ValueError("the seed is either dz (with its stage) or dfeats")
-    if dx_acc is not None and dx_reduce is not None:
-        raise ValueError("dx_acc accumulates the three-channel gradient: it goes without dx_reduce")
+    _check_dx_args(True, dx_reduce, dx_acc)
     stages = net.stages()
     if dfeats is not None:
         if stage is not None:
@@ -773,21 +795,12 @@ def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=Non
         raise ValueError(f"the forward stopped below stage {stage}")
     top = saved["blocks"][first + len(blks) - 1][2]
     if dfeats is not None:
-        dz = ops.avgpool_fc_bwd_data(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], top)
+        dz = _pool_gradient(net, saved, dfeats)
     elif dz.shape != top.shape or dz.dtype != top.dtype:
         raise ValueError(f"dz must be like the output of stage {stage}, {tuple(top.shape)} {top.dtype}, got {tuple(dz.shape)} {dz.dtype}")
     bw = _Backward(net, saved, dtype, False, True, want_wgrad=False)
-    with bw.reductions(dz.device):
-        for below in reversed(stages[:stage]):
-            dz = _stage_backward(bw, below, dz)
-    bw.join()
-    if _is_dense(dz, STEM_WIDTH):
-        raise RuntimeError("the tiles' gradient needs the padded layout of the pooled stem gradient")
-    dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
-    if dx_acc is not None:
-        ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
-        return None, None
-    return ops.stem_dgrad(dstem, net.stem_dgrad_packed(dtype), saved["tile_hw"], reduce=dx_reduce)
+    dz, _dstem = _walk(bw, stages[:stage], dz)
+    return _tiles_gradient(bw, dz, None, dx_reduce, dx_acc)
 
 
 class _EncoderFn(torch.autograd.Function):

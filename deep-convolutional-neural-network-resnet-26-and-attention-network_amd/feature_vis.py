@@ -14,31 +14,18 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib as L
 from . import ops
-from .encoder import STAGE_WIDTHS, ResNet, encoder_forward, encoder_pixel_gradient
-from .head import head_apply
-from .preprocess import S2dTiles, U8Tiles
-from .saliency import bag_setup
+from .attribution import LAYERS, bag_evaluate, bag_setup, check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of  # noqa: F401
+from .encoder import STAGE_WIDTHS, encoder_forward, encoder_pixel_gradient
+from .preprocess import U8Tiles
 
 OPTIMIZERS = ops.PIXEL_RULES
-LAYERS = ("layer1", "layer2", "layer3", "layer4")
+WHAT = "feature visualisation"
 
 FeatureVisResult = namedtuple("FeatureVisResult", ["u8", "x", "trace"])
 FeatureVisResult.__doc__ = """What an optimisation returns: `u8`, the final images as `U8Tiles` (the toolkit's `recreate_image` at this
 project's mean and std of 0.5); `x`, the same images as the fp32 [T,3,H,W] stack that was optimised; `trace` fp32 [steps, T], the
 objective of the image each step STARTED from (the filter's mean activation; minus the bag's loss for `classes`)."""
-
-
-def _stage_of(layer):
-    """1..4 for "layer1".."layer4" or the integer itself."""
-    if isinstance(layer, str):
-        if layer not in LAYERS:
-            raise ValueError(f"layer must be one of {LAYERS} or 1..4, got {layer!r}")
-        return LAYERS.index(layer) + 1
-    if layer not in (1, 2, 3, 4) or isinstance(layer, bool):
-        raise ValueError(f"layer must be one of {LAYERS} or 1..4, got {layer!r}")
-    return int(layer)
 
 
 def _count(v, name, least=1):
@@ -90,19 +77,6 @@ def _init_range(init):
     return lo, hi
 
 
-def _check_stack(tiles):
-    if isinstance(tiles, S2dTiles):
-        raise ValueError("S2dTiles hold bf16-rounded space-to-depth records: feature visualisation takes the fp32 stack or U8Tiles")
-    if not isinstance(tiles, (torch.Tensor, U8Tiles)):
-        raise ValueError(f"tiles must be an fp32 [T,3,H,W] tensor or U8Tiles, got {type(tiles).__name__}")
-    if tiles.dim() != 4 or tiles.shape[1] != 3:
-        raise ValueError(f"expected [T,3,H,W] tiles, got {tuple(tiles.shape)}")
-    if isinstance(tiles, torch.Tensor) and not tiles.is_floating_point():
-        raise ValueError(f"a tensor of tiles must be floating point (wrap uint8 images in U8Tiles), got {tiles.dtype}")
-    if tiles.shape[0] < 1:
-        raise ValueError("no tiles")
-
-
 class FeatureVisualizer:
     """`FeatureVisualizer(model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none")` —
     the defaults are the toolkit's `Adam([image], lr=0.1, weight_decay=1e-6)` (cnn_layer_visualization.py:45).  `model`: a
@@ -131,16 +105,7 @@ class FeatureVisualizer:
     states and a `FlatParams` bucket are not touched."""
 
     def __init__(self, model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none"):
-        from . import alt_resnet
-        from .model import Attention
-        if isinstance(model, Attention):
-            net = model.cnn.module
-        elif isinstance(model, (ResNet, alt_resnet.ResNet)):
-            net = model
-        else:
-            raise ValueError("FeatureVisualizer takes a mil_amd.Attention model or its narrow ResNet encoder")
-        if not isinstance(net, ResNet):
-            raise ValueError("FeatureVisualizer needs the narrow ResNet-26 encoder: the wide encoder (alt_resnet) has no stem data-gradient kernel")
+        net = narrow_encoder(model, "FeatureVisualizer", bare=True)
         if project not in ops.PIXEL_PROJECTIONS:
             raise ValueError(f"project must be one of {ops.PIXEL_PROJECTIONS}, got {project!r}")
         try:
@@ -150,17 +115,14 @@ class FeatureVisualizer:
         if len(betas) != 2:
             raise ValueError(f"betas must be two numbers, got {betas!r}")
         ops.pixel_step_scalars(optimizer, lr, weight_decay, betas, eps, 1)
-        self.model = model if isinstance(model, Attention) else None
+        self.model = model if model is not net else None       # the Attention model, where one was given
         self.net = net
         self.optimizer, self.lr, self.weight_decay, self.betas, self.eps = optimizer, float(lr), float(weight_decay), betas, float(eps)
         self.project = project
 
     # ---- pieces ------------------------------------------------------------------------------------------------------------
     def _device(self):
-        dev = self.net.conv1.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("FeatureVisualizer runs on an AMD GPU only (module parameters are not on a CUDA/HIP device)")
-        return dev
+        return model_device(self.net, "FeatureVisualizer")
 
     def _start(self, ntiles, size, init, seed):
         """Random start bytes [ntiles,3,H,W] from a generator of their own, as the fp32 stack they decode to, on the device."""
@@ -177,14 +139,13 @@ class FeatureVisualizer:
 
     def _ascend(self, x, stage, chans, steps):
         """`steps` steps on x (fp32 on the device, optimised in place) for channel chans[t] of stage `stage`."""
-        net, mode = self.net, self.net.compute_dtype
-        dtype = L.storage_dtype(mode)
+        net = self.net
         c = STAGE_WIDTHS[stage - 1]
         ch = torch.tensor(chans, dtype=torch.int32).to(x.device)
         trace = torch.empty((steps, x.shape[0]), dtype=torch.float32, device=x.device)
         u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
         state = self._state(x)
-        with torch.no_grad(), L.f32_mma(L.mma_code(mode)):
+        with torch.no_grad(), compute_mode(net) as dtype:
             for k in range(steps):
                 _feats, saved = encoder_forward(net, x, dtype, upto=stage)
                 _j, dz = ops.stage_seed(saved["blocks"][-1][2], ch, c, objective=trace[k])
@@ -194,14 +155,14 @@ class FeatureVisualizer:
 
     # ---- methods -----------------------------------------------------------------------------------------------------------
     def filters(self, layer, channels=None, size=(256, 256), steps=30, init=(150, 180), seed=0):
-        stage = _stage_of(layer)
+        stage = stage_of(layer)
         chans = _channel_list(channels, STAGE_WIDTHS[stage - 1])
         size, steps, init = _size(size), _count(steps, "steps"), _init_range(init)
         return self._ascend(self._start(len(chans), size, init, seed), stage, chans, steps)
 
     def dream(self, tiles, layer, channels, steps=250):
-        stage = _stage_of(layer)
-        _check_stack(tiles)
+        stage = stage_of(layer)
+        check_tiles(None, tiles, None, WHAT)
         chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
         steps = _count(steps, "steps")
         dev = self._device()
@@ -209,15 +170,13 @@ class FeatureVisualizer:
         return self._ascend(x, stage, chans, steps)
 
     def objective(self, tiles, layer, channels):
-        stage = _stage_of(layer)
-        _check_stack(tiles)
+        stage = stage_of(layer)
+        check_tiles(None, tiles, None, WHAT)
         chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
-        dev = self._device()
-        net, mode = self.net, self.net.compute_dtype
-        x = tiles.u8.to(dev) if isinstance(tiles, U8Tiles) else tiles.detach().to(dev, torch.float32)
-        ch = torch.tensor(chans, dtype=torch.int32).to(dev)
-        with torch.no_grad(), L.f32_mma(L.mma_code(mode)):
-            _feats, saved = encoder_forward(net, x, L.storage_dtype(mode), upto=stage)
+        x = device_tiles(self.net, tiles, "FeatureVisualizer")
+        ch = torch.tensor(chans, dtype=torch.int32).to(x.device)
+        with torch.no_grad(), compute_mode(self.net) as dtype:
+            _feats, saved = encoder_forward(self.net, x, dtype, upto=stage)
             return ops.stage_seed(saved["blocks"][-1][2], ch, STAGE_WIDTHS[stage - 1])[0]
 
     def classes(self, label, ntiles, size=(256, 256), steps=150, init=(0, 256), seed=0):
@@ -229,22 +188,16 @@ class FeatureVisualizer:
         ntiles = _count(ntiles, "ntiles", 2)
         size, steps, init = _size(size), _count(steps, "steps"), _init_range(init)
         x = self._start(ntiles, size, init, seed)
-        net, mode = self.net, self.net.compute_dtype
-        dtype = L.storage_dtype(mode)
-        layout, y, cw = bag_setup(model, ntiles, int(label))
-        weights = [w.detach() for w in model.head_weights()]
+        setup = bag_setup(model, ntiles, int(label))
+        weights = [w.detach() for w in model.head_weights()]      # hoisted out of the loop: the model does not change under it
         trace = torch.empty((steps, ntiles), dtype=torch.float32, device=x.device)
         u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
         state = self._state(x)
-        with L.f32_mma(L.mma_code(mode)):
+        with compute_mode(self.net) as dtype:
             for k in range(steps):
+                saved, dH, loss = bag_evaluate(model, setup, x, weights=weights)
                 with torch.no_grad():
-                    feats, saved = encoder_forward(net, x, dtype)
-                H = feats.detach().requires_grad_(True)
-                loss = head_apply(H, layout, y, None, cw, weights, None, direct=False)[0]
-                (dH,) = torch.autograd.grad(loss.sum(), H)
-                with torch.no_grad():
-                    trace[k] = -loss.detach()
-                    g, _sal = encoder_pixel_gradient(net, saved, dtype, dfeats=dH)
+                    trace[k] = -loss
+                    g, _sal = encoder_pixel_gradient(self.net, saved, dtype, dfeats=dH)
                     self._step(x, g, state, k, k == steps - 1, u8)
         return FeatureVisResult(U8Tiles(u8), x, trace)

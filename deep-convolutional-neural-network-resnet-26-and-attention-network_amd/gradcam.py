@@ -8,13 +8,10 @@ the forward (`saved["blocks"]`), its gradient is the hand-written backward chain
 """
 import torch
 
-from . import _lib as L
 from . import ops
-from .encoder import STAGE_WIDTHS, ResNet, encoder_forward, encoder_stage_gradient
-from .head import BagLayout, head_apply
-from .preprocess import S2dTiles, U8Tiles
+from .attribution import LAYERS, bag_evaluate, bag_setup, check_tiles, compute_mode, device_tiles, narrow_encoder, stage_of
+from .encoder import STAGE_WIDTHS, encoder_stage_gradient
 
-LAYERS = ("layer1", "layer2", "layer3", "layer4")
 NORMALIZE = ("tile", "bag")
 
 
@@ -43,60 +40,22 @@ class TileGradCam:
     drawn from and `direct_grad` accumulation is not triggered."""
 
     def __init__(self, model, layer="layer4"):
-        from .model import Attention
-        if not isinstance(model, Attention):
-            raise ValueError("TileGradCam takes a mil_amd.Attention model")
-        if not isinstance(model.cnn.module, ResNet):
-            raise ValueError("TileGradCam needs the narrow ResNet-26 encoder: the wide encoder (alt_resnet) has no stage-gradient path")
-        if layer not in LAYERS:
-            raise ValueError(f"layer must be one of {LAYERS}, got {layer!r}")
+        narrow_encoder(model, "TileGradCam", lacks="stage-gradient path")
         self.model = model
-        self.layer = layer
-        self.stage = LAYERS.index(layer) + 1
+        self.stage = stage_of(layer)
+        self.layer = LAYERS[self.stage - 1]
 
     def _check(self, tiles, label):
-        if not isinstance(tiles, (torch.Tensor, U8Tiles, S2dTiles)):
-            raise ValueError(f"tiles must be an fp32 [T,3,H,W] tensor, U8Tiles or S2dTiles, got {type(tiles).__name__}")
-        if tiles.dim() != 4 or tiles.shape[1] != 3:
-            raise ValueError(f"expected [T,3,H,W] tiles, got {tuple(tiles.shape)}")
-        if isinstance(tiles, torch.Tensor) and not tiles.is_floating_point():
-            raise ValueError(f"a tensor of tiles must be floating point (wrap uint8 images in U8Tiles), got {tiles.dtype}")
-        if isinstance(tiles, S2dTiles) and self.model.cnn.module.compute_dtype != torch.bfloat16:
-            raise ValueError("S2dTiles feed the bf16 compute mode only")
-        if tiles.shape[0] < 1:
-            raise ValueError("an empty bag has no class activation map")
-        label = int(label)
-        if not 0 <= label < self.model.C:
-            raise ValueError(f"label must be in [0, {self.model.C}), got {label}")
-        return label
+        return check_tiles(self.model, tiles, label, "class activation map", s2d=True)
 
     def _stage_tensors(self, tiles, label):
         """(the stage's output, the gradient of minus the loss with respect to it, its real channels, the tiles' (H, W))."""
         model = self.model
         net = model.cnn.module
-        dev = model.weight_mask.device
-        if dev.type != "cuda":
-            raise RuntimeError("Attention runs on an AMD GPU only (module parameters are not on a CUDA/HIP device)")
-        if isinstance(tiles, U8Tiles):
-            x = tiles.u8.to(dev)
-        elif isinstance(tiles, S2dTiles):
-            x = tiles.xs.detach().to(dev)
-        else:
-            x = tiles.detach().to(dev, torch.float32)
-        mode = net.compute_dtype
-        dtype = L.storage_dtype(mode)
-        layout = BagLayout.cached([x.shape[0]], dev)
-        y = torch.tensor([label], dtype=torch.long, device=dev)
-        cw = model.loss.weight
-        if cw is not None:
-            cw = torch.as_tensor(cw, dtype=torch.float32, device=dev).contiguous()
+        x = device_tiles(model, tiles)
         first, blks = net.stages()[self.stage - 1]
-        with L.f32_mma(L.mma_code(mode)):
-            with torch.no_grad():
-                feats, saved = encoder_forward(net, x, dtype)
-            H = feats.detach().requires_grad_()
-            loss = head_apply(H, layout, y, None, cw, [w.detach() for w in model.head_weights()], None, direct=False)[0]
-            (dH,) = torch.autograd.grad(loss.sum(), H)
+        with compute_mode(net) as dtype:
+            saved, dH, _loss = bag_evaluate(model, bag_setup(model, x.shape[0], label), x)
             with torch.no_grad():
                 grad = encoder_stage_gradient(net, saved, -dH, dtype, self.stage)
         act = saved["blocks"][first + len(blks) - 1][2]

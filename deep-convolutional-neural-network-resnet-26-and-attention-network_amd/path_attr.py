@@ -4,28 +4,20 @@ The two methods of the saliency toolkit the reference vendors (pytorch-cnn-visua
 `integrated_gradients.py` along a straight path from a baseline image to the tile, `smooth_grad.py` over noisy copies of the
 tile.  With the stock model either is a Python loop around `x.requires_grad_()`.  Here a step is one launch that makes the
 perturbed stack straight from the fp32 or uint8 tiles (`ops.path_point`: counter-based noise, torch's generator is not touched),
-one pass of the hand-written encoder forward and backward, and the stem's data-gradient kernel adding `weight * gradient` into
-the running sum in its store epilogue (`encoder_backward(dx_acc=...)`): no per-step gradient tensor, no torch pass over it.  One
+one pass of the hand-written encoder forward and of its data-gradient-only walk back (`attribution.bag_step`: no weight gradient
+is launched), and the stem's data-gradient kernel adding `weight * gradient` into the running sum in its store epilogue
+(`encoder_pixel_gradient(dx_acc=...)`): no per-step gradient tensor, no torch pass over it.  One
 finishing launch (`ops.attr_finish`) turns the sum into attributions, maps and per-tile sums.  DESIGN.md section 3.40.
 """
 import torch
 
 from . import ops
-from .encoder import ResNet
+from .attribution import bag_setup, bag_step, check_tiles, device_tiles, narrow_encoder
 from .preprocess import U8Tiles
-from .saliency import bag_setup, bag_step, check_tiles, device_tiles
 
 RULES = ("midpoint", "toolkit")
 BASELINES = {"grey": 0.0, "white": 1.0, "black": -1.0}       # in normalised units: Normalize(.5, .5) maps [0, 1] to [-1, 1]
 MAP_REDUCE = ("sum", "max")
-
-
-def _narrow_attention(model, who):
-    from .model import Attention
-    if not isinstance(model, Attention):
-        raise ValueError(f"{who} takes a mil_amd.Attention model")
-    if not isinstance(model.cnn.module, ResNet):
-        raise ValueError(f"{who} needs the narrow ResNet-26 encoder: the wide encoder (alt_resnet) has no stem data-gradient kernel")
 
 
 def _wrap(tiles, x):
@@ -58,7 +50,7 @@ class TileIntegratedGradients:
     a `FlatParams` bucket are not touched."""
 
     def __init__(self, model, steps=32, rule="midpoint", baseline=0.0):
-        _narrow_attention(model, "TileIntegratedGradients")
+        narrow_encoder(model, "TileIntegratedGradients")
         if rule not in RULES:
             raise ValueError(f"rule must be one of {RULES}, got {rule!r}")
         if int(steps) != steps or steps < 1:
@@ -137,7 +129,7 @@ class TileSmoothGrad:
     `TileIntegratedGradients`."""
 
     def __init__(self, model, n=50, noise_level=0.15, seed=0):
-        _narrow_attention(model, "TileSmoothGrad")
+        narrow_encoder(model, "TileSmoothGrad")
         if int(n) != n or n < 1:
             raise ValueError(f"n must be an integer >= 1, got {n!r}")
         if not float(noise_level) >= 0.0:

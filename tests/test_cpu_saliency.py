@@ -88,3 +88,21 @@ def test_ops_stem_dgrad_checks_shapes_on_the_host():
         ops.stem_dgrad(torch.zeros(16, 16, 24), d, (32, 32))
     with pytest.raises(ValueError, match="dstem"):                                  # a CPU tensor is refused before any launch
         ops.stem_dgrad(d, d, (32, 32))
+
+
+def test_attribution_classes_share_one_module_and_keep_their_own_wording():
+    import mil_amd
+    from mil_amd import attribution, feature_vis, gradcam, path_attr, saliency
+    for name in ("bag_setup", "bag_step", "check_tiles", "device_tiles"):
+        assert getattr(saliency, name) is getattr(attribution, name), name
+        assert getattr(path_attr, name) is getattr(attribution, name), name
+    assert gradcam.LAYERS is feature_vis.LAYERS is attribution.LAYERS
+    model = mil_amd.Attention(3, compute_dtype=torch.float32, device="cpu")
+    s2d = mil_amd.S2dTiles(torch.zeros(4, 16, 16, 16, dtype=torch.bfloat16))
+    with pytest.raises(ValueError, match="S2dTiles feed the bf16 compute mode only"):
+        mil_amd.TileGradCam(model)._check(s2d, 0)
+    with pytest.raises(ValueError, match="S2dTiles hold bf16-rounded .*: saliency takes the fp32 stack or U8Tiles"):
+        saliency.check_tiles(model, s2d, 0, "saliency")
+    with pytest.raises(ValueError, match="S2dTiles hold bf16-rounded .*: feature visualisation takes the fp32 stack or U8Tiles"):
+        mil_amd.FeatureVisualizer(model).dream(s2d, "layer1", 0)
+    assert mil_amd.TileGradCam(model, layer=2).layer == "layer2"                    # the shared layer -> stage mapping takes 1..4 too

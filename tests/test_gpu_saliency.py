@@ -294,3 +294,86 @@ def test_tile_saliency_with_flat_params_leaves_the_bucket_alone(golden_dir):
     assert float(bucket.abs().max()) > 0
     mil_amd.TileSaliency(net).maps(x, 0)
     assert torch.equal(flat.flat_grad, bucket)
+
+
+# ---- the step on the data-gradient-only walk ------------------------------------------------------------------------------------
+WGRAD_OPS = ("conv_wgrad", "conv_wgrad_pair", "conv_entry_bwd", "stem_backward", "avgpool_fc_bwd")
+# (3, 50, 70): odd map extents and a width that is no multiple of 16; (6, 64, 64): the smallest bag whose 8x8 layer-3 maps take the
+# LDS-resident chain
+WALK_BAGS = [(3, 50, 70), (6, 64, 64)]
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int32).cpu(), b.contiguous().view(torch.int32).cpu())
+
+
+@pytest.mark.parametrize("feed", ["fp32", "u8"])
+@pytest.mark.parametrize("bag", WALK_BAGS, ids=["3x50x70", "6x64x64"])
+@pytest.mark.parametrize("dtype", MODES, ids=MODE_IDS)
+def test_saliency_step_is_encoder_backwards_dx_and_launches_no_weight_gradient(golden_dir, monkeypatch, ops, dtype, bag, feed):
+    """`TileSaliency` and `bag_step` against `encoder_backward(want_dx=True)` written out by hand as `bag_step` used to run it: the
+    same bits for dx, for the max-|dx| map and for the accumulator, and not one launch of a weight-gradient wrapper."""
+    import mil_amd
+    from mil_amd import _lib as L
+    from mil_amd.encoder import encoder_backward, encoder_forward
+    from mil_amd.head import head_apply
+    from mil_amd.saliency import bag_setup, bag_step, device_tiles
+    label = 1
+    model = _model(golden_dir, dtype)
+    net = model.cnn.module
+    tiles = synth_bag(*bag, 20260301)
+    if feed == "u8":
+        tiles = mil_amd.U8Tiles(_to_u8(tiles))
+    counts = {}
+
+    def counted(name, real):
+        def call(*a, **k):
+            counts[name] += 1
+            return real(*a, **k)
+        return call
+    for name in WGRAD_OPS + ("stem_dgrad", "stem_dgrad_acc"):
+        counts[name] = 0
+        monkeypatch.setattr(ops, name, counted(name, getattr(ops, name)))
+
+    def tail_launches():
+        n = counts["stem_dgrad"] + counts["stem_dgrad_acc"]
+        counts["stem_dgrad"] = counts["stem_dgrad_acc"] = 0
+        return n
+
+    x = device_tiles(model, tiles)
+    setup = bag_setup(model, x.shape[0], label)
+    layout, y, cw = setup
+    mode = net.compute_dtype
+    st = L.storage_dtype(mode)
+
+    def by_hand(**kw):
+        with L.f32_mma(L.mma_code(mode)):
+            with torch.no_grad():
+                feats, saved = encoder_forward(net, x, st)
+            H = feats.detach().requires_grad_()
+            loss = head_apply(H, layout, y, None, cw, [w.detach() for w in model.head_weights()], None, direct=False)[0]
+            (dH,) = torch.autograd.grad(loss.sum(), H)
+            with torch.no_grad():
+                return encoder_backward(net, saved, dH, st, allow_direct=False, want_dx=True, **kw)[1:]
+    dx_ref = by_hand()[0]
+    sal_ref = by_hand(dx_reduce="max_abs")[1]
+    acc_ref = torch.zeros_like(dx_ref)
+    by_hand(dx_acc=(acc_ref, 0.25))
+    assert counts["conv_wgrad"] > 0 and counts["avgpool_fc_bwd"] == 3 and tail_launches() == 3     # the counters see launches
+    assert bool(torch.isfinite(dx_ref).all()) and float(dx_ref.abs().max()) > 0
+    for name in WGRAD_OPS:
+        counts[name] = 0
+
+    sal = mil_amd.TileSaliency(model)
+    training, rng, dev_rng = model.training, torch.get_rng_state(), torch.cuda.get_rng_state()
+    dx = sal.input_gradient(tiles, label)
+    assert tail_launches() == 1
+    m = sal.maps(tiles, label, method="gradient")
+    assert tail_launches() == 1
+    acc = torch.zeros_like(dx_ref)
+    assert bag_step(model, setup, x, dx_acc=(acc, 0.25))[:2] == (None, None)
+    assert tail_launches() == 1
+    assert all(counts[name] == 0 for name in WGRAD_OPS), counts
+    assert _same_bits(dx, dx_ref) and _same_bits(m, sal_ref) and _same_bits(acc, acc_ref)
+    assert all(p.grad is None for p in model.parameters())
+    assert model.training == training and torch.equal(torch.get_rng_state(), rng) and torch.equal(torch.cuda.get_rng_state(), dev_rng)
