@@ -57,6 +57,7 @@ _SIGS = {
     "mil_packed_weight_elems": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_pack_conv_weights": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_conv_igemm": ([_vp] * 6 + [_i] * 12 + [_f, _i, _vp], _i),
+    "mil_conv_dgrad_rule": ([_vp] * 6 + [_i] * 12 + [_f, _i, _i, _vp], _i),
     "mil_conv_wgrad_workspace": ([_c.POINTER(_sz)] + [_i] * 12, _i),
     "mil_conv_wgrad": ([_vp, _vp, _vp, _vp, _vp, _sz] + [_i] * 13 + [_vp], _i),
     "mil_reduce_job_bytes": ([], _i),
@@ -67,6 +68,7 @@ _SIGS = {
     "mil_conv_bwd_fused": ([_vp] * 8 + [_sz] + [_i] * 9 + [_f, _i, _vp], _i),
     "mil_maxpool_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_maxpool_bwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
+    "mil_maxpool_bwd_guided": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_resize_plan": ([_i, _i, _c.POINTER(_i)], _i),
     "mil_resize_coeffs": ([_i, _i, _vp, _vp], _i),
     "mil_resample_plan": ([_i, _i, _i, _c.POINTER(_i)], _i),
@@ -100,6 +102,7 @@ _SIGS = {
     "mil_stem_bwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _i, _vp], _i),
     "mil_stem_dgrad": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_stem_dgrad_acc": ([_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp], _i),
+    "mil_stem_dgrad_gated": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_path_point": ([_vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _c.c_uint64, _c.c_uint32, _i, _i, _i, _vp], _i),
     "mil_attr_finish": ([_vp, _vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
     "mil_stage_seed": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
@@ -112,6 +115,7 @@ _SIGS = {
     "mil_grad_cam": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp], _i),
     "mil_avgpool_fc_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_avgpool_fc_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
+    "mil_avgpool_fc_bwd_data_guided": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mil_wide_packed_elems": ([_c.POINTER(_sz), _i, _i, _i, _i], _i),
     "mil_wide_pack_weights": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_wide_conv": ([_vp] * 6 + [_i] * 12 + [_f, _i, _vp], _i),

@@ -1,5 +1,5 @@
 """What the attribution classes share (TileSaliency, TileGradCam, TileIntegratedGradients, TileSmoothGrad, FeatureVisualizer):
-the constructor and tile checks, the move of the tiles to the device, and ONE evaluation of a bag for a label — the encoder's
+the constructor, tile and channel checks, the move of the tiles to the device, and ONE evaluation of a bag for a label — the encoder's
 forward, the head with its parameters detached, the gradient of the loss with respect to the features — which `bag_step`
 continues to the pixels on the data-gradient-only walk (`encoder_pixel_gradient`).  DESIGN.md section 3.44.
 """
@@ -24,6 +24,31 @@ def stage_of(layer):
     if layer not in (1, 2, 3, 4) or isinstance(layer, bool):
         raise ValueError(f"layer must be one of {LAYERS} or 1..4, got {layer!r}")
     return int(layer)
+
+
+def channel_list(channels, c, ntiles=None):
+    """One channel in [0, c) per tile as a list of ints; None: all channels of the stage; an int: that channel for every tile."""
+    if channels is None:
+        if ntiles is not None:
+            raise ValueError("channels: one per tile, or one int for all tiles")
+        channels = range(c)
+    elif isinstance(channels, int) and not isinstance(channels, bool):
+        channels = [channels] * (1 if ntiles is None else ntiles)
+    elif isinstance(channels, torch.Tensor):
+        channels = channels.tolist()
+    try:
+        out = [int(k) for k in channels]
+        exact = all(int(k) == k and not isinstance(k, bool) for k in channels)
+    except (TypeError, ValueError):
+        raise ValueError(f"channels must be integers, got {channels!r}") from None
+    if not out or not exact:
+        raise ValueError(f"channels must be a non-empty list of integers, got {list(channels)!r}")
+    if ntiles is not None and len(out) != ntiles:
+        raise ValueError(f"{len(out)} channels for {ntiles} tiles")
+    bad = [k for k in out if not 0 <= k < c]
+    if bad:
+        raise ValueError(f"channels must lie in [0, {c}), got {bad}")
+    return out
 
 
 def narrow_encoder(model, who, bare=False, lacks="stem data-gradient kernel"):

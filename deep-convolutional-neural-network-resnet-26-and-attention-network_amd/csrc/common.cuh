@@ -91,6 +91,14 @@ struct F32S {
     static constexpr bool TR16 = true, SPLIT = true;
 };
 
+// Guided<B>: the storage type B with the guided-backpropagation rule attached.  A kernel whose store
+// epilogue applies a LeakyReLU derivative reads mil_tag<T>::RULE — 0: that derivative, 1: the guided gate — and hands
+// mil_tag<T>::base to the helpers below, which are specialised for the three storage types.  For T = BF16 / F32 / F32S base is
+// T and RULE is 0: such an instantiation keeps its name and compiles to the code it was before the rule existed.
+template <typename B> struct Guided : B {};
+template <typename T> struct mil_tag { using base = T; static constexpr int RULE = 0; };
+template <typename B> struct mil_tag<Guided<B>> { using base = B; static constexpr int RULE = 1; };
+
 // One MFMA operand fragment = 8 consecutive-k elements per lane.
 template <typename T> struct Frag8;
 template <> struct Frag8<BF16> { bf16x8_t v; };

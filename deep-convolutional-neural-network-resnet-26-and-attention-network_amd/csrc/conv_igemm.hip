@@ -8,7 +8,7 @@
 //   A operand:  the input halo tile, staged ONCE in LDS and re-read for every tap (no im2col in HBM).
 //   B operand:  weights pre-packed on device in MFMA B-fragment order (pack.hip), staged in LDS.
 //   Epilogue:   accumulators -> LDS (fp32) -> per-pixel 8-channel rows:
-//               v = acc + bias + residual;  v = lrelu(v);  v *= lrelu'(act);  16-B NHWC stores.
+//               v = acc + bias + residual;  v = lrelu(v);  v *= lrelu'(act) (or the guided gate);  16-B NHWC stores.
 //   dgrad:      the same kernel run over dz with transposed+flipped packed weights; stride-2 dgrad
 //               reads dz through the zero-insert loader (transposed convolution).
 #include "geom.cuh"
@@ -30,10 +30,14 @@ struct ConvArgs {
     float slope;
 };
 
+// T = BF16 / F32 / F32S, or Guided<one of them> (mil_conv_dgrad_rule, rule 1): the store epilogue then replaces
+// v *= lrelu'(act) by the guided gate v = (act > 0 && v > 0) ? v : +0 and everything else is the same kernel.
 template <typename T, int CINP, int NT, int MTW>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MIL_POISON(smem);
+    using B = typename mil_tag<T>::base;        // the storage type; T itself may carry the rule (Guided<B>)
+    constexpr int RULE = mil_tag<T>::RULE;
     constexpr int ESZ = T::ESZ;
     constexpr int PIXB = mil_pix_pitch(CINP, ESZ);
     constexpr int CG = CINP / 8;
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
     const TileOrigin o = mil_tile_origin(g, blockIdx.x);
     char* ldsA = smem;
     char* ldsW = smem + a.lds_w_off;
-    mil_load_halo<T, CINP>(ldsA, a.x, g, o, tid, 256);
+    mil_load_halo<B, CINP>(ldsA, a.x, g, o, tid, 256);
 
     const int s_eff = g.zins ? 1 : g.stride;
     int pixbase[MTW];
@@ -77,12 +81,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
             if (tap >= ntaps) { tap = 0; cg = 0; }      // K padding: weights there are zero
             const int ky = tap / g.ks, kx = tap - ky * g.ks;
             const int toff = (ky * g.hw + kx) * PIXB + cg * T::CGB;
-            Frag8<T> bf[NT];
+            Frag8<B> bf[NT];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bf[nt] = lds_frag<T>(ldsW + ((sl * NT + nt) * 64 + lane) * FRAGB);
+            for (int nt = 0; nt < NT; ++nt) bf[nt] = lds_frag<B>(ldsW + ((sl * NT + nt) * 64 + lane) * FRAGB);
 #pragma unroll
             for (int m = 0; m < MTW; ++m) {
-                const Frag8<T> af = lds_pix_frag<T, CINP * 2>(ldsA + pixbase[m] + toff);
+                const Frag8<B> af = lds_pix_frag<B, CINP * 2>(ldsA + pixbase[m] + toff);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mma8(af, bf[nt], acc[m][nt]);
             }
@@ -122,7 +126,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
         const size_t off = (((size_t)img * g.Ho + oy) * g.Wo + ox) * COUTP + c8 * 8;
         if (a.res) {
             float rv[8];
-            load8<T>(a.res + off, rv);
+            load8<B>(a.res + off, rv);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += rv[j];
         }
@@ -130,13 +134,18 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = lrelu(v[j], a.slope);
         }
-        if (a.act) {
+        if constexpr (RULE == 1) {             // guided backpropagation: act is required (checked on the host)
             float av[8];
-            load8<T>(a.act + off, av);
+            load8<B>(a.act + off, av);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (av[j] > 0.f && v[j] > 0.f) ? v[j] : 0.f;
+        } else if (a.act) {
+            float av[8];
+            load8<B>(a.act + off, av);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] *= lrelu_grad(av[j], a.slope);
         }
-        store8<T>(a.y + off, v);
+        store8<B>(a.y + off, v);
     }
 }
 
@@ -770,4 +779,54 @@ extern "C" int mil_conv_igemm(const void* x, const void* wpack, const float* bia
         return dispatch_conv<F32S>(a, cin_p, cout_p, st);
     }
     return MIL_ERR_ARG;
+}
+
+// ---------------------------------------------------------------------------------------------
+// mil_conv_dgrad_rule: the data gradients of a guided-backpropagation walk (include/mil_hip.h).  Always the generic kernel
+// above — 256-pixel tiles where the halo and a filter chunk fit LDS, else 64-pixel tiles — never the persistent, resident or
+// streaming forms; rule 0 launches conv_igemm_kernel<B, ...> itself, rule 1 conv_igemm_kernel<Guided<B>, ...>.
+template <typename T, int CINP, int NT>
+static int launch_conv_generic(const ConvArgs<T>& a, hipStream_t stream) {
+    const int rc = launch_conv<T, CINP, NT, 4>(a, stream);
+    return rc != MIL_ERR_UNSUPPORTED ? rc : launch_conv<T, CINP, NT, 1>(a, stream);
+}
+
+template <typename T>
+static int dispatch_conv_rule(const void* x, const void* wpack, const float* bias_pad, const void* res, const void* act, void* y,
+                              const ConvGeom& g, int nsteps, int cin_p, int cout_p, int apply_lrelu, float slope, hipStream_t st) {
+    using E = typename T::elem;
+    ConvArgs<T> a{};
+    a.x = (const E*)x; a.w = (const E*)wpack; a.bias = bias_pad; a.res = (const E*)res;
+    a.act = (const E*)act; a.y = (E*)y; a.g = g; a.nsteps = nsteps; a.apply_lrelu = apply_lrelu; a.slope = slope;
+#define MIL_RULE_CASE(CI, NTV) return launch_conv_generic<T, CI, NTV>(a, st)
+    if (cin_p == 24 && cout_p == 24) MIL_RULE_CASE(24, 2);
+    if (cin_p == 40 && cout_p == 40) MIL_RULE_CASE(40, 3);
+    if (cin_p == 64 && cout_p == 64) MIL_RULE_CASE(64, 4);
+    if (cin_p == 80 && cout_p == 80) MIL_RULE_CASE(80, 5);
+    if (cin_p == 40 && cout_p == 24) MIL_RULE_CASE(40, 2);   // stage-entry data gradients
+    if (cin_p == 64 && cout_p == 40) MIL_RULE_CASE(64, 3);
+    if (cin_p == 80 && cout_p == 64) MIL_RULE_CASE(80, 4);
+#undef MIL_RULE_CASE
+    return MIL_ERR_UNSUPPORTED;
+}
+
+extern "C" int mil_conv_dgrad_rule(const void* x, const void* wpack, const float* bias_pad, const void* res, const void* act,
+                                   void* y, int n_img, int H, int W, int cin_p, int Ho, int Wo, int cout_p, int ks, int stride,
+                                   int pad, int zero_insert, int apply_lrelu, float slope, int rule, int dtype, void* stream) {
+    if (!x || !wpack || !y || n_img < 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return MIL_ERR_ARG;
+    if (!(ks == 1 || ks == 3 || ks == 4) || !(stride == 1 || stride == 2)) return MIL_ERR_ARG;
+    if (rule < 0 || rule > 1 || (rule == 1 && !act)) return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32 && dtype != MIL_DT_F32S) return MIL_ERR_ARG;
+    if (stride == 2 && !zero_insert) return MIL_ERR_UNSUPPORTED;     // a data gradient runs at stride 1 (zero-insert behind a stride-2 conv)
+    ConvGeom g{};
+    g.n_img = n_img; g.H = H; g.W = W; g.Ho = Ho; g.Wo = Wo; g.ks = ks; g.stride = stride; g.pad = pad;
+    g.zins = zero_insert ? 1 : 0;
+    const int nsteps = (ks * ks * (cin_p / 8) + 3) / 4;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define MIL_RULE_DT(B) (rule == 1 ? dispatch_conv_rule<Guided<B>>(x, wpack, bias_pad, res, act, y, g, nsteps, cin_p, cout_p, apply_lrelu, slope, st) \
+                                  : dispatch_conv_rule<B>(x, wpack, bias_pad, res, act, y, g, nsteps, cin_p, cout_p, apply_lrelu, slope, st))
+    if (dtype == MIL_DT_BF16) return MIL_RULE_DT(BF16);
+    if (dtype == MIL_DT_F32) return MIL_RULE_DT(F32);
+    return MIL_RULE_DT(F32S);
+#undef MIL_RULE_DT
 }

@@ -185,10 +185,16 @@ __global__ void maxpool_fwd_kernel(const typename T::elem* __restrict__ x, typen
 // windows (by..by+1, bx..bx+1) — the even/even pixel by one of them, the mixed ones by two, the odd/odd one
 // by all four — so the four winner records and gradients are loaded once and 9 tap tests replace 16.
 // With use_mask the lrelu' factor comes from bit 4 of the winner record.
+// T = Guided<BF16 / F32> (mil_maxpool_bwd_guided): guided backpropagation through the stem's LeakyReLU.
+// The gate sees the SUM of the window contributions of a pixel — the total gradient arriving at that activation — not each
+// contribution: gx = (winner > 0 && sum > 0) ? sum : +0, the winner's sign from bit 4 of any window that elected the pixel (they
+// agree: it is one value).  slope and use_mask are not read.
 template <typename T>
 __global__ void maxpool_bwd_kernel(const typename T::elem* __restrict__ gy, const uint8_t* __restrict__ widx,
                                    typename T::elem* __restrict__ gx, int n, int H, int W, int Ho, int Wo, int CP,
                                    float slope, int use_mask) {
+    using B = typename mil_tag<T>::base;
+    constexpr int RULE = mil_tag<T>::RULE;
     const int ng = CP / 8;
     const int Hb = (H + 1) / 2, Wb = (W + 1) / 2;
     const size_t total = (size_t)n * Hb * Wb * ng;
@@ -205,6 +211,7 @@ __global__ void maxpool_bwd_kernel(const typename T::elem* __restrict__ gy, cons
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) g[a][b][j] = 0.f;
+        uint32_t closed[2][2] = {{0u, 0u}, {0u, 0u}};           // RULE 1: bit j = the pixel's channel j won with a value <= 0
 #pragma unroll
         for (int wy = 0; wy < 2; ++wy) {
             const int oy = by + wy;
@@ -216,7 +223,7 @@ __global__ void maxpool_bwd_kernel(const typename T::elem* __restrict__ gy, cons
                 const size_t o = (((size_t)img * Ho + oy) * Wo + ox) * CP + c8 * 8;
                 const uint2 packed = *reinterpret_cast<const uint2*>(widx + o);
                 float gv[8];
-                load8<T>(gy + o, gv);
+                load8<B>(gy + o, gv);
                 // window (oy,ox) covers rows 2oy-1..2oy+1: block row dy (pixel 2by+dy) is its tap row ky below
 #pragma unroll
                 for (int dy = 0; dy < 2; ++dy) {
@@ -230,7 +237,14 @@ __global__ void maxpool_bwd_kernel(const typename T::elem* __restrict__ gy, cons
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
                             const uint32_t w = ((j < 4 ? packed.x : packed.y) >> (8 * (j & 3))) & 0xffu;
-                            if ((w & 15u) == me) g[dy][dx][j] += (use_mask && (w & 16u)) ? gv[j] * slope : gv[j];
+                            if constexpr (RULE == 1) {
+                                if ((w & 15u) == me) {
+                                    g[dy][dx][j] += gv[j];
+                                    closed[dy][dx] |= ((w >> 4) & 1u) << j;
+                                }
+                            } else {
+                                if ((w & 15u) == me) g[dy][dx][j] += (use_mask && (w & 16u)) ? gv[j] * slope : gv[j];
+                            }
                         }
                     }
                 }
@@ -244,7 +258,12 @@ __global__ void maxpool_bwd_kernel(const typename T::elem* __restrict__ gy, cons
             for (int dx = 0; dx < 2; ++dx) {
                 const int x = 2 * bx + dx;
                 if (x >= W) continue;
-                store8<T>(gx + (((size_t)img * H + y) * W + x) * CP + c8 * 8, g[dy][dx]);
+                if constexpr (RULE == 1) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        g[dy][dx][j] = (!((closed[dy][dx] >> j) & 1u) && g[dy][dx][j] > 0.f) ? g[dy][dx][j] : 0.f;
+                }
+                store8<B>(gx + (((size_t)img * H + y) * W + x) * CP + c8 * 8, g[dy][dx]);
             }
         }
     }
@@ -278,6 +297,21 @@ extern "C" int mil_maxpool_bwd(const void* gy, const uint8_t* widx, void* gx, in
     if (dtype == MIL_DT_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)gy, widx, (__bf16*)gx, n, H, W, Ho, Wo, cp, slope, apply_lrelu_mask);
     else if (dtype == MIL_DT_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<F32>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)gy, widx, (float*)gx, n, H, W, Ho, Wo, cp, slope, apply_lrelu_mask);
     else return MIL_ERR_ARG;
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The guided form of mil_maxpool_bwd (include/mil_hip.h): same gather, the LeakyReLU factor replaced by the guided gate.
+extern "C" int mil_maxpool_bwd_guided(const void* gy, const uint8_t* widx, void* gx, int n, int H, int W, int cp, int dtype,
+                                      void* stream) {
+    if (!gy || !widx || !gx || cp <= 0 || cp % 8 || n < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32) return MIL_ERR_ARG;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t total = (size_t)n * ((H + 1) / 2) * ((W + 1) / 2) * (cp / 8);
+    if (!total) return MIL_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MIL_DT_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<Guided<BF16>>, dim3(grid_for(total)), dim3(256), 0, st, (const __bf16*)gy, widx, (__bf16*)gx, n, H, W, Ho, Wo, cp, 0.f, 0);
+    else hipLaunchKernelGGL(maxpool_bwd_kernel<Guided<F32>>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)gy, widx, (float*)gx, n, H, W, Ho, Wo, cp, 0.f, 0);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -333,10 +367,14 @@ __global__ void avgpool_fc_fwd_kernel(const typename T::elem* __restrict__ x, co
 
 // dz[t][p][c] = lrelu'(act[t][p][c]) * (sum_o dfeats[t][o] * Wfc[o][c]) / hw      (padded channels -> 0)
 // g[c] first (one thread per channel), then the map in 8-channel pieces.
+// T = Guided<BF16 / F32> (mil_avgpool_fc_bwd_data_guided): dz = (act > 0 && g > 0) ? g : +0, the guided gate at the last block's
+// LeakyReLU (act required, slope not read).
 template <typename T>
 __global__ void avgpool_fc_bwd_kernel(const float* __restrict__ dfeats, const float* __restrict__ wfc,
                                       const typename T::elem* __restrict__ act, typename T::elem* __restrict__ dz, int hw,
                                       int CP, int C, int NF, float slope) {
+    using B = typename mil_tag<T>::base;
+    constexpr int RULE = mil_tag<T>::RULE;
     __shared__ float sd[POOL_MAXC], sg[POOL_MAXC];
     MIL_POISON_STATIC(sd); MIL_POISON_STATIC(sg);
     const int t = blockIdx.x, tid = threadIdx.x;
@@ -358,13 +396,18 @@ __global__ void avgpool_fc_bwd_kernel(const float* __restrict__ dfeats, const fl
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = sg[cg * 8 + j];
-        if (act) {
+        if constexpr (RULE == 1) {
             float a[8];
-            load8<T>(act + off, a);
+            load8<B>(act + off, a);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (a[j] > 0.f && v[j] > 0.f) ? v[j] : 0.f;
+        } else if (act) {
+            float a[8];
+            load8<B>(act + off, a);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] *= lrelu_grad(a[j], slope);
         }
-        store8<T>(dz + off, v);
+        store8<B>(dz + off, v);
     }
 }
 
@@ -508,5 +551,21 @@ extern "C" int mil_avgpool_fc_bwd(const float* dfeats, const float* wfc, const f
         hipLaunchKernelGGL(fc_wgrad_kernel, dim3((total + 3) / 4), dim3(256), 0, st, dfeats, pooled, dwfc, dbias, n, c, nf, accumulate);
         MIL_CHECK_LAUNCH();
     }
+    return MIL_OK;
+}
+
+// The data half of mil_avgpool_fc_bwd under guided backpropagation (include/mil_hip.h): no parameter gradient, act required.
+extern "C" int mil_avgpool_fc_bwd_data_guided(const float* dfeats, const float* wfc, const void* act, void* dz, int n, int hw,
+                                              int cp, int c, int nf, int dtype, void* stream) {
+    if (!dfeats || !wfc || !act || !dz || n < 0 || c <= 0 || nf <= 0 || c > POOL_MAXC || nf > POOL_MAXC || cp > POOL_MAXC || cp < c ||
+        (cp & 7) || hw <= 0)
+        return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32) return MIL_ERR_ARG;
+    if (n == 0) return MIL_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int bd = pool_block(c, nf, cp);
+    if (dtype == MIL_DT_BF16) hipLaunchKernelGGL(avgpool_fc_bwd_kernel<Guided<BF16>>, dim3(n), dim3(bd), 0, st, dfeats, wfc, (const __bf16*)act, (__bf16*)dz, hw, cp, c, nf, 0.f);
+    else hipLaunchKernelGGL(avgpool_fc_bwd_kernel<Guided<F32>>, dim3(n), dim3(bd), 0, st, dfeats, wfc, (const float*)act, (float*)dz, hw, cp, c, nf, 0.f);
+    MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -61,16 +61,47 @@ __device__ __forceinline__ void sdg_acc_store(float* __restrict__ dx, const f32x
     }
 }
 
+// The GATED epilogue (mil_stem_dgrad_gated: guided Grad-CAM): the same eight row pieces, each element
+// multiplied by its pixel's gate byte / 255 — one correctly rounded division and one product, contraction off — and stored.
+// The byte is the same for the three colour channels; a lane reads the two bytes of its two columns.
+__device__ __forceinline__ void sdg_gated_store(float* __restrict__ dx, const uint8_t* __restrict__ gate, const f32x4_t (&acc)[4], int img,
+                                                int g, int q, int r0, int H, int W, int H2, int W2, bool w_even) {
+#pragma clang fp contract(off)
+    const int x = 2 * q;
+    const bool two = x + 1 < W;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int r = r0 + m;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * r + dy;
+            if (g >= 3 || r >= H2 || q >= W2 || y >= H || x >= W) continue;
+            const uint8_t* gp = gate + ((size_t)img * H + y) * W + x;
+            const float s0 = (float)gp[0] / 255.f;
+            const float s1 = two ? (float)gp[1] / 255.f : 0.f;
+            float* o = dx + (((size_t)img * 3 + g) * H + y) * W + x;
+            const float v0 = acc[m][2 * dy] * s0;
+            const float v1 = acc[m][2 * dy + 1] * s1;
+            if (two && w_even) *reinterpret_cast<f32x2_t*>(o) = f32x2_t{v0, v1};
+            else { o[0] = v0; if (two) o[1] = v1; }
+        }
+    }
+}
+
 // bf16: three workgroups per CU (146 VGPRs, no spill; four would spill 35).  The fp32 forms hold 96 registers of filter
 // fragments and run one workgroup per SIMD set (252-254 VGPRs, no spill).
 // ACC (mil_stem_dgrad_acc: the inner step of integrated gradients and SmoothGrad): dx is a running sum
 // and the store epilogue is dx = dx + scale * (this launch's gradient), a product and a sum with contraction off; no
 // `reduce` form.  An output element belongs to one workgroup and one lane, so the read-modify-write needs no atomics.  The
 // ACC = false instantiations compile to the code they were before the parameter existed (`scale` is never read there).
-template <typename T, bool ACC = false>
-__global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_kernel(const typename T::elem* __restrict__ dstem, const void* __restrict__ wpack,
-                                                         float* __restrict__ dx, float* __restrict__ sal, int H, int W, int H2,
-                                                         int W2, int tiles_x, int tiles_y, int ntiles, int reduce, float scale) {
+// EPI: the store epilogue, a third one beside those two — SDG_PLAIN (dx / sal), SDG_ACC, SDG_GATED (mil_stem_dgrad_gated: `gate`
+// [n,H,W] uint8, no `reduce` form).  The loop is one function; stem_dgrad_kernel<T, ACC> keeps its name and its arguments and
+// compiles to the code it was (`gate` is never read there).
+enum { SDG_PLAIN = 0, SDG_ACC = 1, SDG_GATED = 2 };
+template <typename T, int EPI>
+__device__ __forceinline__ void stem_dgrad_body(const typename T::elem* dstem, const void* wpack,
+                                                float* dx, float* sal, const uint8_t* gate, int H, int W,
+                                                int H2, int W2, int tiles_x, int tiles_y, int ntiles, int reduce, float scale) {
     constexpr int ESZ = T::ESZ;
     constexpr int REC = SDG_CP * ESZ;                       // bytes of a pixel record in HBM (and of its LDS image)
     constexpr int PITCH = mil_pix_pitch(SDG_CP, ESZ);       // 48 (bf16) / 112 bytes
@@ -154,8 +185,13 @@ __global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_
         }
         // depth-to-space store: register j of lane group g is dx[img][c = g][2r + (j >> 1)][2q + (j & 1)]
         const int q = tx * SDG_TS + col;
-        if constexpr (ACC) {
+        if constexpr (EPI == SDG_ACC) {
             sdg_acc_store(dx, acc, scale, img, g, q, ty * SDG_TS + wave * 4, H, W, H2, W2, w_even);
+            __syncthreads();
+            continue;
+        }
+        if constexpr (EPI == SDG_GATED) {
+            sdg_gated_store(dx, gate, acc, img, g, q, ty * SDG_TS + wave * 4, H, W, H2, W2, w_even);
             __syncthreads();
             continue;
         }
@@ -195,6 +231,20 @@ __global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_
 }
 
 template <typename T, bool ACC = false>
+__global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_kernel(const typename T::elem* __restrict__ dstem, const void* __restrict__ wpack,
+                                                         float* __restrict__ dx, float* __restrict__ sal, int H, int W, int H2,
+                                                         int W2, int tiles_x, int tiles_y, int ntiles, int reduce, float scale) {
+    stem_dgrad_body<T, ACC ? SDG_ACC : SDG_PLAIN>(dstem, wpack, dx, sal, nullptr, H, W, H2, W2, tiles_x, tiles_y, ntiles, reduce, scale);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, T::DT == MIL_DT_BF16 ? 3 : 1) void stem_dgrad_gated_kernel(const typename T::elem* __restrict__ dstem, const void* __restrict__ wpack,
+                                                         float* __restrict__ dx, const uint8_t* __restrict__ gate, int H, int W, int H2,
+                                                         int W2, int tiles_x, int tiles_y, int ntiles) {
+    stem_dgrad_body<T, SDG_GATED>(dstem, wpack, dx, nullptr, gate, H, W, H2, W2, tiles_x, tiles_y, ntiles, 0, 0.f);
+}
+
+template <typename T, bool ACC = false>
 static int launch_stem_dgrad(const void* dstem, const void* wpack, float* dx, float* sal, int n, int H, int W, int reduce,
                              hipStream_t st, float scale = 0.f) {
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
@@ -230,4 +280,29 @@ extern "C" int mil_stem_dgrad_acc(const void* dstem, const void* wpack, float* a
     if (dtype == MIL_DT_BF16) return launch_stem_dgrad<BF16, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
     if (dtype == MIL_DT_F32) return launch_stem_dgrad<F32, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
     return launch_stem_dgrad<F32S, true>(dstem, wpack, acc_nchw, nullptr, n, H, W, 0, st, scale);
+}
+
+template <typename T>
+static int launch_stem_dgrad_gated(const void* dstem, const void* wpack, const uint8_t* gate, float* dx, int n, int H, int W, hipStream_t st) {
+    const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
+    const int tiles_x = (W2 + SDG_TS - 1) / SDG_TS, tiles_y = (H2 + SDG_TS - 1) / SDG_TS;
+    const long long ntiles = (long long)n * tiles_x * tiles_y;
+    if (ntiles > INT_MAX || (size_t)H2 * W2 * SDG_CP * T::ESZ >= 0x80000000ull) return MIL_ERR_UNSUPPORTED;
+    const int grid = (int)(ntiles < 2048 ? ntiles : 2048);
+    hipLaunchKernelGGL((stem_dgrad_gated_kernel<T>), dim3(grid), dim3(256), 0, st, (const typename T::elem*)dstem, wpack, dx, gate, H, W,
+                       H2, W2, tiles_x, tiles_y, (int)ntiles);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// dx_nchw [n,3,H,W] fp32 = dx * (gate / 255), dx what mil_stem_dgrad(reduce = 0) writes for the same arguments: include/mil_hip.h.
+extern "C" int mil_stem_dgrad_gated(const void* dstem, const void* wpack, const uint8_t* gate, float* dx_nchw, int n, int H, int W,
+                                    int dtype, void* stream) {
+    if (!dstem || !wpack || !gate || !dx_nchw || n < 0 || H <= 0 || W <= 0) return MIL_ERR_ARG;
+    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32 && dtype != MIL_DT_F32S) return MIL_ERR_ARG;
+    if (n == 0) return MIL_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MIL_DT_BF16) return launch_stem_dgrad_gated<BF16>(dstem, wpack, gate, dx_nchw, n, H, W, st);
+    if (dtype == MIL_DT_F32) return launch_stem_dgrad_gated<F32>(dstem, wpack, gate, dx_nchw, n, H, W, st);
+    return launch_stem_dgrad_gated<F32S>(dstem, wpack, gate, dx_nchw, n, H, W, st);
 }

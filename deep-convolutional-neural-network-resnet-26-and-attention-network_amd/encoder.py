@@ -391,8 +391,11 @@ class _Backward:
     """One backward pass: what its steps read (the net, the saved activations, the storage dtype), the gradients they leave
     in `grads` under (block, 1 | 2 | 0 for conv1 | conv2 | the projection) or ("stem", 0), and the workspace policy."""
 
-    def __init__(self, net, saved, dtype, allow_direct, want_dx, want_wgrad=True):
+    def __init__(self, net, saved, dtype, allow_direct, want_dx, want_wgrad=True, rule=None):
         self.net, self.saved, self.dtype, self.want_dx = net, saved, dtype, want_dx
+        # None: the LeakyReLU derivative at every activation.  "guided": guided backpropagation (encoder_pixel_gradient) — the
+        # walk of `_guided_block_backward`, data gradients only
+        self.rule = rule
         # False: a walk that is after the data gradient alone (encoder_pixel_gradient).  The stand-alone weight-gradient launches
         # are skipped; the one-pass kernels that make the data gradient still run, and what they leave in `grads` is dropped
         self.want_wgrad = want_wgrad
@@ -601,6 +604,31 @@ def _entry_block_backward(bw, bi, dz, dz1=None):
     return ops.conv(dz1, w1d, None, ops.cpad(cin), ks=3, stride=1, pad=1, res=addend, act=mask, **up)
 
 
+def _guided_block_backward(bw, bi, dz):
+    """Backward of block `bi` under guided backpropagation, identity or projection shortcut: returns the gradient of its input.
+    At each of the block's two LeakyReLUs the gradient handed on is g where the saved output and g are positive, else 0, g
+    being the TOTAL gradient arriving there (the shortcut's share included): `ops.conv_dgrad_rule(rule=1)`, the generic
+    implicit-GEMM kernel with the gate in its store epilogue.  What carries no activation — the 1x1 projection's transposed
+    conv, and conv1 of block 0, which reads the max-pool output — stays linear and goes through the plain `ops.conv`.  No
+    one-pass kernel, no `conv_pair` / `conv_chain` / `conv_dgrad_s2`, no weight gradient."""
+    net, blk = bw.net, bw.blocks[bi]
+    xin, o1, _out = bw.saved["blocks"][bi]
+    conv, s = blk.conv1, blk.stride
+    cin_p, cout_p = ops.cpad(conv.in_channels), ops.cpad(conv.out_channels)
+    w2d, _ = net._packed(f"b{bi}.c2", L.PACK_DGRAD)
+    w1d, _ = net._packed(f"b{bi}.c1", L.PACK_DGRAD)
+    dz1 = ops.conv_dgrad_rule(dz, w2d, cout_p, ks=3, pad=1, rule=1, act=o1)
+    up = dict(zero_insert=True, out_hw=xin.shape[1:3]) if s == 2 else {}        # a stride-2 conv transposed: on the zero-inserted dz
+    if blk.downsample is None:
+        addend = dz
+    else:
+        wdd, _ = net._packed(f"b{bi}.ds", L.PACK_DGRAD)
+        addend = ops.conv(dz, wdd, None, cin_p, ks=1, stride=1, pad=0, **up)
+    if bi == 0:                             # the max-pool output: no activation in between, nothing to gate
+        return ops.conv(dz1, w1d, None, cin_p, ks=3, stride=1, pad=1, res=addend, **up)
+    return ops.conv_dgrad_rule(dz1, w1d, cin_p, ks=3, pad=1, rule=1, res=addend, act=xin, **up)
+
+
 def _stage_dgrad_chain(bw, first, depth, dz_out):
     """Every 3x3 stride-1 data gradient of the stage in ONE launch (ops.conv_chain: whole images resident in LDS — the
     80-channel stage at 256x256 tiles), plus the weight gradients they feed.  Returns (dz of the entry block's output, its
@@ -643,6 +671,10 @@ def _stage_backward(bw, stage, dz):
     """Backward of `stage` = (index of its first block, its blocks): the stage-wide data-gradient chain where there is one,
     else block by block, last to first.  Returns the gradient of the stage's input."""
     first, blks = stage
+    if bw.rule is not None:
+        for bi in range(first + len(blks) - 1, first - 1, -1):
+            dz = _guided_block_backward(bw, bi, dz)
+        return dz
     chain = _stage_dgrad_chain(bw, first, len(blks), dz)
     if chain is not None:                   # what is left is the entry block, from its dz1 on
         return _entry_block_backward(bw, first, *chain)
@@ -673,14 +705,18 @@ def _stem_backward(bw, dz):
 
 
 # ---- the pieces of a backward walk, shared by encoder_backward, encoder_stage_gradient and encoder_pixel_gradient ----------
-def _check_dx_args(want_dx, dx_reduce, dx_acc):
+def _check_dx_args(want_dx, dx_reduce, dx_acc, gate=None):
     if dx_acc is not None and (dx_reduce is not None or not want_dx):
         raise ValueError("dx_acc accumulates the three-channel gradient: it goes with the tiles' gradient (want_dx=True) and without dx_reduce")
+    if gate is not None and (dx_reduce is not None or dx_acc is not None):
+        raise ValueError("gate multiplies the three-channel gradient as it is stored: it goes without dx_reduce and without dx_acc")
 
 
-def _pool_gradient(net, saved, dfeats, masked=True):
+def _pool_gradient(net, saved, dfeats, masked=True, rule=None):
     """The seed of a walk that drops the fc layer's gradient: from dfeats [T,80] to the gradient behind stage 4."""
-    return ops.avgpool_fc_bwd_data(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], saved["blocks"][-1][2], masked=masked)
+    # rule "guided": the gate at the last block's LeakyReLU in place of its derivative (the wrapper refuses it with masked=False)
+    return ops.avgpool_fc_bwd_data(dfeats.contiguous(), net.fc.weight.detach(), saved["pooled"], saved["blocks"][-1][2], masked=masked,
+                                   rule=0 if rule is None else 1)
 
 
 def _walk(bw, stages, dz, stem=False):
@@ -703,17 +739,22 @@ def _padded(dz, c, why):
     return dz
 
 
-def _tiles_gradient(bw, dz, dstem, dx_reduce, dx_acc):
+def _tiles_gradient(bw, dz, dstem, dx_reduce, dx_acc, gate=None):
     """The tail of a walk under want_dx, from dz, the gradient of the max-pool output, to the tiles: `ops.maxpool_bwd` unless the
     un-pooled stem gradient `dstem` is at hand (the fused stem backward never materialises it), then `ops.stem_dgrad` -> (dx, sal)
-    or, with dx_acc, `ops.stem_dgrad_acc` -> (None, None)."""
+    or, with dx_acc, `ops.stem_dgrad_acc` -> (None, None).  Under the guided rule the pool backward is its guided form; gate:
+    `ops.stem_dgrad`'s."""
     net, saved = bw.net, bw.saved
     _padded(dz, STEM_WIDTH, "the tiles' gradient needs the padded layout of the pooled stem gradient")
+    if dstem is None and bw.rule is not None:
+        dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"], rule=1)
     if dstem is None:
         dstem = ops.maxpool_bwd(dz, saved["widx"], saved["stem_hw"])
     if dx_acc is not None:
         ops.stem_dgrad_acc(dstem, net.stem_dgrad_packed(bw.dtype), saved["tile_hw"], dx_acc[0], dx_acc[1])
         return None, None
+    if gate is not None:
+        return ops.stem_dgrad(dstem, net.stem_dgrad_packed(bw.dtype), saved["tile_hw"], gate=gate)
     return ops.stem_dgrad(dstem, net.stem_dgrad_packed(bw.dtype), saved["tile_hw"], reduce=dx_reduce)
 
 
@@ -768,7 +809,10 @@ def encoder_stage_gradient(net, saved, dfeats, dtype, stage):
     return _padded(dz, STAGE_WIDTHS[stage - 1], "a stage's gradient is returned in the padded layout")
 
 
-def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=None, dx_reduce=None, dx_acc=None):
+BACKWARD_RULES = (None, "guided")         # encoder_pixel_gradient's rule: the LeakyReLU derivative, or guided backpropagation
+
+
+def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=None, dx_reduce=None, dx_acc=None, rule=None, gate=None):
     """The gradient of the TILES alone, (dx, sal) as `ops.stem_dgrad` returns them: the data-gradient-only walk from a seed to the
     pixels.  The seed is either `dz`, the gradient of the pre-activation map behind the output of stage `stage` (1..4; what
     `ops.stage_seed` makes, in that tensor's padded NHWC layout and dtype) for a forward that ran at least that far
@@ -777,10 +821,19 @@ def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=Non
     `want_wgrad=False`: no `ops.conv_wgrad`, no `conv_wgrad_pair` / `conv_entry_bwd`, no `stem_backward`; the one-pass kernels
     that make a data gradient still run and their weight gradients are dropped.  Then `_tiles_gradient`, the tail that
     `encoder_backward` runs under want_dx: dx is bit for bit that function's.  Padded gradient layout, `allow_direct=False`: no
-    `.grad` is read or written."""
+    `.grad` is read or written.
+    rule="guided": guided backpropagation.  At every LeakyReLU the gradient handed on is g where the saved
+    output and g are positive, else 0: `ops.avgpool_fc_bwd_data(rule=1)` for a dfeats seed (a dz seed is taken as given: the
+    gradient behind the stage's last LeakyReLU), `_guided_block_backward` for every block — `ops.conv_dgrad_rule(rule=1)` on the
+    generic kernel, the plain `ops.conv` for the two linear pieces — and `ops.maxpool_bwd(rule=1)`; no one-pass kernel,
+    `conv_pair`, `conv_chain` or `conv_dgrad_s2` runs and no weight gradient is launched.  With rule=None nothing changes.
+    gate: uint8 [T,H,W], handed to `ops.stem_dgrad`, which multiplies dx by gate / 255 as it stores it (without dx_reduce and
+    dx_acc; under either rule)."""
     if (dz is None) == (dfeats is None):
         raise ValueError("the seed is either dz (with its stage) or dfeats")
-    _check_dx_args(True, dx_reduce, dx_acc)
+    if rule not in BACKWARD_RULES:
+        raise ValueError(f"rule must be one of {BACKWARD_RULES}, got {rule!r}")
+    _check_dx_args(True, dx_reduce, dx_acc, gate)
     stages = net.stages()
     if dfeats is not None:
         if stage is not None:
@@ -795,12 +848,12 @@ def encoder_pixel_gradient(net, saved, dtype, *, dz=None, stage=None, dfeats=Non
         raise ValueError(f"the forward stopped below stage {stage}")
     top = saved["blocks"][first + len(blks) - 1][2]
     if dfeats is not None:
-        dz = _pool_gradient(net, saved, dfeats)
+        dz = _pool_gradient(net, saved, dfeats, rule=rule)
     elif dz.shape != top.shape or dz.dtype != top.dtype:
         raise ValueError(f"dz must be like the output of stage {stage}, {tuple(top.shape)} {top.dtype}, got {tuple(dz.shape)} {dz.dtype}")
-    bw = _Backward(net, saved, dtype, False, True, want_wgrad=False)
+    bw = _Backward(net, saved, dtype, False, True, want_wgrad=False, rule=rule)
     dz, _dstem = _walk(bw, stages[:stage], dz)
-    return _tiles_gradient(bw, dz, None, dx_reduce, dx_acc)
+    return _tiles_gradient(bw, dz, None, dx_reduce, dx_acc, gate)
 
 
 class _EncoderFn(torch.autograd.Function):

@@ -15,7 +15,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .attribution import LAYERS, bag_evaluate, bag_setup, check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of  # noqa: F401
+from .attribution import LAYERS, bag_evaluate, bag_setup, channel_list, check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of  # noqa: F401
 from .encoder import STAGE_WIDTHS, encoder_forward, encoder_pixel_gradient
 from .preprocess import U8Tiles
 
@@ -40,31 +40,6 @@ def _size(size):
     except TypeError:
         raise ValueError(f"size must be (H, W), got {size!r}") from None
     return h, w
-
-
-def _channel_list(channels, c, ntiles=None):
-    """One channel in [0, c) per tile as a list of ints; None: all channels of the stage; an int: that channel for every tile."""
-    if channels is None:
-        if ntiles is not None:
-            raise ValueError("channels: one per tile, or one int for all tiles")
-        channels = range(c)
-    elif isinstance(channels, int) and not isinstance(channels, bool):
-        channels = [channels] * (1 if ntiles is None else ntiles)
-    elif isinstance(channels, torch.Tensor):
-        channels = channels.tolist()
-    try:
-        out = [int(k) for k in channels]
-        exact = all(int(k) == k and not isinstance(k, bool) for k in channels)
-    except (TypeError, ValueError):
-        raise ValueError(f"channels must be integers, got {channels!r}") from None
-    if not out or not exact:
-        raise ValueError(f"channels must be a non-empty list of integers, got {list(channels)!r}")
-    if ntiles is not None and len(out) != ntiles:
-        raise ValueError(f"{len(out)} channels for {ntiles} tiles")
-    bad = [k for k in out if not 0 <= k < c]
-    if bad:
-        raise ValueError(f"channels must lie in [0, {c}), got {bad}")
-    return out
 
 
 def _init_range(init):
@@ -156,14 +131,14 @@ class FeatureVisualizer:
     # ---- methods -----------------------------------------------------------------------------------------------------------
     def filters(self, layer, channels=None, size=(256, 256), steps=30, init=(150, 180), seed=0):
         stage = stage_of(layer)
-        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1])
+        chans = channel_list(channels, STAGE_WIDTHS[stage - 1])
         size, steps, init = _size(size), _count(steps, "steps"), _init_range(init)
         return self._ascend(self._start(len(chans), size, init, seed), stage, chans, steps)
 
     def dream(self, tiles, layer, channels, steps=250):
         stage = stage_of(layer)
         check_tiles(None, tiles, None, WHAT)
-        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
+        chans = channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
         steps = _count(steps, "steps")
         dev = self._device()
         x = tiles.to(dev).float() if isinstance(tiles, U8Tiles) else tiles.detach().to(dev, torch.float32, copy=True).contiguous()
@@ -172,7 +147,7 @@ class FeatureVisualizer:
     def objective(self, tiles, layer, channels):
         stage = stage_of(layer)
         check_tiles(None, tiles, None, WHAT)
-        chans = _channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
+        chans = channel_list(channels, STAGE_WIDTHS[stage - 1], tiles.shape[0])
         x = device_tiles(self.net, tiles, "FeatureVisualizer")
         ch = torch.tensor(chans, dtype=torch.int32).to(x.device)
         with torch.no_grad(), compute_mode(self.net) as dtype:

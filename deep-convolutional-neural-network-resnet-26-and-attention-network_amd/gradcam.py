@@ -70,9 +70,14 @@ class TileGradCam:
         if normalize not in NORMALIZE:
             raise ValueError(f"normalize must be one of {NORMALIZE}, got {normalize!r}")
         label = self._check(tiles, label)
-        act, grad, c, hw = self._stage_tensors(tiles, label)
-        if normalize == "tile":
-            return ops.grad_cam(act, grad, c, hw, offset=offset, want_raw=False)[1]
-        raw = ops.grad_cam(act, grad, c, hw, offset=offset, want_map=False)[0]
-        rng = torch.stack((raw.amin(), raw.amax()))
-        return ops.grad_cam(act, grad, c, hw, offset=offset, value_range=rng, want_raw=False)[1]
+        return cam_bytes(*self._stage_tensors(tiles, label), offset, normalize)
+
+
+def cam_bytes(act, grad, c, hw, offset, normalize):
+    """The uint8 [T,H,W] maps of `TileGradCam.maps` from a stage's output and its gradient (`TileGuidedGradCam` makes its gate
+    with the same launches)."""
+    if normalize == "tile":
+        return ops.grad_cam(act, grad, c, hw, offset=offset, want_raw=False)[1]
+    raw = ops.grad_cam(act, grad, c, hw, offset=offset, want_map=False)[0]
+    rng = torch.stack((raw.amin(), raw.amax()))
+    return ops.grad_cam(act, grad, c, hw, offset=offset, value_range=rng, want_raw=False)[1]

@@ -170,6 +170,55 @@ def conv(x, wpack, bias_pad, cout_p, *, ks, stride, pad, out_hw=None, res=None, 
     return y
 
 
+RULES = (0, 1)                                    # mil_conv_dgrad_rule's rule: 0 the plain LeakyReLU derivative, 1 guided backpropagation
+
+
+def _check_rule(rule):
+    if isinstance(rule, bool) or rule not in RULES:
+        raise ValueError(f"rule must be 0 (plain) or 1 (guided), got {rule!r}")
+    return int(rule)
+
+
+def conv_dgrad_rule(x, wpack, cout_p, *, ks, pad, rule, res=None, act=None, zero_insert=False, out_hw=None, slope=LEAK):
+    """A stride-1 (or, with zero_insert, transposed stride-2) data gradient on the generic implicit-GEMM kernel — see
+    mil_conv_dgrad_rule: x = dz, wpack = MIL_PACK_DGRAD fragments.  rule=0: (conv(x) + res) * lrelu'(act), what `conv` computes;
+    rule=1, guided backpropagation: v = conv(x) + res, y = v where act > 0 and v > 0, else +0 — `act` is required.  Never the
+    persistent, resident or streaming kernels `conv` may choose."""
+    rule = _check_rule(rule)
+    if rule == 1 and act is None:
+        raise ValueError("rule=1 gates by the saved activation: act is required")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [n,h,w,cin_p], got {tuple(x.shape)}")
+    n, h, w, cin_p = x.shape
+    if zero_insert:
+        if out_hw is None:
+            raise ValueError("zero_insert needs the full-resolution output size")
+        ho, wo = (int(v) for v in out_hw)
+        if ((ho + 2 * pad - ks) // 2 + 1, (wo + 2 * pad - ks) // 2 + 1) != (h, w):
+            raise ValueError(f"a {ks}x{ks} stride-2 conv (pad {pad}) of {ho}x{wo} maps is not {h}x{w}")
+    else:
+        if out_hw is not None:
+            raise ValueError("out_hw goes with zero_insert")
+        ho, wo = h + 2 * pad - ks + 1, w + 2 * pad - ks + 1
+        if ho < 1 or wo < 1:
+            raise ValueError(f"no output for {h}x{w} maps, ks {ks}, pad {pad}")
+    if cin_p % 8 or cout_p % 8:
+        raise ValueError(f"padded channel counts are multiples of 8, got {cin_p} -> {cout_p}")
+    frag_elems = (ks * ks * (cin_p // 8) + 3) // 4 * ((cout_p + 15) // 16) * 64 * 8      # [kstep][column tile][64 lanes][8]
+    if not wpack.is_cuda or wpack.dtype != x.dtype or wpack.numel() < frag_elems:
+        raise ValueError(f"wpack: expected {frag_elems} {x.dtype} elements of MIL_PACK_DGRAD fragments on the device, got "
+                         f"{wpack.numel()} {wpack.dtype}")
+    y = torch.empty((n, ho, wo, cout_p), dtype=x.dtype, device=x.device)
+    _need(x, x.shape, x.dtype, "x")
+    _need(res, y.shape, x.dtype, "res")
+    _need(act, y.shape, x.dtype, "act")
+    _launch("mil_conv_dgrad_rule", ("conv_dgrad_rule", cin_p, cout_p, ks, rule, bool(zero_insert), n, ho, wo),
+            x.data_ptr(), wpack.data_ptr(), None, L.ptr(res), L.ptr(act), y.data_ptr(),
+            n, h, w, cin_p, ho, wo, cout_p, ks, 1, pad, 1 if zero_insert else 0, 0, slope, rule,
+            L.dt_code(x.dtype, mma=True), L.stream_ptr())
+    return y
+
+
 def wgrad_workspace_bytes(n, h, w, cin, ho, wo, cout, ks, stride, pad, stem, dtype):
     need = ctypes.c_size_t(0)
     L.check(L.lib().mil_conv_wgrad_workspace(ctypes.byref(need), n, h, w, cin, ho, wo, cout, ks, stride, pad,
@@ -238,15 +287,24 @@ def maxpool_fwd(x):
     return y, widx
 
 
-def maxpool_bwd(gy, widx, in_hw, lrelu_mask=True, slope=LEAK):
+def maxpool_bwd(gy, widx, in_hw, lrelu_mask=True, slope=LEAK, rule=0):
     """Gradient of the pooled tensor scattered back to the [n,H,W,cp] pool input; with lrelu_mask the LeakyReLU
-    backward of that input is applied too (from the sign bit recorded in widx)."""
+    backward of that input is applied too (from the sign bit recorded in widx).  rule=1 (mil_maxpool_bwd_guided): the guided
+    gate in place of that factor — the summed gradient of a pixel where the pixel's value and the sum are positive, else +0."""
+    rule = _check_rule(rule)
+    if rule == 1 and not lrelu_mask:
+        raise ValueError("rule=1 replaces the LeakyReLU factor: it does not go with lrelu_mask=False")
     n, ho, wo, cp = widx.shape
     h, w = in_hw
     if ((h - 1) // 2 + 1, (w - 1) // 2 + 1) != (ho, wo):
         raise ValueError(f"pool input {h}x{w} does not produce {ho}x{wo}")
     _need(gy, widx.shape, gy.dtype, "gy")
     gx = torch.empty((n, h, w, cp), dtype=gy.dtype, device=gy.device)
+    if rule == 1:
+        _need(widx, widx.shape, torch.uint8, "widx")
+        L.check(L.lib().mil_maxpool_bwd_guided(gy.data_ptr(), widx.data_ptr(), gx.data_ptr(), n, h, w, cp, L.dt_code(gy.dtype),
+                                               L.stream_ptr()), "mil_maxpool_bwd_guided")
+        return gx
     L.check(L.lib().mil_maxpool_bwd(gy.data_ptr(), widx.data_ptr(), gx.data_ptr(), n, h, w, cp, 1 if lrelu_mask else 0,
                                     slope, L.dt_code(gy.dtype), L.stream_ptr()), "mil_maxpool_bwd")
     return gx
@@ -646,14 +704,17 @@ def stem_forward(kind, x, wpack, bias_pad, cout_p, *, dtype, slope=LEAK, keep_s2
     return xs, pool, widx, tuple(stem.shape[1:3]), stem
 
 
-def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None):
+def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None, gate=None):
     """Data gradient of the stem convolution (see mil_stem_dgrad): dstem [n,ceil(H/2),ceil(W/2),24] — the un-pooled stem
     gradient `maxpool_bwd` returns, bf16 or fp32 — and the MIL_PACK_STEM_DGRAD fragments of conv1.weight -> (dx, sal) for
     tiles of hw = (H, W).  reduce=None: dx [n,3,H,W] fp32 and sal None.  reduce="max_abs": sal [n,H,W] fp32 = max_c |dx| from
     the same accumulators, and dx None unless a `dx` tensor is handed in to be written too.  `dx` / `sal`: the caller's own
-    output tensors (checked) in place of fresh ones."""
+    output tensors (checked) in place of fresh ones.  gate: uint8 [n,H,W], with reduce=None only (see mil_stem_dgrad_gated) —
+    dx is then the gradient times gate / 255 per pixel, multiplied in the kernel's store epilogue: no ungated tensor is made."""
     if reduce not in (None, "max_abs"):
         raise ValueError(f"reduce must be None or 'max_abs', got {reduce!r}")
+    if gate is not None and (reduce is not None or sal is not None):
+        raise ValueError("gate multiplies the three-channel gradient: it goes with reduce=None and without sal")
     if dstem.dim() != 4:
         raise ValueError(f"dstem must be [n,H2,W2,24], got {tuple(dstem.shape)}")
     n = dstem.shape[0]
@@ -672,6 +733,13 @@ def stem_dgrad(dstem, wpack, hw, *, reduce=None, dx=None, sal=None):
         sal = torch.empty((n, h, w), dtype=torch.float32, device=dstem.device)
     _need(dx, (n, 3, h, w), torch.float32, "dx")
     _need(sal, (n, h, w), torch.float32, "sal")
+    if gate is not None:
+        if not isinstance(gate, torch.Tensor):
+            raise ValueError("gate must be a uint8 [n,H,W] tensor on the device")
+        _need(gate, (n, h, w), torch.uint8, "gate")
+        _launch("mil_stem_dgrad_gated", ("stem_dgrad_gated", n, h, w), dstem.data_ptr(), wpack.data_ptr(), gate.data_ptr(),
+                dx.data_ptr(), n, h, w, code, L.stream_ptr())
+        return dx, None
     _launch("mil_stem_dgrad", ("stem_dgrad", n, h, w, reduce is not None), dstem.data_ptr(), wpack.data_ptr(), L.ptr(dx),
             L.ptr(sal), n, h, w, 0 if reduce is None else 1, code, L.stream_ptr())
     return dx, sal
@@ -1069,10 +1137,14 @@ def avgpool_fc_fwd(x, wfc, c, bias=None):
     return pooled, feats
 
 
-def avgpool_fc_bwd_data(dfeats, wfc, pooled, act, masked=True, slope=LEAK):
+def avgpool_fc_bwd_data(dfeats, wfc, pooled, act, masked=True, slope=LEAK, rule=0):
     """The data half of `avgpool_fc_bwd` alone: dz [n,h,w,cp] = (dfeats @ wfc) / (h w), times lrelu'(act) when `masked` — the
     gradient of the pre-activation map the backward chain carries; masked=False: the gradient of `act` itself, the stage's
-    OUTPUT, which is what Grad-CAM reads.  No parameter gradient is computed."""
+    OUTPUT, which is what Grad-CAM reads.  No parameter gradient is computed.  rule=1 (mil_avgpool_fc_bwd_data_guided): the
+    guided gate in place of lrelu' — the gradient where act and the gradient are positive, else +0."""
+    rule = _check_rule(rule)
+    if rule == 1 and not masked:
+        raise ValueError("rule=1 replaces the LeakyReLU factor: it does not go with masked=False")
     n, h, w, cp = act.shape
     nf, c = wfc.shape
     _need(dfeats, (n, nf), torch.float32, "dfeats")
@@ -1080,6 +1152,10 @@ def avgpool_fc_bwd_data(dfeats, wfc, pooled, act, masked=True, slope=LEAK):
     _need(act, act.shape, act.dtype, "act")
     dz = torch.empty_like(act)
     _need(pooled, (n, c), torch.float32, "pooled")        # (read by the weight-gradient half only, which a null dwfc leaves out)
+    if rule == 1:
+        L.check(L.lib().mil_avgpool_fc_bwd_data_guided(dfeats.data_ptr(), wfc.data_ptr(), act.data_ptr(), dz.data_ptr(), n, h * w, cp,
+                                                       c, nf, L.dt_code(act.dtype), L.stream_ptr()), "mil_avgpool_fc_bwd_data_guided")
+        return dz
     L.check(L.lib().mil_avgpool_fc_bwd(dfeats.data_ptr(), wfc.data_ptr(), pooled.data_ptr(), act.data_ptr() if masked else None,
                                        dz.data_ptr(), None, None, n, h * w, cp, c, nf, 0, slope, L.dt_code(act.dtype),
                                        L.stream_ptr()), "mil_avgpool_fc_bwd")

@@ -130,6 +130,22 @@ int mil_conv_igemm(const void* x, const void* wpack, const float* bias_pad, cons
                    void* y, int n_img, int H, int W, int cin_p, int Ho, int Wo, int cout_p, int ks, int stride,
                    int pad, int zero_insert, int apply_lrelu, float slope, int dtype, void* stream);
 
+/* The data gradients of a guided-backpropagation walk (`guided_backprop.py` of the reference's vendored saliency toolkit,
+ * pytorch-cnn-visualizations-master/src, lines 41-50: every activation hands on (out > 0) * clamp(grad, min=0)).  The operands
+ * are mil_conv_igemm's, run over dz with MIL_PACK_DGRAD weights, plus `rule`:
+ *     rule == 0:  y = mask( lrelu?( conv(x) + bias? + res? ) ) — mil_conv_igemm's result on the generic implicit-GEMM kernel
+ *     rule == 1:  v = lrelu?( conv(x) + bias? + res? );  y = (act > 0 && v > 0) ? v : +0        (act required; slope gates nothing)
+ * v is the TOTAL gradient arriving at the activation `act` is the output of (the convolution's own sum plus `res`, the shortcut's
+ * share), so the gate sees what the toolkit's hook sees; LeakyReLU(0.1) is read as a ReLU, its 0.1 branch carries nothing.
+ * Always the generic kernel (256-pixel tiles where the halo and a filter chunk fit LDS, else 64-pixel tiles), never the
+ * persistent, resident or streaming forms: rule 1 is bit for bit the gate applied to rule 0's output for the same operands with
+ * act = NULL.  MIL_DT_BF16 / MIL_DT_F32 / MIL_DT_F32S; (cin_p, cout_p) the square widths 24, 40, 64, 80 and the stage-entry
+ * gradients 40 -> 24, 64 -> 40, 80 -> 64, stride 1 or zero_insert; anything else: MIL_ERR_UNSUPPORTED.  Null x / wpack / y,
+ * rule outside {0,1}, rule 1 without act, another dtype, a size below 1: MIL_ERR_ARG — all decided on the host. */
+int mil_conv_dgrad_rule(const void* x, const void* wpack, const float* bias_pad, const void* res, const void* act,
+                        void* y, int n_img, int H, int W, int cin_p, int Ho, int Wo, int cout_p, int ks, int stride,
+                        int pad, int zero_insert, int apply_lrelu, float slope, int rule, int dtype, void* stream);
+
 /* ---- convolution weight / bias gradient ----------------------------------------------------
  * Replaces the autograd weight- and bias-gradient of the same convs.  dw is written (not
  * accumulated) in the reference layout [cout][cin][k][k] fp32 (k = 7 when stem_mode), db [cout]
@@ -178,6 +194,12 @@ int mil_conv_bwd_fused(const void* dz, const void* wpack_dgrad, const void* x, c
 int mil_maxpool_fwd(const void* x, void* y, uint8_t* widx, int n, int H, int W, int cp, int dtype, void* stream);
 int mil_maxpool_bwd(const void* gy, const uint8_t* widx, void* gx, int n, int H, int W, int cp,
                     int apply_lrelu_mask, float slope, int dtype, void* stream);
+/* mil_maxpool_bwd under guided backpropagation (see mil_conv_dgrad_rule), for the stem's LeakyReLU: the same gather, then
+ *     gx = (winner > 0 && s > 0) ? s : +0,    s = the SUM of the window contributions of the pixel (what
+ * mil_maxpool_bwd(apply_lrelu_mask = 0) writes) — the gate applies to the total gradient arriving at the activation, not to
+ * each window's share; the winner's sign is bit 4 of widx.  MIL_DT_BF16 / MIL_DT_F32 (the fp32 storage of both fp32 modes).
+ * Null pointer, cp < 8 or cp % 8 != 0, n < 0, H or W < 1, another dtype: MIL_ERR_ARG; nothing to do: MIL_OK, no launch. */
+int mil_maxpool_bwd_guided(const void* gy, const uint8_t* widx, void* gx, int n, int H, int W, int cp, int dtype, void* stream);
 
 /* Tile pre-processing on the device (RoiBuilder.py:193-210: Pad(100) -> RandomCrop(roi) -> Resize(res) ->
  * RandomHorizontalFlip -> RandomVerticalFlip -> ToTensor -> Normalize(.5,.5); `img_finalize_flat` without pad/crop/flips):
@@ -475,6 +497,18 @@ int mil_stem_dgrad(const void* dstem, const void* wpack, float* dx_nchw, float* 
 int mil_stem_dgrad_acc(const void* dstem, const void* wpack, float* acc_nchw, float scale, int n, int H, int W, int dtype,
                        void* stream);
 
+/* The gated form of mil_stem_dgrad(reduce = 0), the last launch of guided Grad-CAM (`guided_gradcam.py` of the same toolkit: the
+ * guided gradient times the class activation map):
+ *     dx_nchw [n,3,H,W] fp32 = dx * (gate / 255)
+ * with dx what mil_stem_dgrad writes for the same dstem / wpack / dtype, from the same accumulators, and gate [n,H,W] uint8 one
+ * byte per pixel for its three channels (mil_grad_cam's map).  float(gate) / 255.f is one correctly rounded division and the
+ * product one multiplication, never fused: bit for bit the fp32 `dx * (gate / 255)` of IEEE arithmetic.  No ungated tensor, no
+ * atomics, no workspace: bit-repeatable.  There is no `reduce` form.  Null dstem / wpack / gate / dx_nchw, n < 0, H or W < 1,
+ * another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch; one image's dstem of 2 GiB or more: MIL_ERR_UNSUPPORTED — all decided
+ * on the host before any GPU call. */
+int mil_stem_dgrad_gated(const void* dstem, const void* wpack, const uint8_t* gate, float* dx_nchw, int n, int H, int W,
+                         int dtype, void* stream);
+
 /* A point of a straight path from a baseline colour to the tiles, optionally with Gaussian noise — the input of one step of
  * integrated gradients (`integrated_gradients.py`) or SmoothGrad (`smooth_grad.py`) of the same toolkit:
  *     out[t,c,y,x] = base[c] + alpha * (v - base[c]) + sigma * n(seed, sample, i)          out [n,3,H,W] fp32
@@ -643,6 +677,12 @@ int mil_avgpool_fc_fwd(const void* x, const float* wfc, const float* bias, float
 int mil_avgpool_fc_bwd(const float* dfeats, const float* wfc, const float* pooled, const void* act, void* dz,
                        float* dwfc, float* dbias, int n, int hw, int cp, int c, int nf, int accumulate, float slope,
                        int dtype, void* stream);
+/* The data half of mil_avgpool_fc_bwd (dwfc = NULL) under guided backpropagation (see mil_conv_dgrad_rule), for the last
+ * block's LeakyReLU:  dz = (act > 0 && g > 0) ? g : +0,  g = (dfeats @ wfc)/hw — what the plain call writes with act = NULL.
+ * No parameter gradient.  MIL_DT_BF16 / MIL_DT_F32.  Null pointer (act included), n < 0, hw < 1, c or nf outside [1, 512],
+ * cp > 512, cp < c, cp % 8 != 0, another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch. */
+int mil_avgpool_fc_bwd_data_guided(const float* dfeats, const float* wfc, const void* act, void* dz, int n, int hw, int cp,
+                                   int c, int nf, int dtype, void* stream);
 /* The parameter gradients of the same layer on their own (two-stage, coalesced): dwfc [nf][c] (+)= dfeats^T pooled,
  * dbias [nf] (+)= column sums of dfeats (may be null).  mil_avgpool_fc_bwd skips them when its dwfc is null.
  * Workspace from mil_fc_wgrad_workspace. */
