@@ -25,6 +25,7 @@ PACK_FWD, PACK_DGRAD, PACK_STEM, PACK_DGRAD_S2, PACK_STEM_DGRAD = 0, 1, 2, 3, 4
 FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pillow's own codes)
 ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per tile in mil_attr_finish's workspace
 SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per tile in mil_stage_seed's workspace
+REG_SLICES = 16                              # MIL_REG_SLICES: partial sums per tile and norm in mil_pixel_reg's workspace
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -107,6 +108,11 @@ _SIGS = {
     "mil_attr_finish": ([_vp, _vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
     "mil_stage_seed": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_pixel_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i] + [_f] * 9 + [_vp], _i),
+    "mil_stage_energy": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mil_stage_match": ([_vp] * 6 + [_i] * 5 + [_f, _f, _i, _vp], _i),
+    "mil_pixel_reg": ([_vp] * 5 + [_i] * 4 + [_f, _f, _i, _i, _vp], _i),
+    "mil_pixel_shift": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mil_pixel_momentum_step": ([_vp] * 5 + [_sz, _i, _f, _f, _f, _vp], _i),
     "mil_map_quantile_workspace":([_c.POINTER(_sz), _i, _i], _i),
     "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),
     "mil_attr_render": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),

@@ -5,8 +5,8 @@
 //   stage_seed_kernel<T>          J_t = mean_{y,x} act[t,y,x,ch_t] (partial sums) and dz, the gradient of -J_t in the form the
 //                                 backward chain carries: -(1/(h w)) * lrelu'(act) at channel ch_t, zero everywhere else
 //   stage_seed_sum_kernel         a tile's partial sums added in slice order, divided by h w: objective [T]
-//   pixel_step_kernel<RULE, PROJ> one SGD or Adam step on x [T,3,H,W] fp32 in place, the projection of the new image (none,
-//                                 clamp to [-1,1], or the round trip through bytes) and its bytes, in one pass
+//   pixel_step_kernel<RULE, PROJ> one SGD, Adam or momentum-SGD step on x [T,3,H,W] fp32 in place, the projection of the new image
+//                                 (none, clamp to [-1,1], or the round trip through bytes) and its bytes, in one pass
 //
 // Every product, quotient, difference and sum that reaches an output is a single correctly rounded fp32 operation (rn_mul, rn_add,
 // rn_sub of rounded.cuh carry no `contract` flag; __fdiv_rn, rn_sqrt): numpy's fp32 arithmetic gives the same bits.  Both are streaming
@@ -79,7 +79,7 @@ struct PixelStepArgs {
 
 // One thread = the four elements 4 q .. 4 q + 3 of the linear index (fewer in the last group).  vec: every pointer is on its
 // 16-byte (u8_out: 4-byte) grid, so a whole group is one aligned load and store per tensor; the last, short group goes element by
-// element.  RULE 0: SGD, 1: Adam.  PROJ 0: none, 1: clamp to [-1, 1], 2: table[encode(x)], the round trip through bytes.
+// element.  RULE 0: SGD, 1: Adam, 2: SGD with momentum (m is its buffer, a.beta1 the momentum; mil_pixel_momentum_step).  PROJ 0: none, 1: clamp to [-1, 1], 2: table[encode(x)], the round trip through bytes.
 template <int RULE, int PROJ>
 __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ m,
                                                                float* __restrict__ v, uint8_t* __restrict__ u8_out,
@@ -100,12 +100,18 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
 #pragma unroll
             for (int j = 0; j < 4; ++j) { mv[j] = rm[j]; vv[j] = rv[j]; }
         }
+        if constexpr (RULE == 2) {
+            const f32x4_t rm = *reinterpret_cast<const f32x4_t*>(m + i0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mv[j] = rm[j];
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (j < cnt) {
                 xv[j] = x[i0 + j]; gv[j] = g[i0 + j];
                 if constexpr (RULE == 1) { mv[j] = m[i0 + j]; vv[j] = v[i0 + j]; }
+                if constexpr (RULE == 2) mv[j] = m[i0 + j];
             }
     }
     unsigned codes = 0;
@@ -115,6 +121,9 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
         float xn;
         if constexpr (RULE == 0) {
             xn = rn_sub(xv[j], rn_mul(a.lr, gd));
+        } else if constexpr (RULE == 2) {
+            mv[j] = rn_add(rn_mul(a.beta1, mv[j]), gd);
+            xn = rn_sub(xv[j], rn_mul(a.lr, mv[j]));
         } else {
             mv[j] = rn_add(rn_mul(a.beta1, mv[j]), rn_mul(a.omb1, gd));
             vv[j] = rn_add(rn_mul(a.beta2, vv[j]), rn_mul(rn_mul(a.omb2, gd), gd));
@@ -134,6 +143,7 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
             *reinterpret_cast<f32x4_t*>(m + i0) = f32x4_t{mv[0], mv[1], mv[2], mv[3]};
             *reinterpret_cast<f32x4_t*>(v + i0) = f32x4_t{vv[0], vv[1], vv[2], vv[3]};
         }
+        if constexpr (RULE == 2) *reinterpret_cast<f32x4_t*>(m + i0) = f32x4_t{mv[0], mv[1], mv[2], mv[3]};
         if (u8_out) *reinterpret_cast<unsigned*>(u8_out + i0) = codes;
     } else {
 #pragma unroll
@@ -141,6 +151,7 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
             if (j < cnt) {
                 x[i0 + j] = xv[j];
                 if constexpr (RULE == 1) { m[i0 + j] = mv[j]; v[i0 + j] = vv[j]; }
+                if constexpr (RULE == 2) m[i0 + j] = mv[j];
                 if (u8_out) u8_out[i0 + j] = (uint8_t)((codes >> (8 * j)) & 255u);
             }
     }
@@ -200,6 +211,23 @@ extern "C" int mil_pixel_step(float* x, const float* g, float* m, float* v, unsi
         launch_pixel_step<0>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
     else
         launch_pixel_step<1>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The third RULE of the kernel above behind an entry of its own: mil_pixel_step's rules and their instantiations stay as they are.
+extern "C" int mil_pixel_momentum_step(float* x, const float* g, float* buf, unsigned char* u8_out, const float* table, size_t total,
+                                       int project, float lr, float weight_decay, float momentum, void* stream) {
+    if (!x || !g || !buf || project < 0 || project > 2) return MIL_ERR_ARG;
+    if (project == 2 && !table) return MIL_ERR_ARG;
+    if (!(lr == lr) || !(weight_decay == weight_decay) || !(momentum == momentum)) return MIL_ERR_ARG;
+    if (total == 0) return MIL_OK;
+    const unsigned long long blocks = (((unsigned long long)total + 3) / 4 + FV_THREADS - 1) / FV_THREADS;
+    if (blocks > INT_MAX) return MIL_ERR_UNSUPPORTED;
+    const uintptr_t grid16 = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf);
+    const int vec = !(grid16 & 15) && !(reinterpret_cast<uintptr_t>(u8_out) & 3);
+    const PixelStepArgs a{lr, weight_decay, momentum, 0.f, 0.f, 0.f, 1.f, 1.f, 0.f};
+    launch_pixel_step<2>(project, dim3((unsigned)blocks), reinterpret_cast<hipStream_t>(stream), x, g, buf, nullptr, u8_out, table, a, total, vec);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -1,0 +1,167 @@
+"""Feature inversion and the pixel regularisers: an image optimised on the device until a stage sees in it what it saw in a tile.
+
+`inverted_representation.py` of the saliency toolkit the reference vendors (pytorch-cnn-visualizations-master/src) is Mahendran &
+Vedaldi's inverted representation: from noise, SGD with momentum on 1e-1 * ||f(x) - f(x0)||^2 / ||f(x0)||^2 plus an alpha norm
+and a total-variation norm of the image, 201 steps of a Python loop around a hooked VGG, one image at a time.  Here the target is
+the output of `layerN` of the tile encoder, a whole bag of tiles is inverted at once, and a step is the optional jittered copy
+(`ops.pixel_shift`), the encoder's forward cut short at the stage (`encoder_forward(upto=)`), one launch pair that reads the
+distance and writes the seed of the backward pass (`ops.stage_match`), the data-gradient-only walk to the pixels
+(`encoder_pixel_gradient`), one launch that moves the gradient back through the jitter and adds the regularisers' gradients
+(`ops.pixel_reg`) and one that takes the momentum step, projects and encodes (`ops.pixel_momentum_step`) — nothing synchronises
+with the host.  `PixelRegularizer` also serves `FeatureVisualizer(regularizer=)`.  DESIGN.md section 3.46.
+"""
+from collections import namedtuple
+
+import torch
+
+from . import ops
+from .attribution import check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of
+from .encoder import STAGE_WIDTHS, encoder_forward, encoder_pixel_gradient
+from .preprocess import U8Tiles
+
+WHAT = "feature inversion"
+
+InversionResult = namedtuple("InversionResult", ["u8", "x", "trace", "terms"])
+InversionResult.__doc__ = """What `FeatureInverter.invert` returns: `u8`, the final images as `U8Tiles`; `x`, the same images as the
+fp32 [T,3,H,W] stack that was optimised; `trace` fp32 [steps, T], the weighted distance weight * ||f(x) - f(x0)||^2 / ||f(x0)||^2
+of the image each step STARTED from; `terms` fp32 [steps, 2, T], that image's sum of x^alpha and its total variation."""
+
+
+def _count(v, name, least=1):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < least:
+        raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
+    return int(v)
+
+
+class PixelRegularizer:
+    """`PixelRegularizer(alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0)` — what is added to an objective that is
+    minimised over pixels: alpha_weight * sum x^alpha + tv_weight * TV(x), TV the toolkit's `total_variation_norm` with beta = 2;
+    the defaults are the toolkit's (inverted_representation.py:74-84).  alpha: 2, 4, 6 or 8.  jitter: the largest shift in pixels
+    of the cyclic jitter — every step evaluates the network on the image shifted by (dy, dx), each drawn from [-jitter, jitter],
+    and the gradient is shifted back; 0: none.  `shifts(steps)` draws all of them at once from a CPU `torch.Generator` seeded
+    with `seed`: the global generators are not touched and the shifts are the same on every machine.  A value object: it holds
+    no tensor."""
+
+    def __init__(self, alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0):
+        self.alpha, self.alpha_weight, self.tv_weight = ops.reg_weights(alpha, alpha_weight, tv_weight)
+        self.jitter = _count(jitter, "jitter", 0)
+        self.seed = _count(seed, "seed", 0)
+
+    def __repr__(self):
+        return (f"PixelRegularizer(alpha={self.alpha}, alpha_weight={self.alpha_weight}, tv_weight={self.tv_weight}, "
+                f"jitter={self.jitter}, seed={self.seed})")
+
+    def shifts(self, steps):
+        """[(dy, dx)] * steps: zeros without jitter, else `torch.randint(-jitter, jitter + 1, (steps, 2))` of a generator of
+        their own."""
+        if not self.jitter:
+            return [(0, 0)] * steps
+        gen = torch.Generator().manual_seed(self.seed)
+        return [tuple(s) for s in torch.randint(-self.jitter, self.jitter + 1, (steps, 2), generator=gen).tolist()]
+
+    def jittered(self, x, xs, shift):
+        """Step 1 of a regularised step: the tensor the network reads — x itself without jitter, else its shifted copy in xs."""
+        return ops.pixel_shift(x, xs, shift) if self.jitter else x
+
+    def gradient(self, x, g, out, shift, terms=None):
+        """Step 5: g, the gradient with respect to `jittered(x)`, as the gradient of the regularised objective with respect to x.
+        Without jitter it is written over g; with it, into `out`."""
+        return ops.pixel_reg(x, g, out if self.jitter else g, alpha=self.alpha, alpha_weight=self.alpha_weight, tv_weight=self.tv_weight,
+                             shift=shift, terms=terms)
+
+
+def check_regularizer(regularizer, optional=False):
+    if regularizer is None and optional:
+        return None
+    if not isinstance(regularizer, PixelRegularizer):
+        raise ValueError(f"regularizer must be a mil_amd.PixelRegularizer{' or None' if optional else ''}, got {type(regularizer).__name__}")
+    return regularizer
+
+
+class FeatureInverter:
+    """`FeatureInverter(model, lr=100.0, momentum=0.9, lr_decay=None, weight=0.1, regularizer=PixelRegularizer(), project="none")`
+    — `model`: a `mil_amd.Attention` with the narrow ResNet-26, or that `ResNet` itself.
+
+      invert(tiles, layer, steps=200, init_std=0.1, seed=0) -> InversionResult(u8, x, trace, terms)
+          one image per tile, each optimised from `init_std * randn` (a CPU generator seeded with `seed`; the toolkit's
+          `1e-1 * torch.randn`) so that `layer`'s output for it matches the output for the tile: SGD with momentum on
+          weight * ||f(x) - f(tile)||^2 / ||f(tile)||^2 plus the regulariser.  `tiles`: an fp32 stack or `U8Tiles`, left untouched.
+      distance(x, tiles, layer) -> fp32 [T]: that weighted distance, one truncated forward for x and one for the tiles.
+
+    lr_decay=(every, factor) multiplies lr by `factor` after the steps 0, every, 2 every, ... — the toolkit's schedule, its decay
+    after the very first step included.  The toolkit's own setting is lr=1e4, lr_decay=(40, 0.1) on a VGG; the default here, a
+    constant lr=100, is NOT the toolkit's: on this encoder's golden weights at 64x64 the same loop on the fp32 CPU oracle with
+    lr=1e4 and no decay is NaN within 12 steps, while lr=1e2 and lr=1e3 descend.  The target is the stage's output BEHIND its last
+    LeakyReLU, as for `FeatureVisualizer`.  project: "none", "clamp" or "u8" (`ops.pixel_step`'s).  One forward of `tiles` and one
+    `ops.stage_energy` per call; a step is six groups of launches (five without jitter) and nothing synchronises with the host;
+    all three compute modes and every tile size the encoder takes.  A call leaves the model as it found it: the `training` flag,
+    every `.grad`, the torch RNG states and a `FlatParams` bucket are not touched."""
+
+    def __init__(self, model, lr=100.0, momentum=0.9, lr_decay=None, weight=0.1, regularizer=PixelRegularizer(), project="none"):
+        self.net = narrow_encoder(model, "FeatureInverter", bare=True)
+        if project not in ops.PIXEL_PROJECTIONS:
+            raise ValueError(f"project must be one of {ops.PIXEL_PROJECTIONS}, got {project!r}")
+        self.lr, _wd, self.momentum = ops.momentum_scalars(lr, momentum, 0.0)
+        if lr_decay is not None:
+            try:
+                every, factor = lr_decay
+                every, factor = _count(every, "lr_decay's every"), float(factor)
+            except TypeError:
+                raise ValueError(f"lr_decay must be None or (every, factor), got {lr_decay!r}") from None
+            if not factor > 0.0 or factor == float("inf"):
+                raise ValueError(f"lr_decay's factor must be a positive number, got {factor}")
+            lr_decay = (every, factor)
+        self.lr_decay = lr_decay
+        self.weight = float(weight)
+        if not self.weight > 0.0 or self.weight == float("inf"):
+            raise ValueError(f"weight must be a positive number, got {weight!r}")
+        self.regularizer = check_regularizer(regularizer)
+        self.project = project
+
+    def _target(self, tiles, stage, dtype):
+        """The stage's output for the tiles, as the forward keeps it."""
+        _feats, saved = encoder_forward(self.net, device_tiles(self.net, tiles, "FeatureInverter"), dtype, upto=stage)
+        return saved["blocks"][-1][2]
+
+    def invert(self, tiles, layer, steps=200, init_std=0.1, seed=0):
+        stage = stage_of(layer)
+        check_tiles(None, tiles, None, WHAT)
+        steps, seed = _count(steps, "steps"), _count(seed, "seed", 0)
+        init_std = float(init_std)
+        if not init_std >= 0.0 or init_std == float("inf"):
+            raise ValueError(f"init_std must be a number >= 0, got {init_std}")
+        net, reg, c = self.net, self.regularizer, STAGE_WIDTHS[stage - 1]
+        dev = model_device(net, "FeatureInverter")
+        shifts = reg.shifts(steps)
+        gen = torch.Generator().manual_seed(seed)
+        x = (init_std * torch.randn(tuple(tiles.shape), generator=gen, dtype=torch.float32)).to(dev)
+        n = x.shape[0]
+        trace = torch.empty((steps, n), dtype=torch.float32, device=dev)
+        terms = torch.empty((steps, 2, n), dtype=torch.float32, device=dev)
+        u8 = torch.empty(x.shape, dtype=torch.uint8, device=dev)
+        buf = torch.zeros_like(x)
+        xs, out = (torch.empty_like(x), torch.empty_like(x)) if reg.jitter else (None, None)
+        lr = self.lr
+        with torch.no_grad(), compute_mode(net) as dtype:
+            target = self._target(tiles, stage, dtype)
+            energy = ops.stage_energy(target, c)
+            for k in range(steps):
+                _feats, saved = encoder_forward(net, reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
+                _loss, dz = ops.stage_match(saved["blocks"][-1][2], target, c, weight=self.weight, energy=energy, loss=trace[k])
+                g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
+                g = reg.gradient(x, g, out, shifts[k], terms[k])
+                ops.pixel_momentum_step(x, g, buf, lr=lr, momentum=self.momentum, project=self.project, u8_out=u8 if k == steps - 1 else None)
+                if self.lr_decay is not None and k % self.lr_decay[0] == 0:
+                    lr *= self.lr_decay[1]
+        return InversionResult(U8Tiles(u8), x, trace, terms)
+
+    def distance(self, x, tiles, layer):
+        stage = stage_of(layer)
+        check_tiles(None, tiles, None, WHAT)
+        check_tiles(None, x, None, WHAT)
+        if tuple(x.shape) != tuple(tiles.shape):
+            raise ValueError(f"x {tuple(x.shape)} and tiles {tuple(tiles.shape)} differ")
+        c = STAGE_WIDTHS[stage - 1]
+        with torch.no_grad(), compute_mode(self.net) as dtype:
+            target = self._target(tiles, stage, dtype)
+            return ops.stage_match(self._target(x, stage, dtype), target, c, weight=self.weight)[0]

@@ -17,6 +17,7 @@ import torch
 from . import ops
 from .attribution import LAYERS, bag_evaluate, bag_setup, channel_list, check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of  # noqa: F401
 from .encoder import STAGE_WIDTHS, encoder_forward, encoder_pixel_gradient
+from .feature_inv import check_regularizer
 from .preprocess import U8Tiles
 
 OPTIMIZERS = ops.PIXEL_RULES
@@ -77,10 +78,16 @@ class FeatureVisualizer:
     (the layer visualisation), "clamp" (to [-1, 1]) or "u8" (the class-specific method's round trip through bytes).  A step is
     four groups of launches with no host synchronisation between them; all three compute modes and every tile size the encoder
     takes.  A call leaves the model as it found it, as `TileSaliency` does: the `training` flag, every `.grad`, the torch RNG
-    states and a `FlatParams` bucket are not touched."""
+    states and a `FlatParams` bucket are not touched.
 
-    def __init__(self, model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none"):
+    regularizer (keyword only): None — every launch and every bit as without it — or a `mil_amd.PixelRegularizer`, which
+    `filters`, `dream` and `classes` add to the objective they MINIMISE (minus the filter's mean; the bag's loss): every step
+    then reads the network on the jittered copy of the image (`ops.pixel_shift`, with jitter) and sends the gradient through
+    `ops.pixel_reg` before the optimiser step, as `mil_amd.FeatureInverter` does."""
+
+    def __init__(self, model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none", *, regularizer=None):
         net = narrow_encoder(model, "FeatureVisualizer", bare=True)
+        self.regularizer = check_regularizer(regularizer, optional=True)
         if project not in ops.PIXEL_PROJECTIONS:
             raise ValueError(f"project must be one of {ops.PIXEL_PROJECTIONS}, got {project!r}")
         try:
@@ -112,6 +119,14 @@ class FeatureVisualizer:
     def _state(self, x):
         return (torch.zeros_like(x), torch.zeros_like(x)) if self.optimizer == "adam" else None
 
+    def _regularised(self, x, steps):
+        """(regulariser, its shift per step, the buffers of the jittered copy and of the gradient moved back) — Nones without one."""
+        reg = self.regularizer
+        if reg is None:
+            return None, None, None, None
+        xs, out = (torch.empty_like(x), torch.empty_like(x)) if reg.jitter else (None, None)
+        return reg, reg.shifts(steps), xs, out
+
     def _ascend(self, x, stage, chans, steps):
         """`steps` steps on x (fp32 on the device, optimised in place) for channel chans[t] of stage `stage`."""
         net = self.net
@@ -120,11 +135,14 @@ class FeatureVisualizer:
         trace = torch.empty((steps, x.shape[0]), dtype=torch.float32, device=x.device)
         u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
         state = self._state(x)
+        reg, shifts, xs, out = self._regularised(x, steps)
         with torch.no_grad(), compute_mode(net) as dtype:
             for k in range(steps):
-                _feats, saved = encoder_forward(net, x, dtype, upto=stage)
+                _feats, saved = encoder_forward(net, x if reg is None else reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
                 _j, dz = ops.stage_seed(saved["blocks"][-1][2], ch, c, objective=trace[k])
                 g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
+                if reg is not None:
+                    g = reg.gradient(x, g, out, shifts[k])
                 self._step(x, g, state, k, k == steps - 1, u8)
         return FeatureVisResult(U8Tiles(u8), x, trace)
 
@@ -168,11 +186,14 @@ class FeatureVisualizer:
         trace = torch.empty((steps, ntiles), dtype=torch.float32, device=x.device)
         u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
         state = self._state(x)
+        reg, shifts, xs, out = self._regularised(x, steps)
         with compute_mode(self.net) as dtype:
             for k in range(steps):
-                saved, dH, loss = bag_evaluate(model, setup, x, weights=weights)
+                saved, dH, loss = bag_evaluate(model, setup, x if reg is None else reg.jittered(x, xs, shifts[k]), weights=weights)
                 with torch.no_grad():
                     trace[k] = -loss
                     g, _sal = encoder_pixel_gradient(self.net, saved, dtype, dfeats=dH)
+                    if reg is not None:
+                        g = reg.gradient(x, g, out, shifts[k])
                     self._step(x, g, state, k, k == steps - 1, u8)
         return FeatureVisResult(U8Tiles(u8), x, trace)

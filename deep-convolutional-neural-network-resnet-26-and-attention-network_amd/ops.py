@@ -928,6 +928,178 @@ def pixel_step(x, g, state=None, *, rule="adam", lr=0.1, weight_decay=0.0, betas
     return x
 
 
+def _stage_map(t, c, name):
+    """(n, h, w, cp, dtype code) of a stage output [T,h,w,cpad(c)], checked."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{name} must be [T,h,w,cp], got {tuple(getattr(t, 'shape', ()))}")
+    n, h, w, cp = t.shape
+    if cp != cpad(c) or c < 1:
+        raise ValueError(f"{c} real channels go with {cpad(c)} stored ones, got {cp}")
+    if h < 1 or w < 1:
+        raise ValueError(f"maps of {h}x{w}")
+    code = L.dt_code(t.dtype)
+    _need(t, t.shape, t.dtype, name)
+    return n, h, w, cp, code
+
+
+def stage_energy(target, c, *, energy=None):
+    """E_t = the sum of target^2 over the c real channels of a stage output [T,h,w,cpad(c)] (bf16 or fp32) -> fp32 [T]: what
+    `stage_match` divides by (see mil_stage_energy); computed once per inversion."""
+    c = int(c)
+    n, h, w, cp, code = _stage_map(target, c, "target")
+    if energy is None:
+        energy = torch.empty((n,), dtype=torch.float32, device=target.device)
+    _need(energy, (n,), torch.float32, "energy")
+    ws = torch.empty((n, L.SEED_SLICES), dtype=torch.float32, device=target.device)
+    _launch("mil_stage_energy", ("stage_energy", n, h, w, cp), target.data_ptr(), energy.data_ptr(), ws.data_ptr(), n, h, w, cp, c, code,
+            L.stream_ptr())
+    return energy
+
+
+def stage_match(act, target, c, *, weight=0.1, energy=None, loss=None, dz=None, slope=LEAK):
+    """Loss and seed gradient of feature inversion at a stage output (see mil_stage_match): act and target [T,h,w,cpad(c)], two
+    outputs of one stage as the forward keeps them -> (loss fp32 [T] = weight * sum (act - target)^2 / E_t over the real
+    channels, dz like act = the gradient of loss_t with respect to the pre-activation map, ((2 weight / E_t) (act - target))
+    lrelu'(act), zero in the padding channels).  energy: `stage_energy(target, c)` (None: computed here).  `loss` / `dz`: the
+    caller's own output tensors (checked) — a row of a trace, for one.  E_t == 0 gives what IEEE division gives."""
+    c = int(c)
+    if not isinstance(target, torch.Tensor):
+        raise ValueError("target must be a tensor like act")
+    weight = float(weight)
+    if weight != weight:
+        raise ValueError("weight must be a number")
+    n, h, w, cp, code = _stage_map(act, c, "act")
+    _need(target, act.shape, act.dtype, "target")
+    if energy is None:
+        energy = stage_energy(target, c)
+    _need(energy, (n,), torch.float32, "energy")
+    if loss is None:
+        loss = torch.empty((n,), dtype=torch.float32, device=act.device)
+    _need(loss, (n,), torch.float32, "loss")
+    if dz is None:
+        dz = torch.empty_like(act)
+    _need(dz, act.shape, act.dtype, "dz")
+    ws = torch.empty((n, L.SEED_SLICES), dtype=torch.float32, device=act.device)
+    _launch("mil_stage_match", ("stage_match", n, h, w, cp), act.data_ptr(), target.data_ptr(), energy.data_ptr(), loss.data_ptr(),
+            dz.data_ptr(), ws.data_ptr(), n, h, w, cp, c, weight, slope, code, L.stream_ptr())
+    return loss, dz
+
+
+REG_ALPHAS = (2, 4, 6, 8)                         # mil_pixel_reg's alpha: the even powers it forms by repeated products
+
+
+def _pixel_stack(x, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{name} must be fp32 [T,3,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    if x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError(f"{name}: tiles of {x.shape[2]}x{x.shape[3]}")
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def _shift(shift, h, w):
+    """An integer (dy, dx) reduced mod (h, w)."""
+    try:
+        dy, dx = shift
+        if any(isinstance(v, bool) or int(v) != v for v in (dy, dx)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"shift must be two integers (dy, dx), got {shift!r}") from None
+    return int(dy) % h, int(dx) % w
+
+
+def _overlap(a, b):
+    """True when the two contiguous tensors share memory."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def reg_weights(alpha, alpha_weight, tv_weight):
+    """(alpha, alpha_weight, tv_weight) of `pixel_reg`, checked: an even power in 2..8 and two weights >= 0."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or alpha not in REG_ALPHAS:
+        raise ValueError(f"alpha must be one of {REG_ALPHAS}, got {alpha!r}")
+    aw, tw = float(alpha_weight), float(tv_weight)
+    if not (aw >= 0.0 and tw >= 0.0) or aw == float("inf") or tw == float("inf"):
+        raise ValueError(f"alpha_weight and tv_weight must be finite and >= 0, got {alpha_weight!r} and {tv_weight!r}")
+    return int(alpha), aw, tw
+
+
+def pixel_reg(x, g, out=None, *, alpha=6, alpha_weight=0.0, tv_weight=0.0, shift=(0, 0), terms=None):
+    """The pixel gradient g moved back through a jitter, plus the gradients of the two regularisers of x (see mil_pixel_reg):
+    out[t,c,i,j] = g[t,c,(i+dy) mod H,(j+dx) mod W] + alpha_weight alpha x^(alpha-1) + tv_weight dTV/dx[i,j] for x, g fp32
+    [T,3,H,W]; x is only read.  alpha: 2, 4, 6 or 8; TV: the toolkit's `total_variation_norm` with beta = 2.  shift: any two
+    integers (dy, dx), reduced mod (H, W).  out: None (a fresh tensor) or the caller's; it may be g itself when the reduced
+    shift is (0, 0) and may not overlap g or x otherwise.  terms: an fp32 [2,T] tensor that receives each tile's sum of x^alpha
+    and its total variation.  Returns out."""
+    alpha, aw, tw = reg_weights(alpha, alpha_weight, tv_weight)
+    n, h, w = _pixel_stack(x, "x")
+    dy, dx = _shift(shift, h, w)
+    if not isinstance(g, torch.Tensor):
+        raise ValueError("g must be a tensor like x")
+    _need(x, x.shape, torch.float32, "x")
+    _need(g, x.shape, torch.float32, "g")
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, x.shape, torch.float32, "out")
+    if out.data_ptr() == g.data_ptr() and n:
+        if dy or dx:
+            raise ValueError(f"out may be g itself only without a shift, got shift {(dy, dx)}")
+    elif _overlap(out, g):
+        raise ValueError("out overlaps g")
+    if _overlap(out, x):
+        raise ValueError("out overlaps x, which is only read")
+    _need(terms, (2, n), torch.float32, "terms")
+    ws = torch.empty((2, n, L.REG_SLICES), dtype=torch.float32, device=x.device) if terms is not None else None
+    _launch("mil_pixel_reg", ("pixel_reg", n, h, w, terms is not None), x.data_ptr(), g.data_ptr(), out.data_ptr(), L.ptr(terms), L.ptr(ws),
+            n, h, w, alpha, aw, tw, dy, dx, L.stream_ptr())
+    return out
+
+
+def pixel_shift(x, out, shift):
+    """The jittered copy out[t,c,i,j] = x[t,c,(i-dy) mod H,(j-dx) mod W] of an fp32 stack [T,3,H,W] (see mil_pixel_shift): a bit
+    copy, the inverse of `pixel_reg`'s index map.  out: None or the caller's tensor, not overlapping x.  Returns out."""
+    n, h, w = _pixel_stack(x, "x")
+    dy, dx = _shift(shift, h, w)
+    _need(x, x.shape, torch.float32, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, x.shape, torch.float32, "out")
+    if _overlap(out, x):
+        raise ValueError("out overlaps x")
+    _launch("mil_pixel_shift", ("pixel_shift", n, h, w), x.data_ptr(), out.data_ptr(), n, h, w, dy, dx, L.stream_ptr())
+    return out
+
+
+def momentum_scalars(lr, momentum, weight_decay):
+    """(lr, weight_decay, momentum) of `pixel_momentum_step`, checked."""
+    lr, mo, wd = float(lr), float(momentum), float(weight_decay)
+    if lr != lr or not wd >= 0.0 or not 0.0 <= mo < 1.0:
+        raise ValueError(f"lr must be a number, weight_decay >= 0 and momentum in [0, 1), got {lr}, {wd} and {mo}")
+    return lr, wd, mo
+
+
+def pixel_momentum_step(x, g, buf, *, lr, momentum=0.9, weight_decay=0.0, project="none", u8_out=None):
+    """One step of `torch.optim.SGD` with momentum (no dampening, no Nesterov) on the images x [T,3,H,W] fp32, in place and in
+    one pass (see mil_pixel_momentum_step): buf <- momentum buf + (g + weight_decay x); x <- x - lr buf.  buf: an fp32 tensor
+    like x, updated in place; zeros give torch's first step.  project, u8_out: `pixel_step`'s.  Returns x."""
+    if project not in PIXEL_PROJECTIONS:
+        raise ValueError(f"project must be one of {PIXEL_PROJECTIONS}, got {project!r}")
+    lr, wd, mo = momentum_scalars(lr, momentum, weight_decay)
+    _pixel_stack(x, "x")
+    if not isinstance(g, torch.Tensor) or not isinstance(buf, torch.Tensor):
+        raise ValueError("g and buf must be fp32 tensors like x")
+    _need(x, x.shape, torch.float32, "x")
+    _need(g, x.shape, torch.float32, "g")
+    _need(buf, x.shape, torch.float32, "buf")
+    _need(u8_out, x.shape, torch.uint8, "u8_out")
+    table = None
+    if project == "u8":
+        from .preprocess import U8Tiles
+        table = U8Tiles.decode_table(x.device)
+    _launch("mil_pixel_momentum_step", ("pixel_momentum_step", x.numel(), project, u8_out is not None), x.data_ptr(), g.data_ptr(),
+            buf.data_ptr(), L.ptr(u8_out), L.ptr(table), x.numel(), PIXEL_PROJECTIONS.index(project), lr, wd, mo, L.stream_ptr())
+    return x
+
+
 QUANTILE_GROUPS = ("tile", "bag")
 RENDER_MODES =("grayscale", "colour", "pos_neg")     # mil_attr_render's mode 0, 1, 2
 MapStats = collections.namedtuple("MapStats", "stats p group")

@@ -574,6 +574,68 @@ int mil_pixel_step(float* x, const float* g, float* m, float* v, unsigned char* 
                    int project, float lr, float weight_decay, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
                    float bc1, float sqrt_bc2, float eps, void* stream);
 
+/* Feature inversion (`inverted_representation.py` of the same toolkit): the seed of "make this stage's output equal that one".
+ *     act, target [n,h,w,cp]  two outputs of one stage as the forward keeps them, MIL_DT_BF16 or MIL_DT_F32, c real channels
+ *     energy [n]      E_t = sum over y,x and the c real channels of target^2, fp32: mil_stage_energy writes it, mil_stage_match reads it
+ *     loss [n]        weight * (D_t / E_t), D_t = sum over y,x and the real channels of (act - target)^2 — the toolkit's
+ *                     1e-1 * euclidian_loss; one quotient, one product
+ *     dz [n,h,w,cp]   the gradient of loss_t with respect to the PRE-activation map, the form the backward chain carries, for k < c:
+ *                     dz[t,y,x,k] = (((2 * weight) / E_t) * (act - target)) * (act > 0 ? 1 : slope)
+ *                     2 * weight is exact, the quotient is one fp32 division per tile, then one difference and two products in the order
+ *                     written, rounded to bf16 where dz is bf16; dz is exactly 0 in the padding channels c .. cp - 1
+ * Every square is one product of the fp32 value with itself.  Every element of energy / loss / dz is written.  The sums have a fixed
+ * order: each of MIL_SEED_SLICES workgroups per tile sums its pixels (per thread in work-item order and, within an 8-channel group,
+ * in channel order; a shuffle butterfly; the four waves in order) into ws [n * MIL_SEED_SLICES] fp32, a second small launch adds a
+ * tile's partial sums in slice order.  No atomics: two calls give the same bits.  E_t == 0 is not looked for: scale and loss are what
+ * IEEE division gives (inf or NaN), as in the toolkit, which divides by zero there too.  16-byte accesses where act, target and dz
+ * are on the 16-byte grid, element by element otherwise.  Null pointers, n < 0, h or w < 1, cp not a positive multiple of 8,
+ * c outside [1, cp], another dtype: MIL_ERR_ARG; n == 0: MIL_OK, no launch; h w of 2^24 or more or one map of 2^31 elements or
+ * more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+int mil_stage_energy(const void* target, float* energy, float* ws, int n, int h, int w, int cp, int c, int dtype, void* stream);
+int mil_stage_match(const void* act, const void* target, const float* energy, float* loss, void* dz, float* ws, int n, int h, int w, int cp,
+                    int c, float weight, float slope, int dtype, void* stream);
+
+/* The pixel regularisers of the same file and the way back through a jitter: x, g, out fp32 [n,3,H,W]; x is only read.
+ *     out[t,c,i,j] = g[t,c,(i + dy) mod H,(j + dx) mod W] + ca * x^(alpha - 1) + ct * S[i,j]
+ * with ca = alpha_weight * alpha (one fp32 product on the host), ct = 2 * tv_weight (exact) and, for v = x[t,c,i,j]:
+ *     x^(alpha - 1)  p = v, then alpha - 2 times p = p * v — the gradient of the toolkit's alpha_norm sum x^alpha
+ *     S[i,j]         half the gradient of total_variation_norm with beta = 2, sum over c, i < H - 1, j < W - 1 of
+ *                    (x[i,j] - x[i+1,j])^2 + (x[i,j] - x[i,j+1])^2.  S = 0, then in this order, each where the trimmed slices hold it:
+ *                      i < H - 1 and j < W - 1 (the cell's own term):   S = S + ((v - x[i+1,j]) + (v - x[i,j+1]))
+ *                      i >= 1    and j < W - 1 (the term of the cell above):       S = S + (v - x[i-1,j])
+ *                      j >= 1    and i < H - 1 (the term of the cell to the left): S = S + (v - x[i,j-1])
+ *                    the last row and the last column own no term; H == 1 or W == 1: S = 0 everywhere
+ *     out = g';  out = out + ca * p (only when alpha_weight != 0);  out = out + ct * S (only when tv_weight != 0)
+ * A weight of exactly 0 skips its sum: with both 0, out is the shifted g bit for bit.  alpha: an even integer in 2..8.  Any integer
+ * dy, dx: reduced mod H, W here.  out may BE g when the reduced shift is (0, 0); any other overlap of out with g or x is refused.
+ * terms (NULL: not made) [2,n] fp32: terms[0,t] = sum of p * v (x^alpha), terms[1,t] = the total variation, per cell
+ * (d1 * d1) + (d2 * d2) of the two differences above — whatever the weights are.  Their sums have a fixed order: each of
+ * MIL_REG_SLICES workgroups per tile sums its share of the tile's 3 H W elements (groups of four consecutive elements; per thread in
+ * group order, a shuffle butterfly, the four waves in order) into ws [2 * n * MIL_REG_SLICES] fp32, a second small launch adds the
+ * partial sums in slice order.  No atomics.  The neighbours are read from global memory (no LDS tile).  A whole group is one
+ * 16-byte access per tensor, on whatever 4-byte boundary it starts; where it lies in one row the rows above and below are one
+ * 16-byte load each (for g: where its sources do not wrap), element by element otherwise and in a last short group.
+ * Null x / g / out, terms without ws, alpha odd or outside 2..8, a NaN weight, the overlaps above, n < 0, H or W < 1: MIL_ERR_ARG;
+ * n == 0: MIL_OK, no launch; a tile of 2^31 - 4 elements or more: MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */
+#define MIL_REG_SLICES 16
+int mil_pixel_reg(const float* x, const float* g, float* out, float* terms, float* ws, int n, int H, int W, int alpha, float alpha_weight,
+                  float tv_weight, int dy, int dx, void* stream);
+
+/* The jittered copy out[t,c,i,j] = x[t,c,(i - dy) mod H,(j - dx) mod W]: a bit copy, the inverse of mil_pixel_reg's index map (the
+ * gradient of a function of `out` with respect to x is that gradient read at (i + dy, j + dx)).  Any integer dy, dx.  Null pointers,
+ * out overlapping x, n < 0, H or W < 1: MIL_ERR_ARG; n == 0: MIL_OK; sizes as for mil_pixel_reg. */
+int mil_pixel_shift(const float* x, float* out, int n, int H, int W, int dy, int dx, void* stream);
+
+/* torch.optim.SGD with momentum (no dampening, no Nesterov) on an image stack, in place, in one pass — mil_pixel_step's kernel with a
+ * third rule, behind an entry of its own (mil_pixel_step keeps refusing rule 2):
+ *     g' = g + wd * x;   buf <- momentum * buf + g';   x <- x - lr * buf
+ * each operation rounded once in the order written.  With buf all +0 the step is torch's first one, which sets buf = g': buf ends
+ * as g' and x as mil_pixel_step's rule 0 leaves it, bit for bit (momentum * 0 + g' is exact).  project, table,
+ * u8_out, the accesses and the size limit: mil_pixel_step's.  Null x / g / buf, project outside {0,1,2}, project 2 without table,
+ * lr, wd or momentum NaN: MIL_ERR_ARG; total == 0: MIL_OK, no launch. */
+int mil_pixel_momentum_step(float* x, const float* g, float* buf, unsigned char* u8_out, const float* table, size_t total, int project,
+                            float lr, float weight_decay, float momentum, void* stream);
+
 /* Order statistics of attribution maps: what `convert_to_grayscale` of the same toolkit's misc_functions.py takes with np.min and
  * np.percentile(., 99).  x [n,channels,H,W] fp32: channels == 3 ranks gray = (|g0| + |g1|) + |g2| (fp32, numpy's axis-0 order),
  * channels == 1 ranks the map itself.  A group is one tile (bag == 0; n groups of H W values) or the whole bag (bag == 1; one group
