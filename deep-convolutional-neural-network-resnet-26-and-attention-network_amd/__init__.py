@@ -20,11 +20,11 @@ from .path_attr import TileIntegratedGradients, TileSmoothGrad  # noqa: F401
 from .attr_render import AttributionRenderer  # noqa: F401
 from .attr_mosaic import AttributionMosaic  # noqa: F401
 from .feature_vis import FeatureVisResult, FeatureVisualizer  # noqa: F401
-from .feature_inv import FeatureInverter, InversionResult, PixelRegularizer  # noqa: F401
+from .feature_inv import FeatureInverter, InversionResult, PixelRegularizer, gaussian_blur  # noqa: F401
 from .guided import TileGuidedBackprop, TileGuidedGradCam  # noqa: F401
 
 __all__ = ["alt_resnet", "Attention", "ResNet", "BasicResBlock", "ContextLayer", "CrossEntropyWithProbs", "TileParallel",
            "FlatParams", "FlatAdam", "shard_bags", "gather_features", "BagTrainer", "set_stage", "stage_for_epoch", "write_attention_map", "write_map", "visualize_terms", "save_checkpoint", "load_checkpoint", "TilePreprocessor", "S2dTiles", "U8Tiles", "RoiSelector", "SlideBag", "AttentionMapRenderer", "ColorJitter", "build_library", "lib", "MilLibraryError", "LIB_PATH", "BF16X3", "invalidate_packed_weights",
            "ActivationSummary", "parameter_stats", "tensor_stats", "TileSaliency", "TileGradCam", "TileIntegratedGradients", "TileSmoothGrad", "AttributionRenderer",
-           "AttributionMosaic", "FeatureVisualizer", "FeatureVisResult", "FeatureInverter", "InversionResult", "PixelRegularizer",
+           "AttributionMosaic", "FeatureVisualizer", "FeatureVisResult", "FeatureInverter", "InversionResult", "PixelRegularizer", "gaussian_blur",
            "TileGuidedBackprop", "TileGuidedGradCam"]

@@ -26,6 +26,7 @@ FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pill
 ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per tile in mil_attr_finish's workspace
 SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per tile in mil_stage_seed's workspace
 REG_SLICES = 16                              # MIL_REG_SLICES: partial sums per tile and norm in mil_pixel_reg's workspace
+BLUR_MAX_RADIUS = 16                         # MIL_BLUR_MAX_RADIUS: the largest radius mil_pixel_blur takes
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -112,6 +113,7 @@ _SIGS = {
     "mil_stage_match": ([_vp] * 6 + [_i] * 5 + [_f, _f, _i, _vp], _i),
     "mil_pixel_reg": ([_vp] * 5 + [_i] * 4 + [_f, _f, _i, _i, _vp], _i),
     "mil_pixel_shift": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mil_pixel_blur": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_pixel_momentum_step": ([_vp] * 5 + [_sz, _i, _f, _f, _f, _vp], _i),
     "mil_map_quantile_workspace":([_c.POINTER(_sz), _i, _i], _i),
     "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),

@@ -9,6 +9,12 @@ distance and writes the seed of the backward pass (`ops.stage_match`), the data-
 (`encoder_pixel_gradient`), one launch that moves the gradient back through the jitter and adds the regularisers' gradients
 (`ops.pixel_reg`) and one that takes the momentum step, projects and encodes (`ops.pixel_momentum_step`) — nothing synchronises
 with the host.  `PixelRegularizer` also serves `FeatureVisualizer(regularizer=)`.  DESIGN.md section 3.46.
+
+The regulariser that removes high-frequency patterns is a Gaussian blur, one launch of `ops.pixel_blur` (a separable filter with a
+bit contract of its own, both passes in one kernel): of the image, every `blur_every` steps at the start of the step, or of the
+gradient, in every step between `ops.pixel_reg` and the optimiser step.  The filter is never in place: the loops move between two
+stacks allocated before they start, the jittered copy's where there is one.  `gaussian_blur` is the same launch for stacks and
+attribution maps.  DESIGN.md section 3.47.
 """
 from collections import namedtuple
 
@@ -33,23 +39,52 @@ def _count(v, name, least=1):
     return int(v)
 
 
+def _sigma(v, name):
+    """0.0 (off) or a sigma `ops.gauss_taps` takes."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v < 0:
+        raise ValueError(f"{name} must be a number >= 0 (0: off), got {v!r}")
+    if v:
+        try:
+            ops.gauss_taps(v)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+    return float(v)
+
+
 class PixelRegularizer:
-    """`PixelRegularizer(alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0)` — what is added to an objective that is
-    minimised over pixels: alpha_weight * sum x^alpha + tv_weight * TV(x), TV the toolkit's `total_variation_norm` with beta = 2;
+    """`PixelRegularizer(alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0, *, blur_sigma=0.0, blur_every=4,
+    grad_blur_sigma=0.0, blur_edge="reflect")` — what is added to an objective that is minimised over pixels:
+    alpha_weight * sum x^alpha + tv_weight * TV(x), TV the toolkit's `total_variation_norm` with beta = 2;
     the defaults are the toolkit's (inverted_representation.py:74-84).  alpha: 2, 4, 6 or 8.  jitter: the largest shift in pixels
     of the cyclic jitter — every step evaluates the network on the image shifted by (dy, dx), each drawn from [-jitter, jitter],
     and the gradient is shifted back; 0: none.  `shifts(steps)` draws all of them at once from a CPU `torch.Generator` seeded
-    with `seed`: the global generators are not touched and the shifts are the same on every machine.  A value object: it holds
-    no tensor."""
+    with `seed`: the global generators are not touched and the shifts are the same on every machine.
 
-    def __init__(self, alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0):
+    The two Gaussian blurs (`ops.pixel_blur`; sigma as `ops.gauss_taps` takes it, 0: off; blur_edge: "reflect", "replicate" or
+    "wrap", the cyclic jitter's own rule):
+      blur_sigma       image blur (Yosinski et al. 2015): at the START of step k, for k > 0 and k % blur_every == 0, the image is
+                       replaced by its blurred copy, before the jittered copy and the forward.  A blur therefore never follows
+                       the last optimiser step: the `u8` and `x` of a result stay the ones the step kernel encoded, and the trace
+                       (and terms) of step k describe the blurred image, the one the step started from.  The blurred image is NOT
+                       projected again: with project="u8" it is off the byte grid until the next optimiser step projects it.
+      grad_blur_sigma  gradient blur: the gradient `gradient(...)` returns is blurred before the optimiser step, in every step.
+    With both 0, the default, there is no new launch, no new allocation and every bit is as before.  The filter is never in
+    place, so the loops move between two stacks (`blurred` returns them swapped) instead of copying back.  A value object: it
+    holds no tensor."""
+
+    def __init__(self, alpha=6, alpha_weight=1e-7, tv_weight=1e-8, jitter=0, seed=0, *, blur_sigma=0.0, blur_every=4, grad_blur_sigma=0.0,
+                 blur_edge="reflect"):
         self.alpha, self.alpha_weight, self.tv_weight = ops.reg_weights(alpha, alpha_weight, tv_weight)
         self.jitter = _count(jitter, "jitter", 0)
         self.seed = _count(seed, "seed", 0)
+        self.blur_sigma, self.grad_blur_sigma = _sigma(blur_sigma, "blur_sigma"), _sigma(grad_blur_sigma, "grad_blur_sigma")
+        self.blur_every = _count(blur_every, "blur_every")
+        self.blur_edge = ops.blur_edge(blur_edge)
 
     def __repr__(self):
         return (f"PixelRegularizer(alpha={self.alpha}, alpha_weight={self.alpha_weight}, tv_weight={self.tv_weight}, "
-                f"jitter={self.jitter}, seed={self.seed})")
+                f"jitter={self.jitter}, seed={self.seed}, blur_sigma={self.blur_sigma}, blur_every={self.blur_every}, "
+                f"grad_blur_sigma={self.grad_blur_sigma}, blur_edge={self.blur_edge!r})")
 
     def shifts(self, steps):
         """[(dy, dx)] * steps: zeros without jitter, else `torch.randint(-jitter, jitter + 1, (steps, 2))` of a generator of
@@ -59,15 +94,48 @@ class PixelRegularizer:
         gen = torch.Generator().manual_seed(self.seed)
         return [tuple(s) for s in torch.randint(-self.jitter, self.jitter + 1, (steps, 2), generator=gen).tolist()]
 
+    def scratch(self, x):
+        """(xs, out), the stacks a loop over x allocates before it starts, None where no option needs one.  xs holds the jittered
+        copy during the forward and the backward walk and is dead otherwise: the image blur (at the start of a step) and the
+        gradient blur (behind `ops.pixel_reg`) write into it, so with jitter the blurs cost no stack of their own and without
+        it one.  out: the gradient moved back through the jitter.  A blur the images are too small for under "reflect" is refused
+        here, before the first step, not at the step that would launch it."""
+        for name in ("blur_sigma", "grad_blur_sigma"):
+            sigma = getattr(self, name)
+            if sigma and self.blur_edge == "reflect" and ops.gauss_taps(sigma)[0] > min(x.shape[-2:]) - 1:
+                raise ValueError(f"{name}={sigma} with blur_edge='reflect' needs images of more than {ops.gauss_taps(sigma)[0]} pixels a side, "
+                                 f"got {x.shape[-2]}x{x.shape[-1]}")
+        xs =torch.empty_like(x) if self.jitter or self.blur_sigma or self.grad_blur_sigma else None
+        return xs, torch.empty_like(x) if self.jitter else None
+
+    def blurred(self, x, xs, k):
+        """Step 0 of a regularised step k: (x, xs) — swapped, xs having received the blurred x, when step k starts with an image
+        blur; as given otherwise."""
+        if not self.blur_sigma or k == 0 or k % self.blur_every:
+            return x, xs
+        return ops.pixel_blur(x, xs, sigma=self.blur_sigma, edge=self.blur_edge), x
+
     def jittered(self, x, xs, shift):
         """Step 1 of a regularised step: the tensor the network reads — x itself without jitter, else its shifted copy in xs."""
         return ops.pixel_shift(x, xs, shift) if self.jitter else x
 
-    def gradient(self, x, g, out, shift, terms=None):
+    def gradient(self, x, g, out, shift, terms=None, xs=None):
         """Step 5: g, the gradient with respect to `jittered(x)`, as the gradient of the regularised objective with respect to x.
-        Without jitter it is written over g; with it, into `out`."""
-        return ops.pixel_reg(x, g, out if self.jitter else g, alpha=self.alpha, alpha_weight=self.alpha_weight, tv_weight=self.tv_weight,
-                             shift=shift, terms=terms)
+        Without jitter it is written over g; with it, into `out`.  With a gradient blur its blurred copy, written into xs."""
+        g = ops.pixel_reg(x, g, out if self.jitter else g, alpha=self.alpha, alpha_weight=self.alpha_weight, tv_weight=self.tv_weight,
+                          shift=shift, terms=terms)
+        return ops.pixel_blur(g, xs, sigma=self.grad_blur_sigma, edge=self.blur_edge) if self.grad_blur_sigma else g
+
+
+def gaussian_blur(x, sigma, edge="reflect", out=None):
+    """The Gaussian blur of every plane of a stack [T,3,H,W] or of maps [T,H,W] (fp32, contiguous, on the device) in one launch:
+    `scipy.ndimage.gaussian_filter(plane, sigma, truncate=4.0)` with the mode edge stands for ("reflect": scipy's "mirror",
+    torch's `reflect` padding, radius <= min(H, W) - 1; "replicate": "nearest"; "wrap"), in fp32 with the fixed operation order
+    of `ops.pixel_blur`.  sigma: about 0.125 <= sigma < 4.125 (`ops.gauss_taps`).  out: None or the caller's tensor, not
+    overlapping x.  For example `renderer.grayscale(mil_amd.gaussian_blur(sal.maps(tiles, y), 2.0))`."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 3):
+        raise ValueError(f"x must be an fp32 stack [T,3,H,W] or maps [T,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    return ops.pixel_blur(x, out, sigma=sigma, edge=edge)
 
 
 def check_regularizer(regularizer, optional=False):
@@ -140,16 +208,17 @@ class FeatureInverter:
         terms = torch.empty((steps, 2, n), dtype=torch.float32, device=dev)
         u8 = torch.empty(x.shape, dtype=torch.uint8, device=dev)
         buf = torch.zeros_like(x)
-        xs, out = (torch.empty_like(x), torch.empty_like(x)) if reg.jitter else (None, None)
+        xs, out = reg.scratch(x)
         lr = self.lr
         with torch.no_grad(), compute_mode(net) as dtype:
             target = self._target(tiles, stage, dtype)
             energy = ops.stage_energy(target, c)
             for k in range(steps):
+                x, xs = reg.blurred(x, xs, k)
                 _feats, saved = encoder_forward(net, reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
                 _loss, dz = ops.stage_match(saved["blocks"][-1][2], target, c, weight=self.weight, energy=energy, loss=trace[k])
                 g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
-                g = reg.gradient(x, g, out, shifts[k], terms[k])
+                g = reg.gradient(x, g, out, shifts[k], terms[k], xs)
                 ops.pixel_momentum_step(x, g, buf, lr=lr, momentum=self.momentum, project=self.project, u8_out=u8 if k == steps - 1 else None)
                 if self.lr_decay is not None and k % self.lr_decay[0] == 0:
                     lr *= self.lr_decay[1]

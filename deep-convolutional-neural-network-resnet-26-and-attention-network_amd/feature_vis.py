@@ -83,7 +83,9 @@ class FeatureVisualizer:
     regularizer (keyword only): None — every launch and every bit as without it — or a `mil_amd.PixelRegularizer`, which
     `filters`, `dream` and `classes` add to the objective they MINIMISE (minus the filter's mean; the bag's loss): every step
     then reads the network on the jittered copy of the image (`ops.pixel_shift`, with jitter) and sends the gradient through
-    `ops.pixel_reg` before the optimiser step, as `mil_amd.FeatureInverter` does."""
+    `ops.pixel_reg` before the optimiser step, as `mil_amd.FeatureInverter` does.  Its `blur_sigma` / `grad_blur_sigma` add one
+    `ops.pixel_blur` launch at the start of every `blur_every`-th step (the image) or before every optimiser step (the gradient);
+    the image then moves between two stacks, so the `x` of a result need not be the tensor the loop started from."""
 
     def __init__(self, model, optimizer="adam", lr=0.1, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, project="none", *, regularizer=None):
         net = narrow_encoder(model, "FeatureVisualizer", bare=True)
@@ -124,7 +126,7 @@ class FeatureVisualizer:
         reg = self.regularizer
         if reg is None:
             return None, None, None, None
-        xs, out = (torch.empty_like(x), torch.empty_like(x)) if reg.jitter else (None, None)
+        xs, out = reg.scratch(x)
         return reg, reg.shifts(steps), xs, out
 
     def _ascend(self, x, stage, chans, steps):
@@ -138,11 +140,13 @@ class FeatureVisualizer:
         reg, shifts, xs, out = self._regularised(x, steps)
         with torch.no_grad(), compute_mode(net) as dtype:
             for k in range(steps):
+                if reg is not None:
+                    x, xs = reg.blurred(x, xs, k)
                 _feats, saved = encoder_forward(net, x if reg is None else reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
                 _j, dz = ops.stage_seed(saved["blocks"][-1][2], ch, c, objective=trace[k])
                 g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
                 if reg is not None:
-                    g = reg.gradient(x, g, out, shifts[k])
+                    g = reg.gradient(x, g, out, shifts[k], xs=xs)
                 self._step(x, g, state, k, k == steps - 1, u8)
         return FeatureVisResult(U8Tiles(u8), x, trace)
 
@@ -189,11 +193,13 @@ class FeatureVisualizer:
         reg, shifts, xs, out = self._regularised(x, steps)
         with compute_mode(self.net) as dtype:
             for k in range(steps):
+                if reg is not None:
+                    x, xs = reg.blurred(x, xs, k)
                 saved, dH, loss = bag_evaluate(model, setup, x if reg is None else reg.jittered(x, xs, shifts[k]), weights=weights)
                 with torch.no_grad():
                     trace[k] = -loss
                     g, _sal = encoder_pixel_gradient(self.net, saved, dtype, dfeats=dH)
                     if reg is not None:
-                        g = reg.gradient(x, g, out, shifts[k])
+                        g = reg.gradient(x, g, out, shifts[k], xs=xs)
                     self._step(x, g, state, k, k == steps - 1, u8)
         return FeatureVisResult(U8Tiles(u8), x, trace)

@@ -1069,6 +1069,92 @@ def pixel_shift(x, out, shift):
     return out
 
 
+BLUR_EDGES = ("reflect", "replicate", "wrap")     # mil_pixel_blur's edge 0, 1, 2
+_blur_taps = {}                                   # (sigma, device) -> the fp32 taps on the device
+
+
+def gauss_taps(sigma):
+    """(radius, fp64 numpy [radius + 1]): the centre and one half of `scipy.ndimage`'s Gaussian kernel at truncate=4.0 —
+    radius = int(4 sigma + 0.5), exp(-0.5 / sigma^2 * k^2) over k = -radius .. radius in fp64, divided by their sum.  sigma must
+    give 1 <= radius <= 16 (about 0.125 <= sigma < 4.125): no tap is then zero or denormal as fp32."""
+    import numpy as np
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise ValueError(f"sigma must be a number, got {sigma!r}")
+    sigma = float(sigma)
+    radius = int(4.0 * sigma + 0.5) if sigma == sigma and 0.0 < sigma < float("inf") else 0
+    if not 1 <= radius <= L.BLUR_MAX_RADIUS:
+        raise ValueError(f"sigma must give a radius int(4 sigma + 0.5) in 1..{L.BLUR_MAX_RADIUS} (about 0.125 <= sigma < 4.125), got {sigma!r}")
+    k = np.arange(-radius, radius + 1)
+    p = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    p = p / p.sum()
+    return radius, p[radius:].copy()
+
+
+def gauss_taps_device(sigma, device):
+    """(radius, the taps of `gauss_taps(sigma)` rounded to fp32 on `device`): uploaded once and cached per (sigma, device)."""
+    key = (float(sigma), torch.device(device))
+    hit = _blur_taps.get(key)
+    if hit is None:
+        radius, taps = gauss_taps(sigma)
+        hit = _blur_taps[key] = (radius, torch.from_numpy(taps).to(torch.float32).to(key[1]))
+    return hit
+
+
+def blur_edge(edge):
+    if edge not in BLUR_EDGES:
+        raise ValueError(f"edge must be one of {BLUR_EDGES}, got {edge!r}")
+    return edge
+
+
+def pixel_blur(x, out=None, *, sigma=None, taps=None, edge="reflect"):
+    """A separable symmetric filter along W, then along H, of every plane of x (see mil_pixel_blur): fp32, contiguous, at least
+    2 dimensions, the leading ones being the planes — a stack [T,3,H,W], a map [T,H,W], one plane [H,W].  Exactly one of
+    `sigma` (the Gaussian of `gauss_taps`) and `taps` (w[0..radius], radius + 1 finite numbers, rounded to fp32: the centre tap
+    and one half of any symmetric filter) is given.  edge: "reflect" (the edge sample not repeated; radius <= min(H, W) - 1),
+    "replicate" or "wrap".  out: None (a fresh tensor) or the caller's, which may not overlap x: the filter is never in place.
+    Returns out."""
+    blur_edge(edge)
+    if (sigma is None) == (taps is None):
+        raise ValueError("exactly one of sigma and taps must be given")
+    if not isinstance(x, torch.Tensor) or x.dim() < 2:
+        raise ValueError(f"x must be an fp32 tensor [..., H, W], got {tuple(getattr(x, 'shape', ()))}")
+    h, w = x.shape[-2], x.shape[-1]
+    if h < 1 or w < 1:
+        raise ValueError(f"x: planes of {h}x{w}")
+    # what can be decided without a device comes first
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"x must be a contiguous fp32 tensor, got {x.dtype}, strides {tuple(x.stride())}")
+    if sigma is not None:
+        radius, vals = gauss_taps(sigma)
+    else:
+        try:
+            vals = [float(v) for v in taps]
+        except (TypeError, ValueError):
+            raise ValueError(f"taps must be a sequence of numbers w[0..radius], got {taps!r}") from None
+        radius = len(vals) - 1
+        if not 1 <= radius <= L.BLUR_MAX_RADIUS or any(v != v or v in (float("inf"), float("-inf")) for v in vals):
+            raise ValueError(f"taps must be radius + 1 finite numbers with 1 <= radius <= {L.BLUR_MAX_RADIUS}, got {taps!r}")
+    if edge == "reflect" and radius > min(h, w) - 1:
+        raise ValueError(f"edge 'reflect' needs radius <= min(H, W) - 1, got radius {radius} for planes of {h}x{w}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous fp32 tensor like x {tuple(x.shape)}, got {tuple(getattr(out, 'shape', ()))} "
+                             f"{getattr(out, 'dtype', None)}")
+        if _overlap(out, x):
+            raise ValueError("out overlaps x: the filter is never in place")
+    _need(x, x.shape, torch.float32, "x")
+    _need(out, x.shape, torch.float32, "out")
+    if out is None:
+        out = torch.empty_like(x)
+    planes = x.numel() // (h * w)
+    if planes == 0:
+        return out
+    tdev = gauss_taps_device(sigma, x.device)[1] if sigma is not None else torch.tensor(vals, dtype=torch.float64).to(torch.float32).to(x.device)
+    _launch("mil_pixel_blur", ("pixel_blur", planes, h, w, radius, edge), x.data_ptr(), out.data_ptr(), tdev.data_ptr(), planes, h, w, radius,
+            BLUR_EDGES.index(edge), L.stream_ptr())
+    return out
+
+
 def momentum_scalars(lr, momentum, weight_decay):
     """(lr, weight_decay, momentum) of `pixel_momentum_step`, checked."""
     lr, mo, wd = float(lr), float(momentum), float(weight_decay)

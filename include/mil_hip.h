@@ -626,6 +626,30 @@ int mil_pixel_reg(const float* x, const float* g, float* out, float* terms, floa
  * out overlapping x, n < 0, H or W < 1: MIL_ERR_ARG; n == 0: MIL_OK; sizes as for mil_pixel_reg. */
 int mil_pixel_shift(const float* x, float* out, int n, int H, int W, int dy, int dx, void* stream);
 
+/* A separable symmetric filter over a stack of planes, both passes in one launch — the Gaussian blur of the pixel optimisers (of the
+ * image, of the gradient) and of attribution maps.  x, out: fp32 [planes,H,W], contiguous; planes any count >= 0 (a stack [T,3,H,W] is
+ * 3 T planes, a map [T,H,W] is T).  taps: a DEVICE float[radius + 1] = w[0..radius], the centre tap and one half of the filter; the
+ * arithmetic is defined for any taps, the Gaussian is the host's choice of them.  With v[d] the sample d places from the output's
+ * own along the axis of a pass:
+ *     acc = w[0] * v[0];   for k = 1 .. radius, in this order:   acc = acc + w[k] * (v[-k] + v[+k])
+ * — the sum of the pair, then the product, then the accumulation, each a single correctly rounded fp32 operation, none fused.  The
+ * horizontal pass (along W) runs first and its results are rounded to fp32; the vertical pass (along H) runs over those rounded
+ * values.  The same expressions on numpy fp32 arrays give the same bits.  A sample outside the line of length n (W, then H) is the
+ * sample at the source index the edge rule gives, per axis:
+ *     edge 0  reflect    -i for i < 0, 2 (n - 1) - i for i > n - 1: the edge sample is not repeated (torch's `reflect` padding,
+ *                        scipy's "mirror"); needs radius <= n - 1 on both axes
+ *     edge 1  replicate  i clamped to [0, n - 1] (scipy's "nearest"); any radius
+ *     edge 2  wrap       i mod n (scipy's "wrap", the cyclic jitter's rule); any radius, radius >= n too
+ * One workgroup per 64 x 64 output tile of a plane: the tile and its halo staged in LDS through the index map, the horizontal pass
+ * into a second LDS array, one barrier, the vertical pass to global memory; no atomics; 16-byte global accesses where four
+ * consecutive elements of a row lie inside the plane on the 16-byte grid, element by element otherwise.
+ * Null x / out / taps, out overlapping x (the filter is never in place), planes < 0, H or W < 1, radius outside
+ * 1..MIL_BLUR_MAX_RADIUS, edge outside {0,1,2}, edge 0 with radius > min(H, W) - 1: MIL_ERR_ARG; planes == 0: MIL_OK, no launch; a plane
+ * beyond what mil_pixel_shift takes as a third of a tile (3 H W >= 2^31 - 4), or more than 2^31 - 1 workgroups: MIL_ERR_UNSUPPORTED —
+ * all decided on the host before any GPU call. */
+#define MIL_BLUR_MAX_RADIUS 16
+int mil_pixel_blur(const float* x, float* out, const float* taps, int planes, int H, int W, int radius, int edge, void* stream);
+
 /* torch.optim.SGD with momentum (no dampening, no Nesterov) on an image stack, in place, in one pass — mil_pixel_step's kernel with a
  * third rule, behind an entry of its own (mil_pixel_step keeps refusing rule 2):
  *     g' = g + wd * x;   buf <- momentum * buf + g';   x <- x - lr * buf

@@ -8,7 +8,11 @@
         regulariser gradient and the two norms as tensor expressions, the momentum step as `mul_` / `add_`;
   (iii) each of the new launches alone — `pixel_shift`, `pixel_reg` (with and without terms, aliased and not),
         `pixel_momentum_step`, `stage_match` — with its algorithmic bytes (every tensor read or written once) at the median;
-  (iv)  beside them, the `filters("layer4")` step of `tools/time_feature_vis.py` for 80 tiles on the same box.
+  (iv)  beside them, the `filters("layer4")` step of `tools/time_feature_vis.py` for 80 tiles on the same box;
+  (v)   the Gaussian blur: `pixel_blur` alone on the 3 `--tiles` planes at sigma 1.0 and 4.0 for each edge
+        rule, beside the torch form it replaces (`F.pad` plus two grouped `F.conv2d`) and `pixel_shift`, the pure copy through a
+        comparable gather; and the `invert` and `filters("layer4")` steps without jitter with the image blur (sigma 1 every 2
+        steps), with the gradient blur (sigma 1 every step), with both and with neither.
 
 `--warmup` untimed and `--reps` timed repetitions, medians.  Prints one JSON line.  A report, not a test."""
 import argparse
@@ -66,6 +70,17 @@ def torch_reg(x, g, shift, terms):
     return g
 
 
+TORCH_PAD = {"reflect": "reflect", "replicate": "replicate", "wrap": "circular"}
+
+
+def torch_blur(x, full, edge):
+    """The torch form of `ops.pixel_blur`: the padded stack, then one grouped convolution along W and one along H."""
+    c, r = x.shape[1], (full.numel() - 1) // 2
+    p = torch.nn.functional.pad(x, (r, r, r, r), mode=TORCH_PAD[edge])
+    p = torch.nn.functional.conv2d(p, full.view(1, 1, 1, -1).expand(c, 1, 1, -1), groups=c)
+    return torch.nn.functional.conv2d(p, full.view(1, 1, -1, 1).expand(c, 1, -1, 1), groups=c)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -102,6 +117,17 @@ def main():
     bt = torch.zeros_like(x0)
     k["torch_momentum"] = run(lambda: x.add_(bt.mul_(MO).add_(g0), alpha=-1e-3), 40 * nel)
     res["launches_alone"] = k
+    # (v) the blur alone: 8 bytes per element of compulsory traffic
+    b = {"planes": 3 * n, "pixel_shift": k["pixel_shift"]}
+    for sigma in (1.0, 4.0):
+        radius, half = ops.gauss_taps(sigma)
+        full = torch.tensor(list(half[:0:-1]) + list(half), dtype=torch.float32, device="cuda")
+        for edge in ops.BLUR_EDGES:
+            b[f"pixel_blur_sigma{sigma:g}_{edge}"] = run(lambda: ops.pixel_blur(x, xs, sigma=sigma, edge=edge), 8 * nel)
+            b[f"torch_pad_conv2d_sigma{sigma:g}_{edge}"] = run(lambda: torch_blur(x, full, edge), 8 * nel)
+            b[f"max_abs_difference_sigma{sigma:g}_{edge}"] = float((ops.pixel_blur(x, xs, sigma=sigma, edge=edge) - torch_blur(x, full, edge)).abs().max())
+        b[f"radius_sigma{sigma:g}"] = radius
+    res["blur_alone"] = b
     del x, buf, out, xs, ga, gt, bt
     for name, mode in (("bf16", torch.bfloat16), ("bf16x3", L.BF16X3)):
         st = L.storage_dtype(mode)
@@ -161,6 +187,42 @@ def main():
                     g = encoder.encoder_pixel_gradient(net, saved, st, dz=dz, stage=4)[0]
                     ops.pixel_step(xf, g, state, rule="adam", lr=0.1, weight_decay=1e-6, step=3)
             r["filters_80_tiles"] = run(filters_loop, per=a.steps)
+            # (v) the steps with the blurs, without jitter: two stacks that swap at an image blur, the spare one takes the blurred gradient
+            def blur_steps(first, second, step, image, grad):
+                cur = [first, second]
+                for i in range(a.steps):
+                    if image and i > 0 and i % 2 == 0:
+                        ops.pixel_blur(cur[0], cur[1], sigma=1.0)
+                        cur.reverse()
+                    g = step(cur[0], i)
+                    if grad:
+                        g = ops.pixel_blur(g, cur[1], sigma=1.0)
+                    yield cur[0], g
+
+            def invert_step(xc, i):
+                g = grad(xc, i)
+                return ops.pixel_reg(xc, g, g, alpha=ALPHA, alpha_weight=AW, tv_weight=TW, terms=terms[i])
+
+            def filters_step(xc, i):
+                saved = encoder.encoder_forward(net, xc, st, upto=4)[1]
+                dz = ops.stage_seed(saved["blocks"][-1][2], ch, c)[1]
+                return encoder.encoder_pixel_gradient(net, saved, st, dz=dz, stage=4)[0]
+
+            def invert_blur(image, grad_):
+                for xc, g in blur_steps(x, xs, invert_step, image, grad_):
+                    ops.pixel_momentum_step(xc, g, buf, lr=LR, momentum=MO)
+
+            xf2 = torch.empty_like(xf)
+
+            def filters_blur(image, grad_):
+                for xc, g in blur_steps(xf, xf2, filters_step, image, grad_):
+                    ops.pixel_step(xc, g, state, rule="adam", lr=0.1, weight_decay=1e-6, step=3)
+
+            for label, image, grad_ in (("neither", False, False), ("image_blur", True, False), ("gradient_blur", False, True), ("both", True, True)):
+                x.copy_(x0)
+                buf.zero_()
+                r["invert_step_" + label] = run(lambda: invert_blur(image, grad_), per=a.steps)
+                r["filters_80_tiles_step_" + label] = run(lambda: filters_blur(image, grad_), per=a.steps)
         res[name] = r
         del net, x, buf, out, xs
     print(json.dumps(res))
