@@ -262,4 +262,11 @@ __host__ inline void mil_device_done(std::atomic<unsigned long long>& done) {
     if (hipGetDevice(&dev) == hipSuccess) done.fetch_or(1ull << (dev & 63), std::memory_order_release);
 }
 
+// Host-side pointer tests of the entry points: on the 16-byte grid; two runs of `bytes` bytes that share memory.
+__host__ inline bool mil_on16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
+__host__ inline bool mil_overlap(const void* a, const void* b, unsigned long long bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + bytes && b0 < a0 + bytes;
+}
+
 #define MIL_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return MIL_ERR_LAUNCH; } while (0)

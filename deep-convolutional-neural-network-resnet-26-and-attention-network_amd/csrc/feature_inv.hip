@@ -5,8 +5,8 @@
 //   stage_energy_kernel<T>    E_t = sum of target^2 over the real channels of a stage output (partial sums)
 //   stage_match_kernel<T>     dz, the gradient of weight * sum (act - target)^2 / E_t with respect to the pre-activation map, and the
 //                             partial sums of the distance
-//   slice_sum_kernel          a row's partial sums added in slice order: energy [T], terms [2,T]
-//   stage_match_sum_kernel    the same, then weight * (D / E): loss [T]
+//   slice_sum_kernel<..>      (slice_sum.cuh) a row's partial sums added in slice order: energy [T], terms [2,T]; for loss [T]
+//                             followed by weight * (D / E)
 //   pixel_reg_kernel<TERMS>   the pixel gradient moved back through the jitter plus the gradients of the alpha norm and of the total
 //                             variation of x; with TERMS the partial sums of the two norms themselves
 //   pixel_shift_kernel        the jittered copy of x: a cyclic shift of every plane, bit for bit
@@ -15,13 +15,9 @@
 // correctly rounded fp32 operation in the order include/mil_hip.h writes down; no atomics, every sum in a fixed order; streaming
 // kernels whose neighbours come from global memory (L2), no LDS beyond the words of the block sums; 16-byte accesses where the
 // pointers (the stage kernels) or the rows (the pixel kernels) allow, element by element otherwise.
-#include "common.cuh"
-#include "rounded.cuh"
-#include <climits>
+#include "slice_sum.cuh"
 
-#define FI_THREADS 256
-#define MIL_SEED_SLICES 16              // include/mil_hip.h: partial sums per tile of mil_stage_energy / mil_stage_match
-#define MIL_REG_SLICES 16               // include/mil_hip.h: partial sums per tile and norm of mil_pixel_reg
+#define FI_THREADS SLICE_THREADS
 
 template <typename T>
 __device__ __forceinline__ void fi_load8(const typename T::elem* p, float (&v)[8], int vec) {
@@ -37,24 +33,17 @@ __device__ __forceinline__ void fi_store8(typename T::elem* p, const float (&v)[
     for (int j = 0; j < 8; ++j) p[j] = (typename T::elem)v[j];
 }
 
-// The butterfly over a wave's 64 lanes: every lane ends with the same sum, in one order whatever the grid does.
-__device__ __forceinline__ float fi_wave_sum(float s) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s = rn_add(s, __shfl_xor(s, d));
-    return s;
-}
-
 // Workgroup t * MIL_SEED_SLICES + s owns the pixels [s per, (s + 1) per) of tile t, a work item is one 8-channel group of one pixel
-// (stage_seed_kernel's scheme).  The sum: per thread in work-item order and, within a group, in channel order; then the butterfly
-// and the four waves in order.
+// (stage_seed_kernel's scheme).  The sum: per thread in work-item order and, within a group, in channel order; then slice_sum.cuh's
+// butterfly and the four waves in order.
 template <typename T>
 __global__ __launch_bounds__(FI_THREADS) void stage_energy_kernel(const typename T::elem* __restrict__ target, float* __restrict__ part,
                                                                  int hw, int per, int CP, int C, int vec) {
     __shared__ float red[FI_THREADS / 64];
     MIL_POISON_STATIC(red);
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_SEED_SLICES;
-    const size_t t = blockIdx.x / MIL_SEED_SLICES;
-    const int p0 = s * per < hw ? s * per : hw, p1 = p0 + per < hw ? p0 + per : hw;
+    const SliceRange sl = slice_range<MIL_SEED_SLICES, true>(hw, per);
+    const int tid = threadIdx.x, p0 = sl.lo, p1 = sl.hi;
+    const size_t t = sl.t;
     const int NG = CP >> 3;
     float sum = 0.f;
     for (int idx = tid; idx < (p1 - p0) * NG; idx += FI_THREADS) {
@@ -65,10 +54,7 @@ __global__ __launch_bounds__(FI_THREADS) void stage_energy_kernel(const typename
         for (int j = 0; j < 8; ++j)
             if (cg * 8 + j < C) sum = rn_add(sum, rn_mul(a[j], a[j]));
     }
-    sum = fi_wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) part[t * MIL_SEED_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
+    block_sum(sum, red, part + t * MIL_SEED_SLICES + sl.s);
 }
 
 template <typename T>
@@ -78,9 +64,9 @@ __global__ __launch_bounds__(FI_THREADS) void stage_match_kernel(const typename 
                                                                 float slope, int vec) {
     __shared__ float red[FI_THREADS / 64];
     MIL_POISON_STATIC(red);
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_SEED_SLICES;
-    const size_t t = blockIdx.x / MIL_SEED_SLICES;
-    const int p0 = s * per < hw ? s * per : hw, p1 = p0 + per < hw ? p0 + per : hw;
+    const SliceRange sl = slice_range<MIL_SEED_SLICES, true>(hw, per);
+    const int tid = threadIdx.x, p0 = sl.lo, p1 = sl.hi;
+    const size_t t = sl.t;
     const int NG = CP >> 3;
     const float scale = __fdiv_rn(two_w, energy[t]);
     float sum = 0.f;
@@ -101,28 +87,7 @@ __global__ __launch_bounds__(FI_THREADS) void stage_match_kernel(const typename 
         }
         fi_store8<T>(dz + off, o, vec);
     }
-    sum = fi_wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) part[t * MIL_SEED_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
-}
-
-// rows of `slices` partial sums each, added in slice order
-__global__ __launch_bounds__(FI_THREADS) void slice_sum_kernel(const float* __restrict__ part, float* __restrict__ out, int rows, int slices) {
-    const int r = blockIdx.x * FI_THREADS + threadIdx.x;
-    if (r >= rows) return;
-    float s = 0.f;
-    for (int k = 0; k < slices; ++k) s = rn_add(s, part[(size_t)r * slices + k]);
-    out[r] = s;
-}
-
-__global__ __launch_bounds__(FI_THREADS) void stage_match_sum_kernel(const float* __restrict__ part, const float* __restrict__ energy,
-                                                                    float* __restrict__ loss, int n, float weight) {
-    const int t = blockIdx.x * FI_THREADS + threadIdx.x;
-    if (t >= n) return;
-    float s = 0.f;
-    for (int k = 0; k < MIL_SEED_SLICES; ++k) s = rn_add(s, part[(size_t)t * MIL_SEED_SLICES + k]);
-    loss[t] = rn_mul(weight, __fdiv_rn(s, energy[t]));
+    block_sum(sum, red, part + t * MIL_SEED_SLICES + sl.s);
 }
 
 // Where a linear element of a tile [3,H,W] lies; fi_next: the element behind it.
@@ -190,10 +155,10 @@ __global__ __launch_bounds__(FI_THREADS) void pixel_reg_kernel(const float* __re
                                                               int n, int H, int W, int per, PixelRegArgs a) {
     __shared__ float red[2][FI_THREADS / 64];
     MIL_POISON_STATIC(red);
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_REG_SLICES;
-    const size_t t = blockIdx.x / MIL_REG_SLICES;
-    const int HW = H * W, E = 3 * HW, G = (E + 3) >> 2;
-    const int g0 = s * per < G ? s * per : G, g1 = g0 + per < G ? g0 + per : G;
+    const int HW = H * W, E = 3 * HW;
+    const SliceRange sl = slice_range<MIL_REG_SLICES, true>((E + 3) >> 2, per);
+    const int tid = threadIdx.x, g0 = sl.lo, g1 = sl.hi;
+    const size_t t = sl.t;
     const size_t base = t * (size_t)E;
     const bool need_pow = TERMS || a.alpha_on, need_tv = TERMS || a.tv_on;
     float sum_a = 0.f, sum_t = 0.f;
@@ -269,21 +234,22 @@ __global__ __launch_bounds__(FI_THREADS) void pixel_reg_kernel(const float* __re
         }
     }
     if constexpr (TERMS) {
-        sum_a = fi_wave_sum(sum_a);
-        sum_t = fi_wave_sum(sum_t);
-        if ((tid & 63) == 0) { red[0][tid >> 6] = sum_a; red[1][tid >> 6] = sum_t; }
+        sum_a = wave_sum(sum_a);
+        sum_t = wave_sum(sum_t);
+        waves_put(sum_a, red[0]);
+        waves_put(sum_t, red[1]);
         __syncthreads();
-        if (tid < 2) part[((size_t)tid * n + t) * MIL_REG_SLICES + s] = rn_add(rn_add(rn_add(red[tid][0], red[tid][1]), red[tid][2]), red[tid][3]);
+        if (tid < 2) part[((size_t)tid * n + t) * MIL_REG_SLICES + sl.s] = waves_get(red[tid]);         // part [2][n][MIL_REG_SLICES]
     }
 }
 
 // out[tile][c,i,j] = x[tile][c, (i + sy) mod H, (j + sx) mod W], (sy, sx) = (-dy mod H, -dx mod W) formed by the entry point.
 __global__ __launch_bounds__(FI_THREADS) void pixel_shift_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W, int per, int sy,
                                                                 int sx) {
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_REG_SLICES;
-    const size_t t = blockIdx.x / MIL_REG_SLICES;
-    const int HW = H * W, E = 3 * HW, G = (E + 3) >> 2;
-    const int g0 = s * per < G ? s * per : G, g1 = g0 + per < G ? g0 + per : G;
+    const int HW = H * W, E = 3 * HW;
+    const SliceRange sl = slice_range<MIL_REG_SLICES, true>((E + 3) >> 2, per);
+    const int tid = threadIdx.x, g0 = sl.lo, g1 = sl.hi;
+    const size_t t = sl.t;
     const size_t base = t * (size_t)E;
     for (int q = g0 + tid; q < g1; q += FI_THREADS) {
         const int e0 = q * 4, cnt = E - e0 < 4 ? E - e0 : 4;
@@ -299,30 +265,14 @@ __global__ __launch_bounds__(FI_THREADS) void pixel_shift_kernel(const float* __
     }
 }
 
-static bool fi_on16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
-
-static bool fi_overlap(const void* a, const void* b, unsigned long long bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bytes && b0 < a0 + bytes;
-}
-
 static int fi_mod(int v, int m) { return ((v % m) + m) % m; }
-
-// What the stage entries share: MIL_OK when the shape is one the kernels take.
-static int fi_stage_shape(int n, int h, int w, int cp, int c, int dtype) {
-    if (n < 0 || h < 1 || w < 1 || cp < 8 || (cp & 7) || c < 1 || c > cp) return MIL_ERR_ARG;
-    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32) return MIL_ERR_ARG;
-    const unsigned long long hw = (unsigned long long)h * w;
-    if (n > 0 && (hw >= (1ull << 24) || hw * (unsigned long long)cp > 0x7fffffffull || n > INT_MAX / MIL_SEED_SLICES)) return MIL_ERR_UNSUPPORTED;
-    return MIL_OK;
-}
 
 // include/mil_hip.h has the contracts.  Every status but MIL_ERR_LAUNCH is decided here, before any GPU call.
 extern "C" int mil_stage_energy(const void* target, float* energy, float* ws, int n, int h, int w, int cp, int c, int dtype, void* stream) {
     if (!target || !energy || !ws) return MIL_ERR_ARG;
-    const int rc = fi_stage_shape(n, h, w, cp, c, dtype);
+    const int rc = stage_shape(n, h, w, cp, c, dtype);
     if (rc != MIL_OK || n == 0) return rc;
-    const int hw = h * w, per = (hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES, vec = fi_on16(target);
+    const int hw = h * w, per = (hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES, vec = mil_on16(target);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n * MIL_SEED_SLICES);
     if (dtype == MIL_DT_BF16)
@@ -330,7 +280,7 @@ extern "C" int mil_stage_energy(const void* target, float* energy, float* ws, in
     else
         hipLaunchKernelGGL(stage_energy_kernel<F32>, grid, dim3(FI_THREADS), 0, st, (const float*)target, ws, hw, per, cp, c, vec);
     MIL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(slice_sum_kernel, dim3((n + FI_THREADS - 1) / FI_THREADS), dim3(FI_THREADS), 0, st, ws, energy, n, MIL_SEED_SLICES);
+    launch_slice_sum<MIL_SEED_SLICES>(st, ws, energy, n, SumItself{});
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -338,9 +288,9 @@ extern "C" int mil_stage_energy(const void* target, float* energy, float* ws, in
 extern "C" int mil_stage_match(const void* act, const void* target, const float* energy, float* loss, void* dz, float* ws, int n, int h, int w,
                                int cp, int c, float weight, float slope, int dtype, void* stream) {
     if (!act || !target || !energy || !loss || !dz || !ws) return MIL_ERR_ARG;
-    const int rc = fi_stage_shape(n, h, w, cp, c, dtype);
+    const int rc = stage_shape(n, h, w, cp, c, dtype);
     if (rc != MIL_OK || n == 0) return rc;
-    const int hw = h * w, per = (hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES, vec = fi_on16(act) && fi_on16(target) && fi_on16(dz);
+    const int hw = h * w, per = (hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES, vec = mil_on16(act) && mil_on16(target) && mil_on16(dz);
     const float two_w = 2.0f * weight;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n * MIL_SEED_SLICES);
@@ -351,7 +301,7 @@ extern "C" int mil_stage_match(const void* act, const void* target, const float*
         hipLaunchKernelGGL(stage_match_kernel<F32>, grid, dim3(FI_THREADS), 0, st, (const float*)act, (const float*)target, energy, (float*)dz, ws, hw,
                            per, cp, c, two_w, slope, vec);
     MIL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stage_match_sum_kernel, dim3((n + FI_THREADS - 1) / FI_THREADS), dim3(FI_THREADS), 0, st, ws, energy, loss, n, weight);
+    launch_slice_sum<MIL_SEED_SLICES>(st, ws, loss, n, SumWeightedRatio{energy, weight});
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -372,8 +322,8 @@ extern "C" int mil_pixel_reg(const float* x, const float* g, float* out, float* 
     dy = fi_mod(dy, H);
     dx = fi_mod(dx, W);
     const unsigned long long bytes = 12ull * (unsigned long long)n * H * W;
-    if (out == g ? (dy || dx) : fi_overlap(out, g, bytes)) return MIL_ERR_ARG;
-    if (fi_overlap(out, x, bytes)) return MIL_ERR_ARG;
+    if (out == g ? (dy || dx) : mil_overlap(out, g, bytes)) return MIL_ERR_ARG;
+    if (mil_overlap(out, x, bytes)) return MIL_ERR_ARG;
     if (n == 0) return MIL_OK;
     const int G = (3 * H * W + 3) / 4, per = (G + MIL_REG_SLICES - 1) / MIL_REG_SLICES;
     const PixelRegArgs a{alpha_weight * (float)alpha, 2.0f * tv_weight, alpha, alpha_weight != 0.f, tv_weight != 0.f, dy, dx};
@@ -382,7 +332,7 @@ extern "C" int mil_pixel_reg(const float* x, const float* g, float* out, float* 
     if (terms) {
         hipLaunchKernelGGL(pixel_reg_kernel<true>, grid, dim3(FI_THREADS), 0, st, x, g, out, ws, n, H, W, per, a);
         MIL_CHECK_LAUNCH();
-        hipLaunchKernelGGL(slice_sum_kernel, dim3((2 * n + FI_THREADS - 1) / FI_THREADS), dim3(FI_THREADS), 0, st, ws, terms, 2 * n, MIL_REG_SLICES);
+        launch_slice_sum<MIL_REG_SLICES>(st, ws, terms, 2 * n, SumItself{});
     } else {
         hipLaunchKernelGGL(pixel_reg_kernel<false>, grid, dim3(FI_THREADS), 0, st, x, g, out, ws, n, H, W, per, a);
     }
@@ -394,7 +344,7 @@ extern "C" int mil_pixel_shift(const float* x, float* out, int n, int H, int W, 
     if (!x || !out) return MIL_ERR_ARG;
     const int rc = fi_pixel_shape(n, H, W);
     if (rc != MIL_OK) return rc;
-    if (fi_overlap(out, x, 12ull * (unsigned long long)n * H * W)) return MIL_ERR_ARG;
+    if (mil_overlap(out, x, 12ull * (unsigned long long)n * H * W)) return MIL_ERR_ARG;
     if (n == 0) return MIL_OK;
     const int G = (3 * H * W + 3) / 4, per = (G + MIL_REG_SLICES - 1) / MIL_REG_SLICES;
     hipLaunchKernelGGL(pixel_shift_kernel, dim3((unsigned)n * MIL_REG_SLICES), dim3(FI_THREADS), 0, reinterpret_cast<hipStream_t>(stream), x, out, H, W,

@@ -4,7 +4,7 @@
 //
 //   stage_seed_kernel<T>          J_t = mean_{y,x} act[t,y,x,ch_t] (partial sums) and dz, the gradient of -J_t in the form the
 //                                 backward chain carries: -(1/(h w)) * lrelu'(act) at channel ch_t, zero everywhere else
-//   stage_seed_sum_kernel         a tile's partial sums added in slice order, divided by h w: objective [T]
+//   slice_sum_kernel<.., SumOverCount>   (slice_sum.cuh) a tile's partial sums added in slice order, divided by h w: objective [T]
 //   pixel_step_kernel<RULE, PROJ> one SGD, Adam or momentum-SGD step on x [T,3,H,W] fp32 in place, the projection of the new image
 //                                 (none, clamp to [-1,1], or the round trip through bytes) and its bytes, in one pass
 //
@@ -12,27 +12,24 @@
 // rn_sub of rounded.cuh carry no `contract` flag; __fdiv_rn, rn_sqrt): numpy's fp32 arithmetic gives the same bits.  Both are streaming
 // kernels: 16-byte loads and stores where the pointers allow, no LDS beyond four words of the block sum, no atomics, every sum in
 // a fixed order.
-#include "common.cuh"
-#include "rounded.cuh"
-#include <climits>
+#include "slice_sum.cuh"
 
-#define FV_THREADS 256
-#define MIL_SEED_SLICES 16              // include/mil_hip.h: partial sums per tile of mil_stage_seed
+#define FV_THREADS SLICE_THREADS
 
 // Workgroup t * MIL_SEED_SLICES + s owns the pixels [s per, (s + 1) per) of tile t.  A work item is one 8-channel group of one
 // pixel: it writes the group's eight dz values and, when it is the group of the tile's channel, reads that ONE activation.  A
 // channel outside [0, C) selects nothing (dz all zero, J = 0): no address is formed from it.  part [T][MIL_SEED_SLICES]: the sum of
-// the workgroup's activations — per thread in work-item order, then the butterfly over the wave's lanes and the four waves in
-// order: one summation tree per (h w, CP), whatever the grid does.
+// the workgroup's activations by slice_sum.cuh's tree — per thread in work-item order, then the butterfly over the wave's lanes
+// and the four waves in order: one summation tree per (h w, CP), whatever the grid does.
 template <typename T>
 __global__ __launch_bounds__(FV_THREADS) void stage_seed_kernel(const typename T::elem* __restrict__ act, const int* __restrict__ channels,
                                                                typename T::elem* __restrict__ dz, float* __restrict__ part, int hw, int per,
                                                                int CP, int C, float neg_inv, float slope) {
     __shared__ float red[FV_THREADS / 64];
     MIL_POISON_STATIC(red);
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_SEED_SLICES;
-    const size_t t = blockIdx.x / MIL_SEED_SLICES;
-    const int p0 = s * per < hw ? s * per : hw, p1 = p0 + per < hw ? p0 + per : hw;
+    const SliceRange sl = slice_range<MIL_SEED_SLICES, true>(hw, per);
+    const int tid = threadIdx.x, p0 = sl.lo, p1 = sl.hi;
+    const size_t t = sl.t;
     const int NG = CP >> 3;
     const int ch = channels[t];
     const int cg_t = (ch >= 0 && ch < C) ? ch >> 3 : -1, cj = ch & 7;
@@ -50,19 +47,7 @@ __global__ __launch_bounds__(FV_THREADS) void stage_seed_kernel(const typename T
         }
         store8<T>(dz + off, v);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum = rn_add(sum, __shfl_xor(sum, d));
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) part[t * MIL_SEED_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
-}
-
-__global__ __launch_bounds__(FV_THREADS) void stage_seed_sum_kernel(const float* __restrict__ part, float* __restrict__ objective, int n, float hw) {
-    const int t = blockIdx.x * FV_THREADS + threadIdx.x;
-    if (t >= n) return;
-    float s = 0.f;
-    for (int k = 0; k < MIL_SEED_SLICES; ++k) s = rn_add(s, part[(size_t)t * MIL_SEED_SLICES + k]);
-    objective[t] = __fdiv_rn(s, hw);
+    block_sum(sum, red, part + t * MIL_SEED_SLICES + sl.s);
 }
 
 // rint(clip(x / 2 + 0.5, 0, 1) * 255): x / 2 is exact, the sum and the product are rounded once each, the rounding to an integer is
@@ -160,74 +145,65 @@ __global__ __launch_bounds__(FV_THREADS) void pixel_step_kernel(float* __restric
 // include/mil_hip.h has the contracts.  Every status but MIL_ERR_LAUNCH is decided here, before any GPU call.
 extern "C" int mil_stage_seed(const void* act, const int* channels, float* objective, void* dz, float* ws, int n, int h, int w, int cp,
                               int c, float slope, int dtype, void* stream) {
-    if (!act || !channels || !objective || !dz || !ws || n < 0 || h < 1 || w < 1 || cp < 8 || (cp & 7) || c < 1 || c > cp) return MIL_ERR_ARG;
-    if (dtype != MIL_DT_BF16 && dtype != MIL_DT_F32) return MIL_ERR_ARG;
-    if (n == 0) return MIL_OK;
-    const unsigned long long hw = (unsigned long long)h * w;
-    if (hw >= (1ull << 24) || hw * (unsigned long long)cp > 0x7fffffffull || n > INT_MAX / MIL_SEED_SLICES) return MIL_ERR_UNSUPPORTED;
-    const int per = (int)((hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES);
+    if (!act || !channels || !objective || !dz || !ws) return MIL_ERR_ARG;
+    const int rc = stage_shape(n, h, w, cp, c, dtype);
+    if (rc != MIL_OK || n == 0) return rc;
+    const int hw = h * w, per = (hw + MIL_SEED_SLICES - 1) / MIL_SEED_SLICES;
     const float neg_inv = -(1.0f / (float)hw);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n * MIL_SEED_SLICES);
     if (dtype == MIL_DT_BF16)
-        hipLaunchKernelGGL(stage_seed_kernel<BF16>, grid, dim3(FV_THREADS), 0, st, (const __bf16*)act, channels, (__bf16*)dz, ws, (int)hw, per, cp, c,
+        hipLaunchKernelGGL(stage_seed_kernel<BF16>, grid, dim3(FV_THREADS), 0, st, (const __bf16*)act, channels, (__bf16*)dz, ws, hw, per, cp, c,
                            neg_inv, slope);
     else
-        hipLaunchKernelGGL(stage_seed_kernel<F32>, grid, dim3(FV_THREADS), 0, st, (const float*)act, channels, (float*)dz, ws, (int)hw, per, cp, c,
+        hipLaunchKernelGGL(stage_seed_kernel<F32>, grid, dim3(FV_THREADS), 0, st, (const float*)act, channels, (float*)dz, ws, hw, per, cp, c,
                            neg_inv, slope);
     MIL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stage_seed_sum_kernel, dim3((n + FV_THREADS - 1) / FV_THREADS), dim3(FV_THREADS), 0, st, ws, objective, n, (float)hw);
+    launch_slice_sum<MIL_SEED_SLICES>(st, ws, objective, n, SumOverCount{(float)hw});
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
 
+// What mil_pixel_step and mil_pixel_momentum_step share, behind their own rule-specific checks: the checks of x, g, the
+// projection and the two scalars every rule has, the grid, and `vec` from the pointers RULE actually uses (x, g, the moments
+// that are not null, u8_out).
 template <int RULE>
-static void launch_pixel_step(int project, dim3 grid, hipStream_t st, float* x, const float* g, float* m, float* v, uint8_t* u8_out,
-                              const float* table, const PixelStepArgs& a, unsigned long long total, int vec) {
+static int pixel_step_entry(float* x, const float* g, float* m, float* v, unsigned char* u8_out, const float* table, size_t total, int project,
+                            const PixelStepArgs& a, void* stream) {
+    if (!x || !g || project < 0 || project > 2) return MIL_ERR_ARG;
+    if (project == 2 && !table) return MIL_ERR_ARG;
+    if (!(a.lr == a.lr) || !(a.wd == a.wd)) return MIL_ERR_ARG;
+    if (total == 0) return MIL_OK;
+    const unsigned long long blocks = (((unsigned long long)total + 3) / 4 + FV_THREADS - 1) / FV_THREADS;
+    if (blocks > INT_MAX) return MIL_ERR_UNSUPPORTED;
+    const uintptr_t grid16 = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+    const int vec = !(grid16 & 15) && !(reinterpret_cast<uintptr_t>(u8_out) & 3);
+    const dim3 grid((unsigned)blocks), block(FV_THREADS);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (project == 0)
-        hipLaunchKernelGGL((pixel_step_kernel<RULE, 0>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 0>), grid, block, 0, st, x, g, m, v, u8_out, table, a, (unsigned long long)total, vec);
     else if (project == 1)
-        hipLaunchKernelGGL((pixel_step_kernel<RULE, 1>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 1>), grid, block, 0, st, x, g, m, v, u8_out, table, a, (unsigned long long)total, vec);
     else
-        hipLaunchKernelGGL((pixel_step_kernel<RULE, 2>), grid, dim3(FV_THREADS), 0, st, x, g, m, v, u8_out, table, a, total, vec);
+        hipLaunchKernelGGL((pixel_step_kernel<RULE, 2>), grid, block, 0, st, x, g, m, v, u8_out, table, a, (unsigned long long)total, vec);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
 }
 
 extern "C" int mil_pixel_step(float* x, const float* g, float* m, float* v, unsigned char* u8_out, const float* table, size_t total,
                               int rule, int project, float lr, float weight_decay, float beta1, float one_minus_beta1, float beta2,
                               float one_minus_beta2, float bc1, float sqrt_bc2, float eps, void* stream) {
-    if (!x || !g || rule < 0 || rule > 1 || project < 0 || project > 2) return MIL_ERR_ARG;
+    if (rule < 0 || rule > 1) return MIL_ERR_ARG;
     if (rule == 1 && (!m || !v || !(bc1 > 0.f) || !(sqrt_bc2 > 0.f) || !(eps >= 0.f))) return MIL_ERR_ARG;
-    if (project == 2 && !table) return MIL_ERR_ARG;
-    if (!(lr == lr) || !(weight_decay == weight_decay)) return MIL_ERR_ARG;
-    if (total == 0) return MIL_OK;
-    const unsigned long long blocks = (((unsigned long long)total + 3) / 4 + FV_THREADS - 1) / FV_THREADS;
-    if (blocks > INT_MAX) return MIL_ERR_UNSUPPORTED;
-    uintptr_t grid16 = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g);
-    if (rule == 1) grid16 |= reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
-    const int vec = !(grid16 & 15) && !(reinterpret_cast<uintptr_t>(u8_out) & 3);
     const PixelStepArgs a{lr, weight_decay, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, sqrt_bc2, eps};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (rule == 0)
-        launch_pixel_step<0>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
-    else
-        launch_pixel_step<1>(project, dim3((unsigned)blocks), st, x, g, m, v, u8_out, table, a, total, vec);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    if (rule == 0) return pixel_step_entry<0>(x, g, nullptr, nullptr, u8_out, table, total, project, a, stream);     // SGD reads no moments
+    return pixel_step_entry<1>(x, g, m, v, u8_out, table, total, project, a, stream);
 }
 
 // The third RULE of the kernel above behind an entry of its own: mil_pixel_step's rules and their instantiations stay as they are.
 extern "C" int mil_pixel_momentum_step(float* x, const float* g, float* buf, unsigned char* u8_out, const float* table, size_t total,
                                        int project, float lr, float weight_decay, float momentum, void* stream) {
-    if (!x || !g || !buf || project < 0 || project > 2) return MIL_ERR_ARG;
-    if (project == 2 && !table) return MIL_ERR_ARG;
-    if (!(lr == lr) || !(weight_decay == weight_decay) || !(momentum == momentum)) return MIL_ERR_ARG;
-    if (total == 0) return MIL_OK;
-    const unsigned long long blocks = (((unsigned long long)total + 3) / 4 + FV_THREADS - 1) / FV_THREADS;
-    if (blocks > INT_MAX) return MIL_ERR_UNSUPPORTED;
-    const uintptr_t grid16 = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf);
-    const int vec = !(grid16 & 15) && !(reinterpret_cast<uintptr_t>(u8_out) & 3);
-    const PixelStepArgs a{lr, weight_decay, momentum, 0.f, 0.f, 0.f, 1.f, 1.f, 0.f};
-    launch_pixel_step<2>(project, dim3((unsigned)blocks), reinterpret_cast<hipStream_t>(stream), x, g, buf, nullptr, u8_out, table, a, total, vec);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    if (!buf || !(momentum == momentum)) return MIL_ERR_ARG;
+    return pixel_step_entry<2>(x, g, buf, nullptr, u8_out, table, total, project, PixelStepArgs{lr, weight_decay, momentum, 0.f, 0.f, 0.f, 1.f, 1.f, 0.f},
+                               stream);
 }

@@ -5,7 +5,7 @@
 //
 //   path_point_kernel<U8>    out[t,c,y,x] = base[c] + alpha * (v - base[c]) + sigma * n(seed, sample, i)      fp32 [T,3,H,W]
 //   attr_finish_kernel<U8>   attr = (v - base[c]) * acc, a map [T,H,W] of it (or of acc), and 32 partial sums per tile
-//   attr_sum_kernel          the 32 partial sums of a tile added in slice order: tile_sum [T]
+//   slice_sum_kernel<..>     (slice_sum.cuh) the 32 partial sums of a tile added in slice order: tile_sum [T]
 //
 // v is the fp32 tile value or mil_u8_decode(code) of a uint8 tile (u8_feed.cuh: bit for bit `U8Tiles.float()`).  Every
 // product, difference and sum that reaches an output is a single correctly rounded fp32 operation (rn_sub, rn_mul,
@@ -18,13 +18,10 @@
 // owns those four elements draws them — a value depends on (seed, sample, i) and on nothing else, not on the launch geometry
 // and not on T, H or W beyond i.  Both kernels are streaming: 16-byte loads and stores where the pointers allow, no LDS beyond
 // four words of the block sum, no atomics, every sum in a fixed order.
-#include "common.cuh"
+#include "slice_sum.cuh"
 #include "u8_feed.cuh"
-#include "rounded.cuh"
-#include <climits>
 
-#define PA_THREADS 256
-#define MIL_ATTR_SLICES 32              // include/mil_hip.h: partial sums per tile of mil_attr_finish
+#define PA_THREADS SLICE_THREADS
 
 __device__ __forceinline__ void pa_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                                  unsigned (&r)[4]) {
@@ -119,16 +116,17 @@ __global__ __launch_bounds__(PA_THREADS) void path_point_kernel(const void* __re
 // Workgroup t * MIL_ATTR_SLICES + s owns the pixels [s per, (s + 1) per) of tile t (per: a multiple of 4), all three channels
 // of each: a thread takes four consecutive pixels at a time.  vec: hw % 4 == 0 and every pointer on its 16-byte (uint8: 4-byte) grid.
 // part (nullable) [T][MIL_ATTR_SLICES]: the sum of attr over the workgroup's pixels — per thread in pixel order, (a0 + a1) + a2
-// per pixel, then the butterfly over the wave's lanes and the four waves in order: one summation tree per (hw), no atomics.
+// per pixel, then slice_sum.cuh's butterfly over the wave's lanes and the four waves in order: one summation tree per (hw), no
+// atomics.  The start of a slice is NOT clamped to hw (an empty trailing slice has p0 > p1 and its loop does not run).
 template <bool U8>
 __global__ __launch_bounds__(PA_THREADS) void attr_finish_kernel(const float* __restrict__ acc, const void* __restrict__ tiles, float b0, float b1,
                                                                 float b2, float* __restrict__ attr, float* __restrict__ map, int mode,
                                                                 float* __restrict__ part, int hw, int per, int vec) {
     __shared__ float red[PA_THREADS / 64];
     MIL_POISON_STATIC(red);
-    const int tid = threadIdx.x, s = blockIdx.x % MIL_ATTR_SLICES;
-    const size_t t = blockIdx.x / MIL_ATTR_SLICES;
-    const int p0 = s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    const SliceRange sl = slice_range<MIL_ATTR_SLICES, false>(hw, per);
+    const int tid = threadIdx.x, p0 = sl.lo, p1 = sl.hi;
+    const size_t t = sl.t;
     const bool need_x = attr || part || (map && mode != 2);
     const float base[3] = {b0, b1, b2};
     float sum = 0.f;
@@ -205,20 +203,7 @@ __global__ __launch_bounds__(PA_THREADS) void attr_finish_kernel(const float* __
             }
         }
     }
-    if (!part) return;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum = rn_add(sum, __shfl_xor(sum, d));
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) part[t * MIL_ATTR_SLICES + s] = rn_add(rn_add(rn_add(red[0], red[1]), red[2]), red[3]);
-}
-
-__global__ __launch_bounds__(PA_THREADS) void attr_sum_kernel(const float* __restrict__ part, float* __restrict__ tile_sum, int n) {
-    const int t = blockIdx.x * PA_THREADS + threadIdx.x;
-    if (t >= n) return;
-    float s = 0.f;
-    for (int k = 0; k < MIL_ATTR_SLICES; ++k) s = rn_add(s, part[(size_t)t * MIL_ATTR_SLICES + k]);
-    tile_sum[t] = s;
+    if (part) block_sum(sum, red, part + t * MIL_ATTR_SLICES + sl.s);          // (part is the same for the whole workgroup)
 }
 
 // include/mil_hip.h has the contracts.  Every status but MIL_ERR_LAUNCH is decided here, before any GPU call.
@@ -269,7 +254,7 @@ extern "C" int mil_attr_finish(const float* acc, const void* tiles, int is_u8, f
                            (int)hw, per, vec);
     MIL_CHECK_LAUNCH();
     if (tile_sum) {
-        hipLaunchKernelGGL(attr_sum_kernel, dim3((n + PA_THREADS - 1) / PA_THREADS), dim3(PA_THREADS), 0, st, ws, tile_sum, n);
+        launch_slice_sum<MIL_ATTR_SLICES>(st, ws, tile_sum, n, SumItself{});
         MIL_CHECK_LAUNCH();
     }
     return MIL_OK;

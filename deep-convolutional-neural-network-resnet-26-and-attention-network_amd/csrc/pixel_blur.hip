@@ -159,11 +159,6 @@ __global__ __launch_bounds__(PB_THREADS) void pixel_blur_kernel(const float* __r
     }
 }
 
-static bool pb_overlap(const void* a, const void* b, unsigned long long bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bytes && b0 < a0 + bytes;
-}
-
 // include/mil_hip.h has the contract.  Every status but MIL_ERR_LAUNCH is decided here, before any GPU call.
 extern "C" int mil_pixel_blur(const float* x, float* out, const float* taps, int planes, int H, int W, int radius, int edge, void* stream) {
     if (!x || !out || !taps || planes < 0 || H < 1 || W < 1) return MIL_ERR_ARG;
@@ -173,7 +168,7 @@ extern "C" int mil_pixel_blur(const float* x, float* out, const float* taps, int
     const unsigned long long tiles = (unsigned long long)((W + PB_TILE - 1) / PB_TILE) * (unsigned long long)((H + PB_TILE - 1) / PB_TILE);
     // a plane as large as the stacks [n,3,H,W] of mil_pixel_shift take, a grid that fits an int
     if (planes > 0 && (3ull * hw > 0x7fffffffull - 3 || tiles * (unsigned long long)planes > (unsigned long long)INT_MAX)) return MIL_ERR_UNSUPPORTED;
-    if (pb_overlap(out, x, 4ull * (unsigned long long)planes * hw)) return MIL_ERR_ARG;
+    if (mil_overlap(out, x, 4ull * (unsigned long long)planes * hw)) return MIL_ERR_ARG;
     if (planes == 0) return MIL_OK;
     const int tiles_x = (W + PB_TILE - 1) / PB_TILE, tiles_y = (H + PB_TILE - 1) / PB_TILE;
     const int rp = (radius + 3) & ~3;

@@ -127,6 +127,33 @@ class PixelRegularizer:
         return ops.pixel_blur(g, xs, sigma=self.grad_blur_sigma, edge=self.blur_edge) if self.grad_blur_sigma else g
 
 
+def pixel_descent(x, steps, reg, gradient, step, want_terms=False):
+    """The loop of the pixel optimisers (`FeatureInverter.invert`, `FeatureVisualizer.filters` / `dream` / `classes`): `steps`
+    steps on the stack x, fp32 [T,3,H,W] on the device.  reg: a `PixelRegularizer`, whose protocol is followed here and nowhere
+    else, or None — then no `pixel_shift`, `pixel_reg` or `pixel_blur` is launched and no scratch stack is allocated.
+      gradient(xin, k) -> g    step k's objective on xin, the tensor the network reads (x, or its jittered copy), and its
+                               gradient with respect to xin; called in the caller's grad mode
+      step(x, g, k, u8_out)    the optimiser step on x in place, under `torch.no_grad()` like everything behind `gradient`;
+                               u8_out: the byte buffer in the last step, which encodes into it, None before
+    -> (x, u8, terms): the stack the last step wrote (a step that starts with an image blur swaps x with a scratch stack), its
+    bytes, and with want_terms the regulariser's norms per step, fp32 [steps,2,T] (else None)."""
+    u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    terms = torch.empty((steps, 2, x.shape[0]), dtype=torch.float32, device=x.device) if want_terms else None
+    if reg is not None:
+        shifts, (xs, out) = reg.shifts(steps), reg.scratch(x)
+    for k in range(steps):
+        xin = x
+        if reg is not None:
+            x, xs = reg.blurred(x, xs, k)
+            xin = reg.jittered(x, xs, shifts[k])
+        g = gradient(xin, k)
+        with torch.no_grad():
+            if reg is not None:
+                g = reg.gradient(x, g, out, shifts[k], None if terms is None else terms[k], xs)
+            step(x, g, k, u8 if k == steps - 1 else None)
+    return x, u8, terms
+
+
 def gaussian_blur(x, sigma, edge="reflect", out=None):
     """The Gaussian blur of every plane of a stack [T,3,H,W] or of maps [T,H,W] (fp32, contiguous, on the device) in one launch:
     `scipy.ndimage.gaussian_filter(plane, sigma, truncate=4.0)` with the mode edge stands for ("reflect": scipy's "mirror",
@@ -198,30 +225,28 @@ class FeatureInverter:
         init_std = float(init_std)
         if not init_std >= 0.0 or init_std == float("inf"):
             raise ValueError(f"init_std must be a number >= 0, got {init_std}")
-        net, reg, c = self.net, self.regularizer, STAGE_WIDTHS[stage - 1]
+        net, c = self.net, STAGE_WIDTHS[stage - 1]
         dev = model_device(net, "FeatureInverter")
-        shifts = reg.shifts(steps)
         gen = torch.Generator().manual_seed(seed)
         x = (init_std * torch.randn(tuple(tiles.shape), generator=gen, dtype=torch.float32)).to(dev)
-        n = x.shape[0]
-        trace = torch.empty((steps, n), dtype=torch.float32, device=dev)
-        terms = torch.empty((steps, 2, n), dtype=torch.float32, device=dev)
-        u8 = torch.empty(x.shape, dtype=torch.uint8, device=dev)
+        trace = torch.empty((steps, x.shape[0]), dtype=torch.float32, device=dev)
         buf = torch.zeros_like(x)
-        xs, out = reg.scratch(x)
         lr = self.lr
         with torch.no_grad(), compute_mode(net) as dtype:
             target = self._target(tiles, stage, dtype)
             energy = ops.stage_energy(target, c)
-            for k in range(steps):
-                x, xs = reg.blurred(x, xs, k)
-                _feats, saved = encoder_forward(net, reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
+
+            def gradient(xin, k):
+                _feats, saved = encoder_forward(net, xin, dtype, upto=stage)
                 _loss, dz = ops.stage_match(saved["blocks"][-1][2], target, c, weight=self.weight, energy=energy, loss=trace[k])
-                g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
-                g = reg.gradient(x, g, out, shifts[k], terms[k], xs)
-                ops.pixel_momentum_step(x, g, buf, lr=lr, momentum=self.momentum, project=self.project, u8_out=u8 if k == steps - 1 else None)
+                return encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)[0]
+
+            def step(x, g, k, u8_out):
+                nonlocal lr
+                ops.pixel_momentum_step(x, g, buf, lr=lr, momentum=self.momentum, project=self.project, u8_out=u8_out)
                 if self.lr_decay is not None and k % self.lr_decay[0] == 0:
                     lr *= self.lr_decay[1]
+            x, u8, terms = pixel_descent(x, steps, self.regularizer, gradient, step, want_terms=True)
         return InversionResult(U8Tiles(u8), x, trace, terms)
 
     def distance(self, x, tiles, layer):

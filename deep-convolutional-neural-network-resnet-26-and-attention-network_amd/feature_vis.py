@@ -17,7 +17,7 @@ import torch
 from . import ops
 from .attribution import LAYERS, bag_evaluate, bag_setup, channel_list, check_tiles, compute_mode, device_tiles, model_device, narrow_encoder, stage_of  # noqa: F401
 from .encoder import STAGE_WIDTHS, encoder_forward, encoder_pixel_gradient
-from .feature_inv import check_regularizer
+from .feature_inv import _count, check_regularizer, pixel_descent
 from .preprocess import U8Tiles
 
 OPTIMIZERS = ops.PIXEL_RULES
@@ -27,12 +27,6 @@ FeatureVisResult = namedtuple("FeatureVisResult", ["u8", "x", "trace"])
 FeatureVisResult.__doc__ = """What an optimisation returns: `u8`, the final images as `U8Tiles` (the toolkit's `recreate_image` at this
 project's mean and std of 0.5); `x`, the same images as the fp32 [T,3,H,W] stack that was optimised; `trace` fp32 [steps, T], the
 objective of the image each step STARTED from (the filter's mean activation; minus the bag's loss for `classes`)."""
-
-
-def _count(v, name, least=1):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < least:
-        raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
-    return int(v)
 
 
 def _size(size):
@@ -114,20 +108,14 @@ class FeatureVisualizer:
         u8 = torch.randint(init[0], init[1], (ntiles, 3, size[0], size[1]), generator=gen, dtype=torch.uint8)
         return U8Tiles(u8.to(self._device())).float()
 
-    def _step(self, x, g, state, k, last, u8):
-        ops.pixel_step(x, g, state, rule=self.optimizer, lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
-                       step=k + 1, project=self.project, u8_out=u8 if last else None)
+    def _descend(self, x, steps, gradient):
+        """`pixel_descent` with this visualiser's optimiser, projection and regulariser -> (x, u8)."""
+        state = (torch.zeros_like(x), torch.zeros_like(x)) if self.optimizer == "adam" else None
 
-    def _state(self, x):
-        return (torch.zeros_like(x), torch.zeros_like(x)) if self.optimizer == "adam" else None
-
-    def _regularised(self, x, steps):
-        """(regulariser, its shift per step, the buffers of the jittered copy and of the gradient moved back) — Nones without one."""
-        reg = self.regularizer
-        if reg is None:
-            return None, None, None, None
-        xs, out = reg.scratch(x)
-        return reg, reg.shifts(steps), xs, out
+        def step(x, g, k, u8_out):
+            ops.pixel_step(x, g, state, rule=self.optimizer, lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, eps=self.eps,
+                           step=k + 1, project=self.project, u8_out=u8_out)
+        return pixel_descent(x, steps, self.regularizer, gradient, step)[:2]
 
     def _ascend(self, x, stage, chans, steps):
         """`steps` steps on x (fp32 on the device, optimised in place) for channel chans[t] of stage `stage`."""
@@ -135,19 +123,12 @@ class FeatureVisualizer:
         c = STAGE_WIDTHS[stage - 1]
         ch = torch.tensor(chans, dtype=torch.int32).to(x.device)
         trace = torch.empty((steps, x.shape[0]), dtype=torch.float32, device=x.device)
-        u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-        state = self._state(x)
-        reg, shifts, xs, out = self._regularised(x, steps)
         with torch.no_grad(), compute_mode(net) as dtype:
-            for k in range(steps):
-                if reg is not None:
-                    x, xs = reg.blurred(x, xs, k)
-                _feats, saved = encoder_forward(net, x if reg is None else reg.jittered(x, xs, shifts[k]), dtype, upto=stage)
+            def gradient(xin, k):
+                _feats, saved = encoder_forward(net, xin, dtype, upto=stage)
                 _j, dz = ops.stage_seed(saved["blocks"][-1][2], ch, c, objective=trace[k])
-                g, _sal = encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)
-                if reg is not None:
-                    g = reg.gradient(x, g, out, shifts[k], xs=xs)
-                self._step(x, g, state, k, k == steps - 1, u8)
+                return encoder_pixel_gradient(net, saved, dtype, dz=dz, stage=stage)[0]
+            x, u8 = self._descend(x, steps, gradient)
         return FeatureVisResult(U8Tiles(u8), x, trace)
 
     # ---- methods -----------------------------------------------------------------------------------------------------------
@@ -188,18 +169,11 @@ class FeatureVisualizer:
         setup = bag_setup(model, ntiles, int(label))
         weights = [w.detach() for w in model.head_weights()]      # hoisted out of the loop: the model does not change under it
         trace = torch.empty((steps, ntiles), dtype=torch.float32, device=x.device)
-        u8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-        state = self._state(x)
-        reg, shifts, xs, out = self._regularised(x, steps)
         with compute_mode(self.net) as dtype:
-            for k in range(steps):
-                if reg is not None:
-                    x, xs = reg.blurred(x, xs, k)
-                saved, dH, loss = bag_evaluate(model, setup, x if reg is None else reg.jittered(x, xs, shifts[k]), weights=weights)
+            def gradient(xin, k):
+                saved, dH, loss = bag_evaluate(model, setup, xin, weights=weights)      # outside no_grad: the head is differentiated by autograd
                 with torch.no_grad():
                     trace[k] = -loss
-                    g, _sal = encoder_pixel_gradient(self.net, saved, dtype, dfeats=dH)
-                    if reg is not None:
-                        g = reg.gradient(x, g, out, shifts[k], xs=xs)
-                    self._step(x, g, state, k, k == steps - 1, u8)
+                    return encoder_pixel_gradient(self.net, saved, dtype, dfeats=dH)[0]
+            x, u8 = self._descend(x, steps, gradient)
         return FeatureVisResult(U8Tiles(u8), x, trace)

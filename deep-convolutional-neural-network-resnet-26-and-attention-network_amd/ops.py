@@ -843,22 +843,28 @@ def attr_finish(acc, tiles, base, *, want_attr=True, want_map=False, map_mode="s
     return attr, amap, sums
 
 
+def _stage_map(t, c, name):
+    """(n, h, w, cp, dtype code) of a stage output [T,h,w,cpad(c)], checked."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{name} must be [T,h,w,cp], got {tuple(getattr(t, 'shape', ()))}")
+    n, h, w, cp = t.shape
+    if cp != cpad(c) or c < 1:
+        raise ValueError(f"{c} real channels go with {cpad(c)} stored ones, got {cp}")
+    if h < 1 or w < 1:
+        raise ValueError(f"maps of {h}x{w}")
+    code = L.dt_code(t.dtype)
+    _need(t, t.shape, t.dtype, name)
+    return n, h, w, cp, code
+
+
 def stage_seed(act, channels, c, *, objective=None, dz=None, slope=LEAK):
     """Objective and seed gradient of activation maximisation at a stage output (see mil_stage_seed): act [T,h,w,cpad(c)] — the
     stage's output as the forward keeps it, bf16 or fp32 — and channels, int32 [T] on the device, one channel in [0, c) per tile
     -> (objective fp32 [T] = the mean of each tile's channel, dz like act = the gradient of MINUS that mean with respect to the
     pre-activation map: -(1/(h w)) lrelu'(act) at the tile's channel, zero elsewhere).  `objective` / `dz`: the caller's own
     output tensors (checked) — a row of a trace, for one."""
-    if not isinstance(act, torch.Tensor) or act.dim() != 4:
-        raise ValueError(f"act must be [T,h,w,cp], got {tuple(getattr(act, 'shape', ()))}")
-    n, h, w, cp = act.shape
     c = int(c)
-    if cp != cpad(c) or c < 1:
-        raise ValueError(f"{c} real channels go with {cpad(c)} stored ones, got {cp}")
-    if h < 1 or w < 1:
-        raise ValueError(f"maps of {h}x{w}")
-    code = L.dt_code(act.dtype)
-    _need(act, act.shape, act.dtype, "act")
+    n, h, w, cp, code = _stage_map(act, c, "act")
     if not isinstance(channels, torch.Tensor):
         raise ValueError("channels must be an int32 [T] tensor on the device")
     _need(channels, (n,), torch.int32, "channels")
@@ -895,6 +901,22 @@ def pixel_step_scalars(rule, lr, weight_decay, betas, eps, step):
     return lr, wd, b1, 1.0 - b1, b2, 1.0 - b2, bc1, bc2 ** 0.5, eps
 
 
+def _pixel_step_tail(symbol, label, x, g, state, u8_out, project, *scalars):
+    """What `pixel_step` and `pixel_momentum_step` share behind their own checks of the rule: g, the rule's state tensors
+    ((name, tensor) pairs, None where it keeps none) and u8_out checked against x, the decode table of project="u8", and the
+    launch, timed as label + (project, whether it encodes).  Returns x."""
+    for name, t in (("x", x), ("g", g)) + state:
+        _need(t, x.shape, torch.float32, name)
+    _need(u8_out, x.shape, torch.uint8, "u8_out")
+    table = None
+    if project == "u8":
+        from .preprocess import U8Tiles
+        table = U8Tiles.decode_table(x.device)
+    _launch(symbol, label + (project, u8_out is not None), x.data_ptr(), g.data_ptr(), *(L.ptr(t) for _name, t in state), L.ptr(u8_out),
+            L.ptr(table), x.numel(), *scalars, L.stream_ptr())
+    return x
+
+
 def pixel_step(x, g, state=None, *, rule="adam", lr=0.1, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, step=1, project="none",
                u8_out=None):
     """One optimiser step on the images x [T,3,H,W] fp32 for the gradient g, in place and in one pass (see mil_pixel_step).
@@ -914,32 +936,8 @@ def pixel_step(x, g, state=None, *, rule="adam", lr=0.1, weight_decay=0.0, betas
         m, v = state
     elif state is not None:
         raise ValueError("rule='sgd' keeps no state")
-    _need(x, x.shape, torch.float32, "x")
-    _need(g, x.shape, torch.float32, "g")
-    _need(m, x.shape, torch.float32, "m")
-    _need(v, x.shape, torch.float32, "v")
-    _need(u8_out, x.shape, torch.uint8, "u8_out")
-    table = None
-    if project == "u8":
-        from .preprocess import U8Tiles
-        table = U8Tiles.decode_table(x.device)
-    _launch("mil_pixel_step", ("pixel_step", x.numel(), rule, project, u8_out is not None), x.data_ptr(), g.data_ptr(), L.ptr(m), L.ptr(v),
-            L.ptr(u8_out), L.ptr(table), x.numel(), PIXEL_RULES.index(rule), PIXEL_PROJECTIONS.index(project), *scalars, L.stream_ptr())
-    return x
-
-
-def _stage_map(t, c, name):
-    """(n, h, w, cp, dtype code) of a stage output [T,h,w,cpad(c)], checked."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 4:
-        raise ValueError(f"{name} must be [T,h,w,cp], got {tuple(getattr(t, 'shape', ()))}")
-    n, h, w, cp = t.shape
-    if cp != cpad(c) or c < 1:
-        raise ValueError(f"{c} real channels go with {cpad(c)} stored ones, got {cp}")
-    if h < 1 or w < 1:
-        raise ValueError(f"maps of {h}x{w}")
-    code = L.dt_code(t.dtype)
-    _need(t, t.shape, t.dtype, name)
-    return n, h, w, cp, code
+    return _pixel_step_tail("mil_pixel_step", ("pixel_step", x.numel(), rule), x, g, (("m", m), ("v", v)), u8_out, project,
+                            PIXEL_RULES.index(rule), PIXEL_PROJECTIONS.index(project), *scalars)
 
 
 def stage_energy(target, c, *, energy=None):
@@ -1173,17 +1171,8 @@ def pixel_momentum_step(x, g, buf, *, lr, momentum=0.9, weight_decay=0.0, projec
     _pixel_stack(x, "x")
     if not isinstance(g, torch.Tensor) or not isinstance(buf, torch.Tensor):
         raise ValueError("g and buf must be fp32 tensors like x")
-    _need(x, x.shape, torch.float32, "x")
-    _need(g, x.shape, torch.float32, "g")
-    _need(buf, x.shape, torch.float32, "buf")
-    _need(u8_out, x.shape, torch.uint8, "u8_out")
-    table = None
-    if project == "u8":
-        from .preprocess import U8Tiles
-        table = U8Tiles.decode_table(x.device)
-    _launch("mil_pixel_momentum_step", ("pixel_momentum_step", x.numel(), project, u8_out is not None), x.data_ptr(), g.data_ptr(),
-            buf.data_ptr(), L.ptr(u8_out), L.ptr(table), x.numel(), PIXEL_PROJECTIONS.index(project), lr, wd, mo, L.stream_ptr())
-    return x
+    return _pixel_step_tail("mil_pixel_momentum_step", ("pixel_momentum_step", x.numel()), x, g, (("buf", buf),), u8_out, project,
+                            PIXEL_PROJECTIONS.index(project), lr, wd, mo)
 
 
 QUANTILE_GROUPS = ("tile", "bag")

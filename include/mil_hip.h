@@ -530,7 +530,10 @@ int mil_path_point(const void* tiles, int is_u8, float* out, float base0, float 
  *                       map_mode 2: max_c |acc_c| — reads no tiles (tiles may be NULL when it is the only output)
  *     tile_sum [n]    = the sum of attr over the tile, in a fixed order: each of MIL_ATTR_SLICES workgroups per tile sums its pixels
  *                       ((a0 + a1) + a2 per pixel) into ws [n * MIL_ATTR_SLICES] fp32, a second small launch adds a tile's partial
- *                       sums in slice order.  No atomics: two calls give the same bits
+ *                       sums in slice order.  No atomics: two calls give the same bits.  (This summation tree — a thread's items
+ *                       in order, the butterfly over the wave's 64 lanes, the four waves in order, the slices in order — is the
+ *                       one csrc/slice_sum.cuh implements for mil_attr_finish, mil_stage_seed, mil_stage_energy, mil_stage_match
+ *                       and mil_pixel_reg; tests/slice_sum_reference.py restates it and the GPU tests hold it bit for bit.)
  * tiles as for mil_path_point.  Null acc, no output, tiles NULL where they are read, tile_sum without ws, is_u8 outside {0,1},
  * map_mode outside {0,1,2}, n < 0, H or W < 1: MIL_ERR_ARG; n == 0: MIL_OK, no launch; 3 H W of 2^31 or more:
  * MIL_ERR_UNSUPPORTED — all decided on the host before any GPU call. */

@@ -100,6 +100,15 @@ def test_status_codes_are_decided_before_any_gpu_call():
     assert af(p, None, 0, 0, 0, 0, None, p, 2, None, None, 0, 8, 8, None) == 0     # the gradient's own map needs no tiles
     header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mil_hip.h")
     assert L.ATTR_SLICES == 32 and "#define MIL_ATTR_SLICES 32" in open(header).read()
+    # the three slice counts: the header, _lib.py, the one place the kernels define them, and the tree's numpy restatement
+    import glob
+    import slice_sum_reference as tree
+    csrc = glob.glob(os.path.join(os.path.dirname(header), "..", "*_amd", "csrc"))[0]
+    for name, value in (("ATTR", L.ATTR_SLICES), ("SEED", L.SEED_SLICES), ("REG", L.REG_SLICES)):
+        line = f"#define MIL_{name}_SLICES {value}"
+        assert line in open(header).read() and getattr(tree, f"{name}_SLICES") == value
+        sources = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cuh")))
+        assert [os.path.basename(f) for f in sources if line in open(f).read()] == ["slice_sum.cuh"]
 
 
 def test_wrappers_check_their_arguments_on_the_host():

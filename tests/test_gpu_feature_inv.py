@@ -12,6 +12,7 @@ import torch
 
 import feature_inv_reference as ref
 import feature_vis_reference as fv_ref
+import slice_sum_reference as tree
 from fixture_inputs import synth_bag
 from gpu_util import X3, cpad
 from oracle import mil_oracle as orc
@@ -117,6 +118,8 @@ def test_stage_match_and_energy_against_numpy(ops, c, hw, dtype):
           f"|loss - loss64| / loss64 {(l_err / l64).max():.2e} (bound {l_bound:.2e})")
     assert (e_err <= n * U * e64).all(), (e_err, n * U * e64)
     assert (l_err <= l_bound * l64).all(), (l_err, l64)
+    assert _same(energy, torch.from_numpy(tree.stage_energy(st, c)))              # the summation tree itself
+    assert _same(loss, torch.from_numpy(tree.stage_match_loss(sa, st, c, energy.cpu().numpy(), 0.1)))
     loss2, dz2 = ops.stage_match(act, target, c, weight=0.1)                      # fresh outputs, its own energy: the same bits
     assert _same(loss2, loss) and _same(dz2, dz) and _same(ops.stage_energy(target, c), energy)
 
@@ -127,7 +130,7 @@ REG_WEIGHTS = [(0.0, 0.25), (0.125, 0.0), (0.3, 0.7)]
 
 
 @pytest.mark.parametrize("alpha", [2, 6])
-@pytest.mark.parametrize("shape", REG_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", REG_SHAPES + [(1, 3, 96, 96)], ids=lambda s: "x".join(map(str, s)))
 def test_pixel_reg_bit_for_bit(ops, shape, alpha):
     """Every shift and weight combination of one shape and alpha on one x (values outside [-1, 1]).  (1,3,5,7) sits 4 bytes off
     the 16-byte grid and ends in a short group; (2,3,33,37)'s second tile starts off the grid; (1,3,1,9) is on the grid with a
@@ -136,7 +139,9 @@ def test_pixel_reg_bit_for_bit(ops, shape, alpha):
     terms.  n is the number of summed terms (3 H W powers; two squares per cell of the trimmed planes).  Each is >= 0, so the
     fixed-order fp32 sum lies within n u sum|terms| of the exact sum however it is bracketed, provided the terms' own roundings
     (alpha - 1 products; a difference, a square and the sum of two squares) plus the additions one term passes through stay below n:
-    the tightest case is (1,3,6,1) — 18 terms, one group of 4 per workgroup then 5 slices: 4 + 5 additions and 5 products."""
+    the tightest case is (1,3,6,1) — 18 terms, one group of 4 per workgroup then 5 slices: 4 + 5 additions and 5 products.
+    Beside the bound, the terms bit for bit against the summation tree itself; (1,3,96,96) gives a thread a second group
+    (432 groups per slice)."""
     _t, _c, H, W = shape
     misalign = shape == (1, 3, 5, 7)
     rng = np.random.default_rng(sum(shape) * 10 + alpha)
@@ -147,6 +152,7 @@ def test_pixel_reg_bit_for_bit(ops, shape, alpha):
     dx_, dg = _buffer(torch.from_numpy(x), misalign), _buffer(torch.from_numpy(g), misalign)
     kept = dx_.clone()
     t64 = ref.reg_terms64(x, alpha)
+    t32 = torch.from_numpy(tree.reg_terms(x, alpha))
     n_terms = np.array([3 * H * W, 2 * 3 * (H - 1) * (W - 1)], dtype=np.float64)[:, None]
     for shift in [(0, 0), (-3, 5), (H, W), (H + 1, -W - 2)]:
         for aw, tw in REG_WEIGHTS + [(0.0, 0.0)]:
@@ -157,6 +163,7 @@ def test_pixel_reg_bit_for_bit(ops, shape, alpha):
             assert _same(out, torch.from_numpy(want)), (shift, aw, tw)
             err = np.abs(terms.cpu().numpy().astype(np.float64) - t64)
             assert (err <= n_terms * U * t64).all(), (shift, aw, tw, err, n_terms * U * t64)
+            assert _same(terms, t32), (shift, aw, tw)
             plain = ops.pixel_reg(dx_, dg, None, alpha=alpha, alpha_weight=aw, tv_weight=tw, shift=shift)      # without terms
             assert _same(plain, out)
             if shift[0] % H == 0 and shift[1] % W == 0:                          # the aliased form: out is g

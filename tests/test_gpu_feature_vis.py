@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import feature_vis_reference as ref
+import slice_sum_reference as tree
 from fixture_inputs import synth_bag
 from gpu_util import X3, cpad
 from oracle import mil_oracle as orc
@@ -85,6 +86,7 @@ def test_stage_seed_against_numpy(ops, c, hw, dtype):
     err = np.abs(obj.cpu().numpy().astype(np.float64) - j64)
     print(f"stage_seed[c={c}, {h}x{w}, {dtype}]: |J - J64| {err.max():.2e}, bound {bound.min():.2e}")
     assert (err <= bound).all(), (err, bound)
+    assert _same(obj, torch.from_numpy(tree.stage_seed_objective(stored, chans)))  # the summation tree itself
     obj2, dz2 = ops.stage_seed(act, ch, c)                                       # fresh outputs, second run: the same bits
     assert _same(obj2, obj) and _same(dz2, dz)
 

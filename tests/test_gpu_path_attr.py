@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import path_attr_reference as ref
+import slice_sum_reference as tree
 from fixture_inputs import synth_bag
 from gpu_util import X3, rel_err, round_to, to_nhwc
 from oracle import mil_oracle as orc
@@ -208,7 +209,7 @@ def test_stem_dgrad_acc_is_acc_plus_scale_times_dx(ops, dtype, shape):
 
 
 # ---- attr_finish ---------------------------------------------------------------------------------------------------------------
-FINISH_SHAPES = [(1, 5, 7), (2, 33, 37), (2, 50, 70)]
+FINISH_SHAPES = [(1, 5, 7), (2, 33, 37), (2, 50, 70), (1, 192, 192)]        # the last: a thread takes a second group of four pixels
 
 
 @pytest.mark.parametrize("kind", ["f32", "u8"])
@@ -229,6 +230,7 @@ def test_attr_finish_against_the_cpu_fp32_restatement(ops, shape, kind):
     bound = 3 * h * w * 2.0 ** -24 * attr.double().cpu().abs().sum((1, 2, 3))
     print(f"attr_finish tile sums {shape} {kind}: error / bound {float(((sums.double().cpu() - s64).abs() / bound).max()):.3f}")
     assert bool(((sums.double().cpu() - s64).abs() <= bound).all())
+    assert np.array_equal(sums.cpu().numpy().view(np.int32), tree.attr_tile_sums(a.numpy()).view(np.int32))     # the summation tree itself
     # every subset of the outputs, every map mode: the same values, bit for bit (two launches included)
     for wa, wm, ws in itertools.product((False, True), repeat=3):
         if not (wa or wm or ws):
