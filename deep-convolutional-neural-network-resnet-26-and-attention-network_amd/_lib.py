@@ -26,6 +26,7 @@ FILTER_LANCZOS, FILTER_BILINEAR = 1, 2       # mil_resample_plan / _coeffs (Pill
 ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per tile in mil_attr_finish's workspace
 SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per tile in mil_stage_seed's workspace
 REG_SLICES = 16                              # MIL_REG_SLICES: partial sums per tile and norm in mil_pixel_reg's workspace
+OD_SLICES = 16                               # MIL_OD_SLICES: partial sums per tile in mil_od_moments_u8's workspace
 BLUR_MAX_RADIUS = 16                         # MIL_BLUR_MAX_RADIUS: the largest radius mil_pixel_blur takes
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
@@ -84,6 +85,9 @@ _SIGS = {
     "mil_roi_stats": ([_vp, _c.c_int64, _vp, _c.c_int64, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "mil_heatmap_render": ([_vp, _c.c_int64, _vp, _c.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp], _i),
     "mil_color_jitter_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
+    "mil_stain_affine_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_od_moments_u8": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp], _i),
+    "mil_od_project_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "mil_stem_fwd_fused_xs": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_stem_fwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_block_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -1252,6 +1252,107 @@ def attr_render(x, stats, mode="grayscale"):
     return (out0, out1) if mode == "pos_neg" else out0
 
 
+PROJECT_MODES = ("concentrations", "ratio")         # mil_od_project_u8's mode 0, 1
+_od_tables = {}                                     # device -> the 511 fp32 values on it
+
+
+def od_tables_host():
+    """The 511 fp32 values of the stain kernels' byte contract as numpy: L[v] = -ln((v + 1) / 256) for v = 0..255, then
+    TH[k] = -ln((k + 0.5) / 256) for k = 1..255 — `math.log` in fp64, rounded once to fp32."""
+    import math
+    import numpy as np
+    vals = [-math.log((v + 1) / 256.0) for v in range(256)] + [-math.log((k + 0.5) / 256.0) for k in range(1, 256)]
+    return np.asarray(vals, dtype=np.float64).astype(np.float32)
+
+
+def od_tables(device):
+    """`od_tables_host()` on `device`: uploaded once and cached per device (as `U8Tiles.decode_table` is)."""
+    dev = torch.device(device)
+    tab = _od_tables.get(dev)
+    if tab is None:
+        tab = _od_tables[dev] = torch.from_numpy(od_tables_host()).to(dev)
+    return tab
+
+
+def _u8_stack(u8, name="tiles"):
+    """(T, H, W) of a uint8 planar stack [T,3,H,W] on the GPU (what `U8Tiles.u8` is; a contiguous view at any byte offset)."""
+    if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[1] != 3:
+        raise ValueError(f"{name} must be a uint8 tensor [T,3,H,W], got {getattr(u8, 'dtype', type(u8).__name__)} "
+                         f"{tuple(getattr(u8, 'shape', ()))}")
+    t, _, h, w = u8.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"{name}: empty tiles {tuple(u8.shape)}")
+    if h * w > 2 ** 31 - 1 - 4096:
+        raise ValueError(f"{name}: tiles of {h} x {w} pixels are beyond 32-bit indexing")
+    _need(u8, u8.shape, torch.uint8, name)
+    return t, h, w
+
+
+def _beta(beta):
+    beta = float(beta)
+    if beta != beta:
+        raise ValueError("beta must be a number")
+    return beta
+
+
+def stain_affine(u8, affine):
+    """The OD-space affine map of `mil_stain_affine_u8` on the uint8 stack u8 [T,3,H,W], in place: affine fp32 [T,12] (per tile)
+    or [1,12] (one map for the stack), rows A[i,0..2], b[i]; on the host or on u8's device.  A non-finite entry is refused.
+    Returns u8."""
+    t, h, w = _u8_stack(u8)
+    if not isinstance(affine, torch.Tensor) or affine.dtype != torch.float32 or affine.dim() != 2 or affine.shape[1] != 12 \
+            or affine.shape[0] not in (1, t):
+        raise ValueError(f"affine must be fp32 [{t},12] or [1,12], got {getattr(affine, 'dtype', type(affine).__name__)} "
+                         f"{tuple(getattr(affine, 'shape', ()))}")
+    if not bool(torch.isfinite(affine).all()):
+        raise ValueError("affine holds a non-finite entry")
+    if t == 0:
+        return u8
+    shared = int(affine.shape[0] == 1)
+    affine = affine.to(u8.device).contiguous()
+    _launch("mil_stain_affine_u8", ("stain_affine", t, h, w, shared), u8.data_ptr(), affine.data_ptr(), od_tables(u8.device).data_ptr(),
+            t, h, w, shared, L.stream_ptr())
+    return u8
+
+
+def od_moments(u8, beta=0.15, group="tile"):
+    """Tissue statistics in OD space (see mil_od_moments_u8): fp64 [G,10] on the device = the count of tissue pixels (all three
+    of L[r], L[g], L[b] >= beta), sum od_c (r, g, b) and sum od_c od_d (rr, rg, rb, gg, gb, bb) per group — G = T for group
+    "tile", 1 for "bag".  Fixed summation tree: two calls give the same bits.  No host synchronisation."""
+    if group not in QUANTILE_GROUPS:
+        raise ValueError(f"group must be one of {QUANTILE_GROUPS}, got {group!r}")
+    beta = _beta(beta)
+    t, h, w = _u8_stack(u8)
+    bag = group == "bag"
+    out = torch.empty((1 if bag else t, 10), dtype=torch.float64, device=u8.device)
+    ws = torch.empty((max(t, 1) * L.OD_SLICES, 10), dtype=torch.float64, device=u8.device)
+    _launch("mil_od_moments_u8", ("od_moments", t, h, w, bag), u8.data_ptr(), od_tables(u8.device).data_ptr(), t, h, w, beta, int(bag),
+            ws.data_ptr(), ws.numel() * 8, out.data_ptr(), L.stream_ptr())
+    return out
+
+
+def od_project(u8, P, mode="concentrations", beta=0.15):
+    """Two projections of every pixel's OD as maps (see mil_od_project_u8): P [2,3] (rounded to fp32).  Returns (maps, valid):
+    mode "concentrations" — maps fp32 [2,T,H,W] = (p_0, p_1) at tissue pixels; mode "ratio" — maps fp32 [T,H,W] = p_1 / p_0 at
+    tissue pixels with p_0 > 0; +inf everywhere else.  valid int32 [T]: the pixels of each tile that got a value."""
+    if mode not in PROJECT_MODES:
+        raise ValueError(f"mode must be one of {PROJECT_MODES}, got {mode!r}")
+    beta = _beta(beta)
+    t, h, w = _u8_stack(u8)
+    P = torch.as_tensor(P).detach().to("cpu", torch.float64)
+    if tuple(P.shape) != (2, 3) or not bool(torch.isfinite(P).all()):
+        raise ValueError(f"P must hold 2 x 3 finite numbers, got {tuple(P.shape)}")
+    dev = u8.device
+    maps = torch.empty((2, t, h, w) if mode == "concentrations" else (t, h, w), dtype=torch.float32, device=dev)
+    valid = torch.empty((t,), dtype=torch.int32, device=dev)
+    if t == 0:
+        return maps, valid
+    pd = P.to(torch.float32).to(dev)
+    _launch("mil_od_project_u8", ("od_project", t, h, w, mode), u8.data_ptr(), od_tables(dev).data_ptr(), pd.data_ptr(), t, h, w,
+            PROJECT_MODES.index(mode), beta, maps.data_ptr(), valid.data_ptr(), L.stream_ptr())
+    return maps, valid
+
+
 def cam_overlay(tiles, map_u8, lut, alpha_byte):
     """(heat, on_image), two uint8 [T,H,W,3] (see mil_cam_overlay): the colour table `lut` (uint8 [256,3]) looked up at the map
     bytes `map_u8` [T,H,W], and Pillow's alpha_composite of that with alpha `alpha_byte` (0..255) over the `U8Tiles`."""

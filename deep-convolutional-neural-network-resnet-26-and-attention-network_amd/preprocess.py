@@ -150,17 +150,19 @@ class TilePreprocessor:
             self.kk_dev = torch.from_numpy(self.kk_host).to(dev)
         return self.bounds_dev, self.kk_dev
 
-    def __call__(self, rois, params=None, out="nchw", jitter=None):
+    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None):
         """rois: uint8 [T,S,S,3] on the GPU (the cached `data_cache` array).  params: int32 [T,4] from `draw_params`
         (train chain) or None (validation chain).  Returns fp32 [T,3,R,R] in [-1,1] (out="nchw": the reference's tensor), or
         — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
         — out="s2d" — as `S2dTiles` (bf16 space-to-depth: the bf16 compute mode only).  With either handle the fp32 stack is
         never materialised.  jitter: `ColorJitter.draw_params(T)` (or injected `JitterParams`) — the resized bytes are colour-
         jittered (RoiBuilder.py:200) before they are returned (out="u8") or decoded with `U8Tiles.float()` (out="nchw":
-        lossless, the values the fp32 chain makes of the jittered bytes); out="s2d" with a jitter raises ValueError."""
-        if jitter is not None:
+        lossless, the values the fp32 chain makes of the jittered bytes); out="s2d" with a jitter raises ValueError.  stain: a
+        `StainAffine` (one map, or one per tile) — the resized bytes go through it (`mil_stain_affine_u8`) BEFORE the colour
+        jitter; out as with a jitter."""
+        if jitter is not None or stain is not None:
             t = rois.shape[0] if isinstance(rois, torch.Tensor) and rois.dim() == 4 else -1      # -1: rois are refused below
-            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8"))
+            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8"), stain)
         self._check_out(out)
         if rois.dtype != torch.uint8 or rois.dim() != 4 or rois.shape[3] != 3 or rois.shape[1] != rois.shape[2]:
             raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(rois.shape)} {rois.dtype}")
@@ -183,16 +185,24 @@ class TilePreprocessor:
             done += n
         return S2dTiles(res) if out == "s2d" else U8Tiles(res) if out == "u8" else res
 
-    def _jittered(self, out, jitter, t, make_u8):
-        """`make_u8()` (this preprocessor's U8Tiles of `t` tiles) jittered with `jitter` and returned as `out` asks; the
-        jitter parameters and `out` are checked before anything is launched."""
+    def _jittered(self, out, jitter, t, make_u8, stain=None):
+        """`make_u8()` (this preprocessor's U8Tiles of `t` tiles) mapped with `stain`, then jittered with `jitter` (either may
+        be None), and returned as `out` asks; the parameters and `out` are checked before anything is launched."""
         from .color_jitter import apply_jitter, checked_params
+        from .stain import apply_stain, checked_affine
         self._check_out(out)
         if out == "s2d":
-            raise ValueError("the colour jitter works on the resized bytes: use out='u8' (or 'nchw')")
-        if t >= 0:
+            raise ValueError(f"the {'colour jitter' if jitter is not None else 'stain map'} works on the resized bytes: "
+                             "use out='u8' (or 'nchw')")
+        if stain is not None:
+            checked_affine(stain, t if t >= 0 else 1)
+        if jitter is not None and t >= 0:
             jitter = checked_params(jitter, t)
-        tiles = apply_jitter(make_u8(), jitter)
+        tiles = make_u8()
+        if stain is not None and len(tiles):
+            apply_stain(tiles, stain)
+        if jitter is not None:
+            apply_jitter(tiles, jitter)
         return tiles if out == "u8" else tiles.float()
 
     def _check_out(self, out):
@@ -220,16 +230,16 @@ class TilePreprocessor:
             return torch.empty((t, 3, r, r), dtype=torch.uint8, device=dev), "mil_tile_preprocess_u8"
         return torch.empty((t, 3, r, r), dtype=torch.float32, device=dev), "mil_tile_preprocess"
 
-    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None):
+    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None):
         """The same chains on windows of a slide that stays where it is (`array_read_region`, RoiBuilder.py:117-124, then
         :193-210): slide uint8 [H,W,3] on the GPU (any contiguous view, whatever its alignment), coords int [T,2] of (row, col)
         of `roi_size` windows.  No [T,S,S,3] stack is made: the kernel reads the windows in place (mil_tile_preprocess_win*).
         params / out / the return value as in `__call__`, bit for bit what `__call__` returns for the same windows copied into a
         stack.  A window outside the slide raises ValueError, a slide on the CPU RuntimeError, both before any launch.  With
-        coords=None `slide` is an ROI stack [n,S,S,3]: the same kernel at row pitch 3S.  jitter: as in `__call__`."""
-        if jitter is not None:
+        coords=None `slide` is an ROI stack [n,S,S,3]: the same kernel at row pitch 3S.  jitter, stain: as in `__call__`."""
+        if jitter is not None or stain is not None:
             t = int(source_windows(slide, coords, self.roi_size)[1].numel())
-            return self._jittered(out, jitter, t, lambda: self.from_slide(slide, coords, params, "u8"))
+            return self._jittered(out, jitter, t, lambda: self.from_slide(slide, coords, params, "u8"), stain)
         self._check_out(out)
         src, off, pitch = source_windows(slide, coords, self.roi_size)
         if not src.is_cuda:

@@ -18,13 +18,18 @@ class SlideBag:
     (RoiBuilder.py:230).  `selector`: a `RoiSelector` of the same roi_size (default: the reference's constants).  `coords`:
     a loaded `coor_cache`, int [T,2] of (row, col) — `build()` then has nothing to do.  `color_jitter`: a `ColorJitter` —
     `get_train_data` then jitters its tiles (RoiBuilder.py:200); validation and inference data never are.
+    `stain_normalizer`: a `StainNormalizer` — train, validation and inference tiles are mapped onto its target appearance with
+    the bag's own fit, made once, at first use, on an evenly strided subset of at most 256 of its windows taken through the flat
+    chain at the resolution of that moment, and kept as `stain_fit`.  `stain_jitter`: a `StainJitter` — train tiles only.  With
+    both, normalisation and jitter are composed into one `StainAffine`: one launch, one rounding to bytes, before the colour
+    jitter.
 
     Unlike the reference, a bag with no kept window returns an EMPTY stack [0,3,R,R] from the three `get_*` methods, not the
     `torch.zeros(20,3,128,128)` placeholder of RoiBuilder.py:236,257 (which has neither the bag's resolution nor any tile of
     it); the caller decides what to do with a slide without tissue."""
 
     def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None,
-                 color_jitter=None):
+                 color_jitter=None, *, stain_normalizer=None, stain_jitter=None):
         if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
             raise ValueError(f"expected a uint8 [H,W,3] slide, got {getattr(slide, 'dtype', type(slide))} "
                              f"{tuple(getattr(slide, 'shape', ()))}")
@@ -36,6 +41,8 @@ class SlideBag:
             raise ValueError(f"the selector cuts {self.selector.roi_size}-pixel windows, the bag {self.roi_size}-pixel ones")
         self.slide = slide
         self.color_jitter = color_jitter
+        self.stain_normalizer, self.stain_jitter = stain_normalizer, stain_jitter
+        self.stain_fit = None                                # the bag's StainFit once a stain_normalizer made it
         self.coords = None                                   # coor_cache: int64 [T,2] numpy (row, col) once built
         if coords is not None:
             c = np.asarray(coords.cpu() if isinstance(coords, torch.Tensor) else coords)
@@ -87,32 +94,54 @@ class SlideBag:
             raise ValueError(f"choice must hold {self.max_tiles} distinct indices below {n}")
         return idx
 
-    def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None):
+    def _stain(self, n, stain_jitter_params=None):
+        """The `StainAffine` the bag applies to a stack of `n` of its tiles (None: none): the normaliser's map with the bag's
+        fit — made here, once — followed by the stain jitter's per-tile maps, composed."""
+        if n == 0 or (self.stain_normalizer is None and stain_jitter_params is None):
+            return None
+        aff = None
+        if self.stain_normalizer is not None:
+            if self.stain_fit is None:
+                sub = self.coords[::-(-len(self.coords) // 256)]
+                self.stain_fit = self.stain_normalizer.fit(self.prep.from_slide(self.slide, sub, None, "u8"))
+            aff = self.stain_normalizer.affine(self.stain_fit)
+        if stain_jitter_params is not None:
+            jit = self.stain_jitter.affine(stain_jitter_params, n)
+            aff = jit if aff is None else aff.then(jit)
+        return aff
+
+    def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None, *, stain_jitter_params=None):
         """`get_train_data` (RoiBuilder.py:215-238): the cap of `choose`, then the train chain on the chosen windows with
         `draw_params(generator)` or the injected `params` [n,4].  A bag with a `color_jitter` then jitters the tiles with
         `color_jitter.draw_params(n, generator)` (drawn after the crop / flip parameters) or the injected `jitter_params`;
-        a bag without one refuses `jitter_params`."""
+        a bag without one refuses `jitter_params`.  A bag with a `stain_jitter` draws `stain_jitter.draw_params(n, generator)`
+        after those (or takes the injected `stain_jitter_params`); the stain map comes before the colour jitter.  A bag
+        without one refuses `stain_jitter_params`."""
         self._ready()
         if jitter_params is not None and self.color_jitter is None:
             raise ValueError("jitter_params given to a bag made without color_jitter=")
+        if stain_jitter_params is not None and self.stain_jitter is None:
+            raise ValueError("stain_jitter_params given to a bag made without stain_jitter=")
         idx = self.choose(generator, choice)
         c = self.coords if idx is None else self.coords[idx]
         if params is None:
             params = self.prep.draw_params(len(c), generator)
         if self.color_jitter is not None and jitter_params is None:
             jitter_params = self.color_jitter.draw_params(len(c), generator)
-        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params)
+        if self.stain_jitter is not None and stain_jitter_params is None and len(c):
+            stain_jitter_params = self.stain_jitter.draw_params(len(c), generator)
+        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params))
 
     def get_validation_data(self, out="u8"):
         """`get_validation_data` (RoiBuilder.py:240-259): the flat chain on every kept window."""
         self._ready()
-        return self.prep.from_slide(self.slide, self.coords, None, out)
+        return self.prep.from_slide(self.slide, self.coords, None, out, stain=self._stain(len(self.coords)))
 
     def get_inference_data(self, out="u8"):
         """`get_inference_data` (RoiBuilder.py:261-284): (tiles of the flat chain, their coordinates).  The reference's third
         item, the ROIs themselves (for `imshow` in its `visualize`), is `rois(indices)` for the ones that are drawn."""
         self._ready()
-        return self.prep.from_slide(self.slide, self.coords, None, out), self.coords.copy()
+        return self.prep.from_slide(self.slide, self.coords, None, out, stain=self._stain(len(self.coords))), self.coords.copy()
 
     def attention_maps(self, output, scale, features=True, **renderer_args):
         """The five tissue panels of the reference's `visualize` -> `create_map` (gbm/classify_combined.py:142-218) for one

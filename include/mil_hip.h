@@ -312,6 +312,47 @@ int mil_heatmap_render(const uint8_t* base, int64_t base_bytes, const int64_t* w
 int mil_color_jitter_u8(uint8_t* tiles, const int32_t* order, const float* factors, const int32_t* hue_shift, uint32_t* lsum,
                         int T, int R, void* stream);
 
+/* H&E stain handling for the same resized tiles, uint8 [T,3,H,W] planar (H != W allowed; a plane may start at any byte
+ * alignment): the affine map in optical-density (OD) space that stain normalisation (Macenko et al. 2009) and stain augmentation
+ * (Tellez et al. 2018) both are, and the two reductions a Macenko fit needs.  tables (511 floats, DEVICE; mil_amd.ops.od_tables
+ * builds them on the host in fp64 with log and rounds once):
+ *     tables[v]       = L[v]  = -ln((v + 1) / 256),   v = 0..255   the OD of a byte, L[255] = 0
+ *     tables[255 + k] = TH[k] = -ln((k + 0.5) / 256), k = 1..255   strictly decreasing: where the byte goes from k - 1 to k
+ *     byte(o)         = #{k : o <= TH[k]}     255 for o <= TH[255], 0 for o > TH[1] (and for a NaN), a tie goes to the brighter byte
+ * No exp decides a byte on the device: the kernel finds the count by comparisons against TH (from a guess), so
+ * np.searchsorted on the same table gives the same bytes, and byte(L[v]) == v: the identity map returns its input.
+ *
+ * mil_stain_affine_u8: in place, per pixel and output channel i, with affine[t] (float [T,12], or [1,12] with shared = 1) holding
+ * the rows A[i,0], A[i,1], A[i,2], b[i]:
+ *     o_i = ((A[i,0] L[r] + A[i,1] L[g]) + A[i,2] L[b]) + b_i     every product and sum rounded once, in that order; no FMA
+ * and byte(o_i) is stored; the three bytes of a pixel are read before any is written.  One pointwise launch (65535 tiles each):
+ * four consecutive pixels of a plane per access, as one dword where the address lies on the 4-byte grid, byte by byte otherwise;
+ * no access leaves a plane.
+ *
+ * mil_od_moments_u8: a pixel is TISSUE when L[r], L[g], L[b] are all >= beta.  out (double [groups,10]; a group is a tile, bag 0,
+ * or the whole stack, bag 1) = the tissue count, sum od_c (3), sum od_c od_d for c <= d (rr, rg, rb, gg, gb, bb): the terms are
+ * exact in fp64 and are added one rounded addition at a time in a fixed tree — slice s of MIL_OD_SLICES of a tile owns a run of
+ * ceil(ceil(H W / 4) / MIL_OD_SLICES) four-pixel groups; a thread of 256 adds its groups (every 256th) in order, the 64 lanes of
+ * a wave by a butterfly, the four waves in order; then a tile's slices in order (bag 0) or, in ONE workgroup, thread i the
+ * slice sums i, i + 256, ... of the stack in order and the same wave / workgroup tree (bag 1).  No floating-point atomics: two
+ * calls give the same bits.  workspace: T * MIL_OD_SLICES * 10 doubles.  T == 0 with bag 1 writes ten zeros.
+ *
+ * mil_od_project_u8: with P (float [2,3], DEVICE), p_k = (P[k,0] L[r] + P[k,1] L[g]) + P[k,2] L[b], rounded as above,
+ *     mode 0  concentrations   maps [2,T,H,W]: maps[0] = p_0, maps[1] = p_1 at tissue pixels
+ *     mode 1  ratio            maps [T,H,W] = p_1 / p_0 (IEEE division) at tissue pixels with p_0 > 0
+ * every other pixel gets +inf (the division is not evaluated there); valid[t] (int32 [T]; the call zeroes it) counts tile t's
+ * pixels that got a value (integer atomics).  +inf sorts above every value in mil_map_quantile.
+ *
+ * All three: null pointers, T < 0, H or W < 1, shared / bag / mode outside {0,1}, beta NaN, a workspace too small: MIL_ERR_ARG;
+ * H W > 2^31 - 1 - 4096 (or T * MIL_OD_SLICES beyond 32 bits): MIL_ERR_UNSUPPORTED; T == 0: MIL_OK, no launch — all decided on
+ * the host before any GPU call. */
+#define MIL_OD_SLICES 16
+int mil_stain_affine_u8(uint8_t* tiles, const float* affine, const float* tables, int T, int H, int W, int shared, void* stream);
+int mil_od_moments_u8(const uint8_t* tiles, const float* tables, int T, int H, int W, float beta, int bag, double* workspace,
+                      size_t workspace_bytes, double* out, void* stream);
+int mil_od_project_u8(const uint8_t* tiles, const float* tables, const float* P, int T, int H, int W, int mode, float beta,
+                      float* maps, int32_t* valid, void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
