@@ -13,6 +13,7 @@ from .slide_bag import SlideBag  # noqa: F401
 from .heatmap import AttentionMapRenderer  # noqa: F401
 from .color_jitter import ColorJitter  # noqa: F401
 from .stain import HED, StainAffine, StainFit, StainJitter, StainNormalizer  # noqa: F401
+from .affine import RandomAffine, affine_matrix, quarter_turn_matrix  # noqa: F401
 from .model import Attention, ContextLayer, CrossEntropyWithProbs, TileParallel  # noqa: F401
 from .summary import ActivationSummary, parameter_stats, tensor_stats  # noqa: F401
 from .saliency import TileSaliency  # noqa: F401
@@ -28,4 +29,5 @@ __all__ = ["alt_resnet", "Attention", "ResNet", "BasicResBlock", "ContextLayer",
            "FlatParams", "FlatAdam", "shard_bags", "gather_features", "BagTrainer", "set_stage", "stage_for_epoch", "write_attention_map", "write_map", "visualize_terms", "save_checkpoint", "load_checkpoint", "TilePreprocessor", "S2dTiles", "U8Tiles", "RoiSelector", "SlideBag", "AttentionMapRenderer", "ColorJitter", "build_library", "lib", "MilLibraryError", "LIB_PATH", "BF16X3", "invalidate_packed_weights",
            "ActivationSummary", "parameter_stats", "tensor_stats", "TileSaliency", "TileGradCam", "TileIntegratedGradients", "TileSmoothGrad", "AttributionRenderer",
            "AttributionMosaic", "FeatureVisualizer", "FeatureVisResult", "FeatureInverter", "InversionResult", "PixelRegularizer", "gaussian_blur",
-           "TileGuidedBackprop", "TileGuidedGradCam", "HED", "StainAffine", "StainFit", "StainJitter", "StainNormalizer"]
+           "TileGuidedBackprop", "TileGuidedGradCam", "HED", "StainAffine", "StainFit", "StainJitter", "StainNormalizer",
+           "RandomAffine", "affine_matrix", "quarter_turn_matrix"]

@@ -1353,6 +1353,103 @@ def od_project(u8, P, mode="concentrations", beta=0.15):
     return maps, valid
 
 
+def affine_matrices(matrices, n, name="matrices"):
+    """`matrices` (a tensor, an array or nested lists) as a contiguous float64 [n,6] host tensor; ValueError for another shape,
+    a non-numeric dtype or a non-finite entry.  Needs no device."""
+    try:
+        m = torch.as_tensor(matrices).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must be float64 [{n},6]") from None
+    if m.dtype == torch.bool or m.is_complex() or tuple(m.shape) != (n, 6):
+        raise ValueError(f"{name} must be float64 [{n},6], got {tuple(m.shape)} {m.dtype}")
+    m = m.to(torch.float64).contiguous()
+    if not bool(torch.isfinite(m).all()):
+        raise ValueError(f"{name} holds a non-finite entry")
+    return m
+
+
+def affine_fill(fill):
+    """A fill colour, one byte or three, as mil_affine_u8 takes it: r | g << 8 | b << 16.  ValueError otherwise."""
+    import numbers
+    vals = (fill,) * 3 if isinstance(fill, numbers.Integral) and not isinstance(fill, bool) else fill
+    if not isinstance(vals, (tuple, list)) or len(vals) != 3 or any(
+            not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 0 <= v <= 255 for v in vals):
+        raise ValueError(f"fill must be a byte or three bytes, got {fill!r}")
+    return int(vals[0]) | int(vals[1]) << 8 | int(vals[2]) << 16
+
+
+def _affine_hw(out_hw, h, w):
+    if out_hw is None:
+        return h, w
+    try:
+        oh, ow = (int(v) for v in out_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"out_hw must be (height, width), got {out_hw!r}") from None
+    if oh < 1 or ow < 1 or oh * ow > 2 ** 31 - 1 - 4096:
+        raise ValueError(f"out_hw must be positive and within 32-bit indexing, got {out_hw!r}")
+    return oh, ow
+
+
+def affine_u8(src, matrices, fill=0, out_hw=None):
+    """Pillow's bilinear `Image.transform(size, Image.AFFINE, m, Image.BILINEAR, fillcolor=fill)` of every tile of the planar
+    uint8 stack src [n,3,h,w], bit for bit (see mil_affine_u8): matrices float64 [n,6], the map from output pixel centres to
+    input coordinates, one per tile; fill a byte or three; out_hw the output size (default: the input's).  Returns a NEW uint8
+    [n,3,oh,ow] on src's device.  Every refusal comes before the launch."""
+    n, h, w = _u8_stack(src, "src")
+    oh, ow = _affine_hw(out_hw, h, w)
+    m = affine_matrices(matrices, n)
+    fill = affine_fill(fill)
+    out = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=src.device)
+    if n:
+        md = m.to(src.device)
+        _launch("mil_affine_u8", ("affine_u8", n, h, w, oh, ow), src.data_ptr(), 3 * h * w, w, 1, h * w, w, h, out.data_ptr(), 1, oh * ow,
+                ow, oh, md.data_ptr(), fill, n, L.stream_ptr())
+    return out
+
+
+def affine_windows_u8(source, coords, matrices, fill=0, size=None):
+    """The window form of `affine_u8`, interleaved: source a uint8 slide [H,W,3] with coords (int [n,2] of (row, col), the
+    origins of S x S windows, S = `size`) or an ROI stack [n,S,S,3] with coords=None (`size` is then not needed); matrices
+    float64 [n,6] in WINDOW coordinates.  Returns a NEW uint8 [n,S,S,3].  For a slide every window reads the slide itself — the host adds the window's
+    origin to the matrix (a2 + col, a5 + row: one double addition each), W, H and the clips are the slide's — so a rotated
+    window shows the tissue that lies beside it, and only what lies outside the slide becomes `fill`:
+    `Image.fromarray(slide).transform((S, S), Image.AFFINE, m', Image.BILINEAR, fillcolor=fill)`.  For a stack the source of a
+    window is the window, and what lies outside it is `fill`.  Every refusal comes before the launch."""
+    from .preprocess import source_windows
+    if coords is None:
+        if not isinstance(source, torch.Tensor) or source.dim() != 4:
+            raise ValueError("without coords the source is an ROI stack [n,S,S,3]")
+        s = int(source.shape[1]) if size is None else int(size)
+        src, off, _ = source_windows(source, None, s)
+        origins = None
+    else:
+        if size is None or int(size) < 1:
+            raise ValueError("windows of a slide need their size (a positive number of pixels)")
+        s = int(size)
+        src, off, _ = source_windows(source, coords, s)
+        width = int(src.shape[1])
+        origins = torch.stack([off // 3 % width, off // 3 // width], dim=1).to(torch.float64)          # (col, row)
+    n = int(off.numel())
+    m = affine_matrices(matrices, n)
+    fill = affine_fill(fill)
+    if not src.is_cuda:
+        raise RuntimeError("the affine transform runs on an AMD GPU only (no CPU fallback)")
+    out = torch.empty((n, s, s, 3), dtype=torch.uint8, device=src.device)
+    if n == 0:
+        return out
+    if origins is None:
+        tile, width, height = 3 * s * s, s, s
+    else:
+        m = m.clone()
+        m[:, 2] += origins[:, 0]
+        m[:, 5] += origins[:, 1]
+        tile, height = 0, int(src.shape[0])
+    md = m.to(src.device)
+    _launch("mil_affine_u8", ("affine_windows_u8", n, s, tile == 0), src.data_ptr(), tile, 3 * width, 3, 1, width, height,
+            out.data_ptr(), 3, 1, s, s, md.data_ptr(), fill, n, L.stream_ptr())
+    return out
+
+
 def cam_overlay(tiles, map_u8, lut, alpha_byte):
     """(heat, on_image), two uint8 [T,H,W,3] (see mil_cam_overlay): the colour table `lut` (uint8 [256,3]) looked up at the map
     bytes `map_u8` [T,H,W], and Pillow's alpha_composite of that with alpha `alpha_byte` (0..255) over the `U8Tiles`."""

@@ -11,6 +11,8 @@ import torch
 
 from . import _lib as L
 
+AFFINE_CHUNK = 64       # windows per rotated stack of the `affine=` path: bounds the intermediate at AFFINE_CHUNK * 3 S^2 bytes
+
 
 class S2dTiles:
     """A stack of tiles held as the bf16 space-to-depth tensor the stem kernels read, `xs [T, R/2, R/2, 16]` (channel =
@@ -150,7 +152,7 @@ class TilePreprocessor:
             self.kk_dev = torch.from_numpy(self.kk_host).to(dev)
         return self.bounds_dev, self.kk_dev
 
-    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None):
+    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0):
         """rois: uint8 [T,S,S,3] on the GPU (the cached `data_cache` array).  params: int32 [T,4] from `draw_params`
         (train chain) or None (validation chain).  Returns fp32 [T,3,R,R] in [-1,1] (out="nchw": the reference's tensor), or
         — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
@@ -159,10 +161,16 @@ class TilePreprocessor:
         jittered (RoiBuilder.py:200) before they are returned (out="u8") or decoded with `U8Tiles.float()` (out="nchw":
         lossless, the values the fp32 chain makes of the jittered bytes); out="s2d" with a jitter raises ValueError.  stain: a
         `StainAffine` (one map, or one per tile) — the resized bytes go through it (`mil_stain_affine_u8`) BEFORE the colour
-        jitter; out as with a jitter."""
+        jitter; out as with a jitter.  affine: float64 [T,6], one matrix per ROI in its own coordinates (`RandomAffine.draw_params(T,
+        roi_size)`) — every ROI is first transformed as Pillow's `transform((S, S), AFFINE, m, BILINEAR, fillcolor=affine_fill)`
+        does it (what lies outside the ROI becomes `affine_fill`, a byte or three), then goes through the chain above."""
         if jitter is not None or stain is not None:
             t = rois.shape[0] if isinstance(rois, torch.Tensor) and rois.dim() == 4 else -1      # -1: rois are refused below
-            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8"), stain)
+            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8", affine=affine, affine_fill=affine_fill), stain)
+        if affine is not None:
+            if not isinstance(rois, torch.Tensor) or rois.dim() != 4:
+                raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(getattr(rois, 'shape', ()))}")
+            return self._transformed(rois, None, params, out, affine, affine_fill)
         self._check_out(out)
         if rois.dtype != torch.uint8 or rois.dim() != 4 or rois.shape[3] != 3 or rois.shape[1] != rois.shape[2]:
             raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(rois.shape)} {rois.dtype}")
@@ -205,6 +213,35 @@ class TilePreprocessor:
             apply_jitter(tiles, jitter)
         return tiles if out == "u8" else tiles.float()
 
+    def _transformed(self, source, coords, params, out, affine, fill):
+        """The `affine=` path of `__call__` (coords None) and `from_slide`: the windows transformed with `ops.affine_windows_u8`
+        in stacks of at most AFFINE_CHUNK, each handed to `__call__`; no array of T * S^2 pixels exists.  Everything is checked
+        before the first launch."""
+        from . import ops
+        self._check_out(out)
+        src, off, _ = source_windows(source, coords, self.roi_size)
+        t = int(off.numel())
+        m = ops.affine_matrices(affine, t, "affine")
+        ops.affine_fill(fill)
+        if not src.is_cuda:
+            raise RuntimeError("tile pre-processing runs on an AMD GPU only (no CPU fallback)")
+        params = self._params(params, t, src.device)
+        if coords is not None:
+            width = int(src.shape[1])
+            coords = torch.stack([off // 3 // width, off // 3 % width], dim=1)                    # (row, col), int64
+        parts = []
+        for lo in range(0, t, AFFINE_CHUNK):
+            hi = min(t, lo + AFFINE_CHUNK)
+            if coords is None:
+                win = ops.affine_windows_u8(src[lo:hi], None, m[lo:hi], fill)
+            else:
+                win = ops.affine_windows_u8(src, coords[lo:hi], m[lo:hi], fill, self.roi_size)
+            parts.append(self(win, None if params is None else params[lo:hi], out))
+        if not parts:
+            res = self._result(out, 0, src.device)[0]
+            return S2dTiles(res) if out == "s2d" else U8Tiles(res) if out == "u8" else res
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0) if out == "nchw" else type(parts[0]).cat(parts)
+
     def _check_out(self, out):
         if out not in ("nchw", "s2d", "u8"):
             raise ValueError("out must be 'nchw', 's2d' or 'u8'")
@@ -230,16 +267,25 @@ class TilePreprocessor:
             return torch.empty((t, 3, r, r), dtype=torch.uint8, device=dev), "mil_tile_preprocess_u8"
         return torch.empty((t, 3, r, r), dtype=torch.float32, device=dev), "mil_tile_preprocess"
 
-    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None):
+    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0):
         """The same chains on windows of a slide that stays where it is (`array_read_region`, RoiBuilder.py:117-124, then
         :193-210): slide uint8 [H,W,3] on the GPU (any contiguous view, whatever its alignment), coords int [T,2] of (row, col)
         of `roi_size` windows.  No [T,S,S,3] stack is made: the kernel reads the windows in place (mil_tile_preprocess_win*).
         params / out / the return value as in `__call__`, bit for bit what `__call__` returns for the same windows copied into a
         stack.  A window outside the slide raises ValueError, a slide on the CPU RuntimeError, both before any launch.  With
-        coords=None `slide` is an ROI stack [n,S,S,3]: the same kernel at row pitch 3S.  jitter, stain: as in `__call__`."""
+        coords=None `slide` is an ROI stack [n,S,S,3]: the same kernel at row pitch 3S.  jitter, stain: as in `__call__`.
+        affine: float64 [T,6], one matrix per window in WINDOW coordinates (`RandomAffine.draw_params(T, roi_size)`).  Every
+        window is first transformed — reading the SLIDE, so a rotated window shows the tissue beside it and only what lies
+        outside the slide becomes `affine_fill` —, then goes through the chain: bit for bit
+        `Image.fromarray(slide).transform((S, S), Image.AFFINE, m + origin, Image.BILINEAR, fillcolor=affine_fill)` followed by
+        `__call__` on those windows (origin: col added to a2, row to a5).  The transformed windows are made AFFINE_CHUNK at a
+        time."""
         if jitter is not None or stain is not None:
             t = int(source_windows(slide, coords, self.roi_size)[1].numel())
-            return self._jittered(out, jitter, t, lambda: self.from_slide(slide, coords, params, "u8"), stain)
+            return self._jittered(out, jitter, t,
+                                  lambda: self.from_slide(slide, coords, params, "u8", affine=affine, affine_fill=affine_fill), stain)
+        if affine is not None:
+            return self._transformed(slide, coords, params, out, affine, affine_fill)
         self._check_out(out)
         src, off, pitch = source_windows(slide, coords, self.roi_size)
         if not src.is_cuda:

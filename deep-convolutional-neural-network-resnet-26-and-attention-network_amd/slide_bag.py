@@ -22,14 +22,16 @@ class SlideBag:
     the bag's own fit, made once, at first use, on an evenly strided subset of at most 256 of its windows taken through the flat
     chain at the resolution of that moment, and kept as `stain_fit`.  `stain_jitter`: a `StainJitter` — train tiles only.  With
     both, normalisation and jitter are composed into one `StainAffine`: one launch, one rounding to bytes, before the colour
-    jitter.
+    jitter.  `affine`: a `RandomAffine` — every window of `get_train_data` is rotated / sheared / scaled / shifted about its
+    centre BEFORE the train chain, reading the slide itself (the tissue beside the window, not a fill colour, fills the corners;
+    only what lies outside the slide gets `affine.fill`); validation and inference data never are.
 
     Unlike the reference, a bag with no kept window returns an EMPTY stack [0,3,R,R] from the three `get_*` methods, not the
     `torch.zeros(20,3,128,128)` placeholder of RoiBuilder.py:236,257 (which has neither the bag's resolution nor any tile of
     it); the caller decides what to do with a slide without tissue."""
 
     def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None,
-                 color_jitter=None, *, stain_normalizer=None, stain_jitter=None):
+                 color_jitter=None, *, stain_normalizer=None, stain_jitter=None, affine=None):
         if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
             raise ValueError(f"expected a uint8 [H,W,3] slide, got {getattr(slide, 'dtype', type(slide))} "
                              f"{tuple(getattr(slide, 'shape', ()))}")
@@ -42,6 +44,7 @@ class SlideBag:
         self.slide = slide
         self.color_jitter = color_jitter
         self.stain_normalizer, self.stain_jitter = stain_normalizer, stain_jitter
+        self.affine = affine
         self.stain_fit = None                                # the bag's StainFit once a stain_normalizer made it
         self.coords = None                                   # coor_cache: int64 [T,2] numpy (row, col) once built
         if coords is not None:
@@ -110,14 +113,20 @@ class SlideBag:
             aff = jit if aff is None else aff.then(jit)
         return aff
 
-    def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None, *, stain_jitter_params=None):
+    def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None, *, stain_jitter_params=None,
+                       affine_params=None):
         """`get_train_data` (RoiBuilder.py:215-238): the cap of `choose`, then the train chain on the chosen windows with
         `draw_params(generator)` or the injected `params` [n,4].  A bag with a `color_jitter` then jitters the tiles with
         `color_jitter.draw_params(n, generator)` (drawn after the crop / flip parameters) or the injected `jitter_params`;
         a bag without one refuses `jitter_params`.  A bag with a `stain_jitter` draws `stain_jitter.draw_params(n, generator)`
         after those (or takes the injected `stain_jitter_params`); the stain map comes before the colour jitter.  A bag
-        without one refuses `stain_jitter_params`."""
+        without one refuses `stain_jitter_params`.  A bag with an `affine` draws `affine.draw_params(n, roi_size, generator)`
+        LAST, after every draw above (seeded sequences of bags without one do not move), or takes the injected `affine_params`
+        (float64 [n,6], window coordinates); the windows are transformed before the train chain.  A bag without one refuses
+        `affine_params`."""
         self._ready()
+        if affine_params is not None and self.affine is None:
+            raise ValueError("affine_params given to a bag made without affine=")
         if jitter_params is not None and self.color_jitter is None:
             raise ValueError("jitter_params given to a bag made without color_jitter=")
         if stain_jitter_params is not None and self.stain_jitter is None:
@@ -130,7 +139,12 @@ class SlideBag:
             jitter_params = self.color_jitter.draw_params(len(c), generator)
         if self.stain_jitter is not None and stain_jitter_params is None and len(c):
             stain_jitter_params = self.stain_jitter.draw_params(len(c), generator)
-        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params))
+        if self.affine is None:
+            return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params))
+        if affine_params is None:
+            affine_params = self.affine.draw_params(len(c), self.roi_size, generator)
+        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params),
+                                    affine=affine_params, affine_fill=self.affine.fill)
 
     def get_validation_data(self, out="u8"):
         """`get_validation_data` (RoiBuilder.py:240-259): the flat chain on every kept window."""

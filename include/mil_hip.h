@@ -353,6 +353,41 @@ int mil_od_moments_u8(const uint8_t* tiles, const float* tables, int T, int H, i
 int mil_od_project_u8(const uint8_t* tiles, const float* tables, const float* P, int T, int H, int W, int mode, float beta,
                       float* maps, int32_t* valid, void* stream);
 
+/* Rotation / affine augmentation of uint8 RGB images: torchvision's RandomAffine / RandomRotation as its PIL backend computes
+ * them, Image.transform(size, Image.AFFINE, m, Image.BILINEAR, fillcolor=fill), bit for bit Pillow's bytes.  matrices (double
+ * [n,6], DEVICE) holds a0..a5 per image: the map from OUTPUT pixel centres to INPUT coordinates.  For a source of W x H pixels
+ * and output pixel (x, y), each channel separately, in IEEE double with every operation rounded once in the order written (no
+ * FMA):
+ *     xs = x + 0.5 ; ys = y + 0.5
+ *     xin = (a0*xs + a1*ys) + a2          yin = (a3*xs + a4*ys) + a5
+ *     not (0 <= xin < W and 0 <= yin < H):  out = fill   (all channels; a NaN coordinate counts as outside)
+ *     xf = xin - 0.5 ; yf = yin - 0.5 ; X = floor(xf) ; Y = floor(yf) ; dx = xf - X ; dy = yf - Y
+ *     x0 = clip(X, 0, W-1) ; x1 = clip(X+1, 0, W-1) ; y0 = clip(Y, 0, H-1)
+ *     v1 = p[y0][x0] + (p[y0][x1] - p[y0][x0]) * dx
+ *     v2 = p[Y+1][x0] + (p[Y+1][x1] - p[Y+1][x0]) * dx   if 0 <= Y+1 < H   else v1
+ *     out = (uint8) trunc( v1 + (v2 - v1) * dy )
+ * Bilinear only (Pillow's NEAREST is a separate 16.16 fixed-point path).  Integer matrix entries give dx = dy = 0: a bit copy,
+ * so the quarter turns come out of the same kernel.
+ *
+ * Addressing, in bytes.  Channel c of source pixel (xx, yy) of image t is
+ *     src[t * src_tile_stride + yy * src_row_stride + xx * src_pix_stride + c * src_chan_stride]       (64-bit products)
+ * and channel c of output pixel number i = y * ow + x of image t is
+ *     dst[t * 3 * ow * oh + i * dst_pix_stride + c * dst_chan_stride]
+ * (the destination is a dense stack of n images of 3 * ow * oh bytes).  The layouts in use:
+ *     planar       [n,3,H,W] -> [n,3,oh,ow]   src (3HW, W, 1, HW),    dst (1, ow*oh)
+ *     interleaved  [n,H,W,3] -> [n,oh,ow,3]   src (3HW, 3W, 3, 1),    dst (3, 1)
+ *     slide        [H,W,3]   -> [n,oh,ow,3]   src (0,   3W, 3, 1),    dst (3, 1): every window reads the SAME image, the caller
+ *                  adds the window's origin (col, row) to (a2, a5); what lies outside the slide, and only that, becomes fill
+ * Four consecutive output pixels per thread: one dword per plane (dst_pix_stride 1) or three consecutive dwords (dst strides
+ * (3, 1)) at any byte alignment, byte stores for the last, partial group of an image and for any other strides.  No access
+ * leaves the source image or the destination stack.  fill_rgb = r | g << 8 | b << 16.
+ * Null pointers, n < 0, W / H / ow / oh < 1, a negative src_tile_stride, any other stride < 1: MIL_ERR_ARG; ow * oh >
+ * 2^31 - 1 - 1024: MIL_ERR_UNSUPPORTED; n == 0: MIL_OK, no launch — all decided on the host before any GPU call.  Any n
+ * (launches of 65535 images). */
+int mil_affine_u8(const uint8_t* src, int64_t src_tile_stride, int64_t src_row_stride, int64_t src_pix_stride,
+                  int64_t src_chan_stride, int W, int H, uint8_t* dst, int64_t dst_pix_stride, int64_t dst_chan_stride, int ow, int oh,
+                  const double* matrices, uint32_t fill_rgb, int n, void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
