@@ -14,6 +14,7 @@ from .heatmap import AttentionMapRenderer  # noqa: F401
 from .color_jitter import ColorJitter  # noqa: F401
 from .stain import HED, StainAffine, StainFit, StainJitter, StainNormalizer  # noqa: F401
 from .affine import RandomAffine, affine_matrix, quarter_turn_matrix  # noqa: F401
+from .elastic import ElasticDeform  # noqa: F401
 from .model import Attention, ContextLayer, CrossEntropyWithProbs, TileParallel  # noqa: F401
 from .summary import ActivationSummary, parameter_stats, tensor_stats  # noqa: F401
 from .saliency import TileSaliency  # noqa: F401
@@ -30,4 +31,4 @@ __all__ = ["alt_resnet", "Attention", "ResNet", "BasicResBlock", "ContextLayer",
            "ActivationSummary", "parameter_stats", "tensor_stats", "TileSaliency", "TileGradCam", "TileIntegratedGradients", "TileSmoothGrad", "AttributionRenderer",
            "AttributionMosaic", "FeatureVisualizer", "FeatureVisResult", "FeatureInverter", "InversionResult", "PixelRegularizer", "gaussian_blur",
            "TileGuidedBackprop", "TileGuidedGradCam", "HED", "StainAffine", "StainFit", "StainJitter", "StainNormalizer",
-           "RandomAffine", "affine_matrix", "quarter_turn_matrix"]
+           "RandomAffine", "affine_matrix", "quarter_turn_matrix", "ElasticDeform"]

@@ -89,6 +89,8 @@ _SIGS = {
     "mil_od_moments_u8": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp], _i),
     "mil_od_project_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "mil_affine_u8": ([_vp] + [_c.c_int64] * 4 + [_i, _i, _vp, _c.c_int64, _c.c_int64, _i, _i, _vp, _c.c_uint32, _i, _vp], _i),
+    "mil_affine_elastic_u8": ([_vp] + [_c.c_int64] * 4 + [_i, _i, _vp, _c.c_int64, _c.c_int64, _i, _i, _vp, _c.c_uint32, _i,
+                               _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "mil_stem_fwd_fused_xs": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_stem_fwd_fused_u8": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),
     "mil_conv_block_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _i),

@@ -1254,6 +1254,7 @@ def attr_render(x, stats, mode="grayscale"):
 
 PROJECT_MODES = ("concentrations", "ratio")         # mil_od_project_u8's mode 0, 1
 _od_tables = {}                                     # device -> the 511 fp32 values on it
+_elastic_tables = {}                                # (size, cells, device) -> (idx, w) of `elastic_tables` on it
 
 
 def od_tables_host():
@@ -1447,6 +1448,133 @@ def affine_windows_u8(source, coords, matrices, fill=0, size=None):
     md = m.to(src.device)
     _launch("mil_affine_u8", ("affine_windows_u8", n, s, tile == 0), src.data_ptr(), tile, 3 * width, 3, 1, width, height,
             out.data_ptr(), 3, 1, s, s, md.data_ptr(), fill, n, L.stream_ptr())
+    return out
+
+
+def elastic_tables(size, cells):
+    """The table pair of the uniform cubic B-spline for an axis of `size` output pixels divided into `cells` cells (see
+    mil_affine_elastic_u8): (idx int32 [size], w float64 [size,4]) on the host, in numpy doubles, one rounded operation at a time:
+
+        u = ((x + 0.5) * cells) / size ;  i = min(floor(u), cells-1) ;  t = u - i ;  s = 1 - t ;  t2 = t*t ;  t3 = t2*t
+        w0 = ((s*s)*s)/6      w1 = ((3*t3 - 6*t2) + 4)/6      w2 = (((-3*t3 + 3*t2) + 3*t) + 1)/6      w3 = t3/6
+
+    Output position x reads lattice entries idx[x] .. idx[x] + 3.  ValueError unless size and cells are positive integers."""
+    import numbers
+    import numpy as np
+    if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 1 for v in (size, cells)):
+        raise ValueError(f"size and cells must be positive integers, got {size!r}, {cells!r}")
+    x = np.arange(int(size), dtype=np.float64)
+    u = ((x + 0.5) * np.float64(cells)) / np.float64(size)
+    i = np.minimum(np.floor(u), np.float64(int(cells) - 1))
+    t = u - i
+    s = 1.0 - t
+    t2 = t * t
+    t3 = t2 * t
+    w = np.stack([((s * s) * s) / 6.0, ((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0, (((-3.0 * t3 + 3.0 * t2) + 3.0 * t) + 1.0) / 6.0, t3 / 6.0],
+                 axis=1)
+    return torch.from_numpy(i.astype(np.int32)), torch.from_numpy(np.ascontiguousarray(w))
+
+
+def _elastic_tables_on(size, cells, device):
+    """`elastic_tables(size, cells)`, checked on the host (indices in [0, cells-1], finite weights: what keeps the kernel inside
+    the lattice) and uploaded; a few recent ones are kept per device."""
+    key = (int(size), int(cells), torch.device(device))
+    tab = _elastic_tables.get(key)
+    if tab is None:
+        idx, w = elastic_tables(int(size), int(cells))
+        if int(idx.min()) < 0 or int(idx.max()) > int(cells) - 1 or not bool(torch.isfinite(w).all()):
+            raise ValueError(f"elastic tables for {size} pixels in {cells} cells are out of range")
+        if len(_elastic_tables) >= 16:
+            _elastic_tables.clear()
+        tab = _elastic_tables[key] = (idx.to(key[2]), w.to(key[2]))
+    return tab
+
+
+def elastic_lattice(ctrl, n, name="ctrl"):
+    """`ctrl` (a tensor, an array or nested lists) as a contiguous float64 [n,2,gy+3,gx+3] host tensor, gy, gx >= 1: one control
+    lattice per tile, component 0 the x and component 1 the y displacement in source pixels; ValueError for another shape, a
+    non-numeric dtype or a non-finite entry.  Needs no device."""
+    try:
+        c = torch.as_tensor(ctrl).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must be float64 [{n},2,gy+3,gx+3]") from None
+    if c.dtype == torch.bool or c.is_complex() or c.dim() != 4 or c.shape[0] != n or c.shape[1] != 2 or c.shape[2] < 4 or c.shape[3] < 4:
+        raise ValueError(f"{name} must be float64 [{n},2,gy+3,gx+3] with gy, gx >= 1, got {tuple(c.shape)} {c.dtype}")
+    c = c.to(torch.float64).contiguous()
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError(f"{name} holds a non-finite entry")
+    return c
+
+
+def _identity_matrices(n):
+    return torch.tensor([[1.0, 0.0, 0.0, 0.0, 1.0, 0.0]], dtype=torch.float64).repeat(n, 1)
+
+
+def _launch_elastic(label, src, strides, width, height, out, dst_strides, ow, oh, m, fill, c):
+    """One mil_affine_elastic_u8 call for the host matrices m [n,6] and lattices c [n,2,ly,lx] (both checked)."""
+    dev = src.device
+    ly, lx = int(c.shape[2]), int(c.shape[3])
+    iy, wy = _elastic_tables_on(oh, ly - 3, dev)
+    ix, wx = _elastic_tables_on(ow, lx - 3, dev)
+    md, cd = m.to(dev), c.to(dev)
+    _launch("mil_affine_elastic_u8", label, src.data_ptr(), *strides, width, height, out.data_ptr(), *dst_strides, ow, oh,
+            md.data_ptr(), fill, int(m.shape[0]), cd.data_ptr(), ly, lx, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(),
+            L.stream_ptr())
+
+
+def elastic_u8(src, matrices, ctrl, fill=0, out_hw=None):
+    """`affine_u8` with an elastic deformation fused into the same resampling (see mil_affine_elastic_u8): src planar uint8
+    [n,3,h,w], matrices float64 [n,6] (None: the identity), ctrl float64 [n,2,gy+3,gx+3], one control lattice per tile in source
+    pixels over gy x gx cells of the OUTPUT; fill, out_hw as in `affine_u8`.  Returns a NEW uint8 [n,3,oh,ow].  A lattice of zeros
+    gives `affine_u8`'s bytes.  Every refusal comes before the launch."""
+    n, h, w = _u8_stack(src, "src")
+    oh, ow = _affine_hw(out_hw, h, w)
+    m = _identity_matrices(n) if matrices is None else affine_matrices(matrices, n)
+    c = elastic_lattice(ctrl, n)
+    fill = affine_fill(fill)
+    out = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=src.device)
+    if n:
+        _launch_elastic(("elastic_u8", n, h, w, oh, ow), src, (3 * h * w, w, 1, h * w), w, h, out, (1, oh * ow), ow, oh, m, fill, c)
+    return out
+
+
+def elastic_windows_u8(source, coords, matrices, ctrl, fill=0, size=None):
+    """The window form of `elastic_u8`, interleaved, as `affine_windows_u8` is of `affine_u8`: source a uint8 slide [H,W,3] with
+    coords (int [n,2] of (row, col)) and `size`, or an ROI stack [n,S,S,3] with coords=None; matrices float64 [n,6] in WINDOW
+    coordinates (None: the identity); ctrl float64 [n,2,gy+3,gx+3] in source pixels.  Returns a NEW uint8 [n,S,S,3].  For a
+    slide the window's origin is added to a2 and a5 on the host and every window reads the slide itself: a deformed window shows
+    the tissue that lies beside it, and only what lies outside the slide becomes `fill`.  Every refusal comes before the launch."""
+    from .preprocess import source_windows
+    if coords is None:
+        if not isinstance(source, torch.Tensor) or source.dim() != 4:
+            raise ValueError("without coords the source is an ROI stack [n,S,S,3]")
+        s = int(source.shape[1]) if size is None else int(size)
+        src, off, _ = source_windows(source, None, s)
+        origins = None
+    else:
+        if size is None or int(size) < 1:
+            raise ValueError("windows of a slide need their size (a positive number of pixels)")
+        s = int(size)
+        src, off, _ = source_windows(source, coords, s)
+        width = int(src.shape[1])
+        origins = torch.stack([off // 3 % width, off // 3 // width], dim=1).to(torch.float64)          # (col, row)
+    n = int(off.numel())
+    m = _identity_matrices(n) if matrices is None else affine_matrices(matrices, n)
+    c = elastic_lattice(ctrl, n)
+    fill = affine_fill(fill)
+    if not src.is_cuda:
+        raise RuntimeError("the elastic deformation runs on an AMD GPU only (no CPU fallback)")
+    out = torch.empty((n, s, s, 3), dtype=torch.uint8, device=src.device)
+    if n == 0:
+        return out
+    if origins is None:
+        tile, width, height = 3 * s * s, s, s
+    else:
+        m = m.clone()
+        m[:, 2] += origins[:, 0]
+        m[:, 5] += origins[:, 1]
+        tile, height = 0, int(src.shape[0])
+    _launch_elastic(("elastic_windows_u8", n, s, tile == 0), src, (tile, 3 * width, 3, 1), width, height, out, (3, 1), s, s, m, fill, c)
     return out
 
 

@@ -152,7 +152,7 @@ class TilePreprocessor:
             self.kk_dev = torch.from_numpy(self.kk_host).to(dev)
         return self.bounds_dev, self.kk_dev
 
-    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0):
+    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None):
         """rois: uint8 [T,S,S,3] on the GPU (the cached `data_cache` array).  params: int32 [T,4] from `draw_params`
         (train chain) or None (validation chain).  Returns fp32 [T,3,R,R] in [-1,1] (out="nchw": the reference's tensor), or
         — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
@@ -163,14 +163,18 @@ class TilePreprocessor:
         `StainAffine` (one map, or one per tile) — the resized bytes go through it (`mil_stain_affine_u8`) BEFORE the colour
         jitter; out as with a jitter.  affine: float64 [T,6], one matrix per ROI in its own coordinates (`RandomAffine.draw_params(T,
         roi_size)`) — every ROI is first transformed as Pillow's `transform((S, S), AFFINE, m, BILINEAR, fillcolor=affine_fill)`
-        does it (what lies outside the ROI becomes `affine_fill`, a byte or three), then goes through the chain above."""
+        does it (what lies outside the ROI becomes `affine_fill`, a byte or three), then goes through the chain above.  elastic:
+        float64 [T,2,gy+3,gx+3], one control lattice per ROI in ROI pixels, before the resize (`ElasticDeform.draw_params(T,
+        roi_size)`) — the ROI is deformed in the SAME resampling as `affine` (alone: with the identity matrix), one launch per
+        stack of AFFINE_CHUNK (`mil_affine_elastic_u8`)."""
         if jitter is not None or stain is not None:
             t = rois.shape[0] if isinstance(rois, torch.Tensor) and rois.dim() == 4 else -1      # -1: rois are refused below
-            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8", affine=affine, affine_fill=affine_fill), stain)
-        if affine is not None:
+            return self._jittered(out, jitter, t, lambda: self(rois, params, "u8", affine=affine, affine_fill=affine_fill, elastic=elastic),
+                                  stain)
+        if affine is not None or elastic is not None:
             if not isinstance(rois, torch.Tensor) or rois.dim() != 4:
                 raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(getattr(rois, 'shape', ()))}")
-            return self._transformed(rois, None, params, out, affine, affine_fill)
+            return self._transformed(rois, None, params, out, affine, affine_fill, elastic)
         self._check_out(out)
         if rois.dtype != torch.uint8 or rois.dim() != 4 or rois.shape[3] != 3 or rois.shape[1] != rois.shape[2]:
             raise ValueError(f"expected uint8 [T,S,S,3] ROIs, got {tuple(rois.shape)} {rois.dtype}")
@@ -213,15 +217,17 @@ class TilePreprocessor:
             apply_jitter(tiles, jitter)
         return tiles if out == "u8" else tiles.float()
 
-    def _transformed(self, source, coords, params, out, affine, fill):
-        """The `affine=` path of `__call__` (coords None) and `from_slide`: the windows transformed with `ops.affine_windows_u8`
-        in stacks of at most AFFINE_CHUNK, each handed to `__call__`; no array of T * S^2 pixels exists.  Everything is checked
-        before the first launch."""
+    def _transformed(self, source, coords, params, out, affine, fill, elastic=None):
+        """The `affine=` / `elastic=` path of `__call__` (coords None) and `from_slide`: the windows transformed with
+        `ops.affine_windows_u8` — with a lattice, `ops.elastic_windows_u8`: both transforms in one launch — in stacks of at most
+        AFFINE_CHUNK, each handed to `__call__`; no array of T * S^2 pixels exists.  Everything is checked before the first
+        launch."""
         from . import ops
         self._check_out(out)
         src, off, _ = source_windows(source, coords, self.roi_size)
         t = int(off.numel())
-        m = ops.affine_matrices(affine, t, "affine")
+        m = None if affine is None else ops.affine_matrices(affine, t, "affine")
+        lat = None if elastic is None else ops.elastic_lattice(elastic, t, "elastic")
         ops.affine_fill(fill)
         if not src.is_cuda:
             raise RuntimeError("tile pre-processing runs on an AMD GPU only (no CPU fallback)")
@@ -232,7 +238,10 @@ class TilePreprocessor:
         parts = []
         for lo in range(0, t, AFFINE_CHUNK):
             hi = min(t, lo + AFFINE_CHUNK)
-            if coords is None:
+            if lat is not None:
+                win = ops.elastic_windows_u8(src[lo:hi] if coords is None else src, None if coords is None else coords[lo:hi],
+                                             None if m is None else m[lo:hi], lat[lo:hi], fill, self.roi_size)
+            elif coords is None:
                 win = ops.affine_windows_u8(src[lo:hi], None, m[lo:hi], fill)
             else:
                 win = ops.affine_windows_u8(src, coords[lo:hi], m[lo:hi], fill, self.roi_size)
@@ -267,7 +276,7 @@ class TilePreprocessor:
             return torch.empty((t, 3, r, r), dtype=torch.uint8, device=dev), "mil_tile_preprocess_u8"
         return torch.empty((t, 3, r, r), dtype=torch.float32, device=dev), "mil_tile_preprocess"
 
-    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0):
+    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None):
         """The same chains on windows of a slide that stays where it is (`array_read_region`, RoiBuilder.py:117-124, then
         :193-210): slide uint8 [H,W,3] on the GPU (any contiguous view, whatever its alignment), coords int [T,2] of (row, col)
         of `roi_size` windows.  No [T,S,S,3] stack is made: the kernel reads the windows in place (mil_tile_preprocess_win*).
@@ -279,13 +288,16 @@ class TilePreprocessor:
         outside the slide becomes `affine_fill` —, then goes through the chain: bit for bit
         `Image.fromarray(slide).transform((S, S), Image.AFFINE, m + origin, Image.BILINEAR, fillcolor=affine_fill)` followed by
         `__call__` on those windows (origin: col added to a2, row to a5).  The transformed windows are made AFFINE_CHUNK at a
-        time."""
+        time.  elastic: float64 [T,2,gy+3,gx+3], one control lattice per window in window pixels (`ElasticDeform.draw_params(T,
+        roi_size)`): the deformation is one more term of the same source coordinate, so with both `affine` and `elastic` a window
+        is still resampled once, one launch per chunk, reading the slide."""
         if jitter is not None or stain is not None:
             t = int(source_windows(slide, coords, self.roi_size)[1].numel())
             return self._jittered(out, jitter, t,
-                                  lambda: self.from_slide(slide, coords, params, "u8", affine=affine, affine_fill=affine_fill), stain)
-        if affine is not None:
-            return self._transformed(slide, coords, params, out, affine, affine_fill)
+                                  lambda: self.from_slide(slide, coords, params, "u8", affine=affine, affine_fill=affine_fill,
+                                                          elastic=elastic), stain)
+        if affine is not None or elastic is not None:
+            return self._transformed(slide, coords, params, out, affine, affine_fill, elastic)
         self._check_out(out)
         src, off, pitch = source_windows(slide, coords, self.roi_size)
         if not src.is_cuda:

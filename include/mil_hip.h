@@ -388,6 +388,36 @@ int mil_affine_u8(const uint8_t* src, int64_t src_tile_stride, int64_t src_row_s
                   int64_t src_chan_stride, int W, int H, uint8_t* dst, int64_t dst_pix_stride, int64_t dst_chan_stride, int ow, int oh,
                   const double* matrices, uint32_t fill_rgb, int n, void* stream);
 
+/* Elastic deformation fused into that resampling: mil_affine_u8 with one more term in the source coordinate, so a rotated AND
+ * deformed image is interpolated once.  Everything mil_affine_u8 takes, plus (all DEVICE arrays)
+ *     ctrl  double [n,2,ly,lx]   one control lattice per image: component 0 the x displacement, component 1 the y displacement,
+ *                                in SOURCE pixels; ly = gy + 3, lx = gx + 3 where gy, gx >= 1 are the numbers of cells the
+ *                                OUTPUT image is divided into
+ *     iy    int32 [oh], wy double [oh,4]      the rows' table pair: first lattice row and the four weights of output row y
+ *     ix    int32 [ow], wx double [ow,4]      the same for the columns
+ * For output pixel (x, y), with c = ctrl[t][k], k = 0 for dx and k = 1 for dy:
+ *     r_i = ((wy[y][0]*c[iy[y]+0][ix[x]+i] + wy[y][1]*c[iy[y]+1][ix[x]+i]) + wy[y][2]*c[iy[y]+2][ix[x]+i]) + wy[y][3]*c[iy[y]+3][ix[x]+i]
+ *                                                                                                                  i = 0..3
+ *     d   = ((wx[x][0]*r_0 + wx[x][1]*r_1) + wx[x][2]*r_2) + wx[x][3]*r_3
+ *     xin = ((a0*xs + a1*ys) + a2) + dx          yin = ((a3*xs + a4*ys) + a5) + dy
+ * and from xin, yin onward mil_affine_u8's contract word for word: inside test, fill, xf, taps, v1, v2, truncation.  IEEE double,
+ * every product and sum rounded once in the order written, nothing fused.  In the slide-window form the caller has added the
+ * window's origin to a2 and a5 first, as for mil_affine_u8.  The tables of the uniform cubic B-spline (mil_amd.ops.elastic_tables,
+ * numpy doubles on the host), for x = 0..size-1 of an axis of `size` output pixels divided into `cells` cells:
+ *     u = ((x + 0.5) * cells) / size ;  i = min(floor(u), cells-1) ;  t = u - i ;  s = 1 - t ;  t2 = t*t ;  t3 = t2*t
+ *     w0 = ((s*s)*s)/6      w1 = ((3*t3 - 6*t2) + 4)/6      w2 = (((-3*t3 + 3*t2) + 3*t) + 1)/6      w3 = t3/6
+ * A lattice of zeros (+0.0 or -0.0) changes neither the inside test nor a tap: the bytes are mil_affine_u8's, hence Pillow's.  The
+ * weights are non-negative and sum to 1 within rounding, so |d| does not exceed the largest |ctrl| entry by more than rounding.
+ * The kernel clamps iy to [0, ly-4] and ix to [0, lx-4] (valid tables lie there): no access leaves the lattice, the tables, the
+ * source image or the destination stack.  Addressing, thread layout and store paths are mil_affine_u8's.
+ * Null pointers, n < 0, W / H / ow / oh < 1, ly or lx < 4, a negative src_tile_stride, any other stride < 1: MIL_ERR_ARG; ow * oh >
+ * 2^31 - 1 - 1024: MIL_ERR_UNSUPPORTED; n == 0: MIL_OK, no launch — all decided on the host before any GPU call.  Any n
+ * (launches of 65535 images; the lattice pointer advances with the matrices). */
+int mil_affine_elastic_u8(const uint8_t* src, int64_t src_tile_stride, int64_t src_row_stride, int64_t src_pix_stride,
+                          int64_t src_chan_stride, int W, int H, uint8_t* dst, int64_t dst_pix_stride, int64_t dst_chan_stride,
+                          int ow, int oh, const double* matrices, uint32_t fill_rgb, int n, const double* ctrl, int ly, int lx,
+                          const int32_t* iy, const double* wy, const int32_t* ix, const double* wx, void* stream);
+
 /* Forward of a whole identity-shortcut residual block in one pass (bf16 path; nnBlocks.py:175-189 with
  * downsample=None): o1 = lrelu(conv3x3(x)+b1) — written because the backward needs it — and
  * y = lrelu(conv3x3(o1)+b2+x).  x is read once (operand and residual), the mid activation feeds conv2 from LDS.
