@@ -15,6 +15,7 @@ from .color_jitter import ColorJitter  # noqa: F401
 from .stain import HED, StainAffine, StainFit, StainJitter, StainNormalizer  # noqa: F401
 from .affine import RandomAffine, affine_matrix, quarter_turn_matrix  # noqa: F401
 from .elastic import ElasticDeform  # noqa: F401
+from .blur_u8 import GaussianBlurU8, gaussian_blur_u8  # noqa: F401
 from .model import Attention, ContextLayer, CrossEntropyWithProbs, TileParallel  # noqa: F401
 from .summary import ActivationSummary, parameter_stats, tensor_stats  # noqa: F401
 from .saliency import TileSaliency  # noqa: F401
@@ -31,4 +32,4 @@ __all__ = ["alt_resnet", "Attention", "ResNet", "BasicResBlock", "ContextLayer",
            "ActivationSummary", "parameter_stats", "tensor_stats", "TileSaliency", "TileGradCam", "TileIntegratedGradients", "TileSmoothGrad", "AttributionRenderer",
            "AttributionMosaic", "FeatureVisualizer", "FeatureVisResult", "FeatureInverter", "InversionResult", "PixelRegularizer", "gaussian_blur",
            "TileGuidedBackprop", "TileGuidedGradCam", "HED", "StainAffine", "StainFit", "StainJitter", "StainNormalizer",
-           "RandomAffine", "affine_matrix", "quarter_turn_matrix", "ElasticDeform"]
+           "RandomAffine", "affine_matrix", "quarter_turn_matrix", "ElasticDeform", "GaussianBlurU8", "gaussian_blur_u8"]

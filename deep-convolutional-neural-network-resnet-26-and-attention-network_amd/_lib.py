@@ -28,6 +28,7 @@ SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per
 REG_SLICES = 16                              # MIL_REG_SLICES: partial sums per tile and norm in mil_pixel_reg's workspace
 OD_SLICES = 16                               # MIL_OD_SLICES: partial sums per tile in mil_od_moments_u8's workspace
 BLUR_MAX_RADIUS = 16                         # MIL_BLUR_MAX_RADIUS: the largest radius mil_pixel_blur takes
+BLUR_U8_MAX_BOX = 7                          # MIL_BLUR_U8_MAX_BOX: the largest box radius r per axis of mil_gaussian_blur_u8
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
 
 
@@ -121,7 +122,8 @@ _SIGS = {
     "mil_pixel_reg": ([_vp] * 5 + [_i] * 4 + [_f, _f, _i, _i, _vp], _i),
     "mil_pixel_shift": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mil_pixel_blur": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
-    "mil_pixel_momentum_step": ([_vp] * 5 + [_sz, _i, _f, _f, _f, _vp], _i),
+    "mil_gaussian_blur_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mil_pixel_momentum_step":([_vp] * 5 + [_sz, _i, _f, _f, _f, _vp], _i),
     "mil_map_quantile_workspace":([_c.POINTER(_sz), _i, _i], _i),
     "mil_map_quantile": ([_vp, _i, _i, _i, _i, _c.c_double, _i, _vp, _sz, _vp, _vp, _vp], _i),
     "mil_attr_render": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),

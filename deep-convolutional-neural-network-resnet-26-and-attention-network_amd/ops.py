@@ -1153,6 +1153,129 @@ def pixel_blur(x, out=None, *, sigma=None, taps=None, edge="reflect"):
     return out
 
 
+BLUR_U8_MAX_SIGMA = 8.0                            # the largest sigma whose box radius is <= MIL_BLUR_U8_MAX_BOX
+
+
+def _box_params(sigma):
+    """(r, ww, fw) of one axis of `mil_gaussian_blur_u8` for a sigma in [0, 8]: Pillow's fp32 arithmetic (include/mil_hip.h), every
+    operation rounded to fp32, sqrt and floor taken in double."""
+    import math
+    import numpy as np
+    f32 = np.float32
+    radius = f32(sigma)
+    sigma2 = f32(f32(radius * radius) / f32(3))
+    big = f32(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f32(math.floor((float(big) - 1.0) / 2.0))
+    a = f32(f32(f32(f32(2) * l) + f32(1)) * f32(f32(l * f32(l + f32(1))) - f32(f32(3) * sigma2)))
+    a = f32(a / f32(f32(6) * f32(sigma2 - f32(f32(l + f32(1)) * f32(l + f32(1))))))
+    fr = f32(l + a)
+    r = int(fr)
+    ww = int(f32(f32(16777216) / f32(f32(fr * f32(2)) + f32(1))))
+    return r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2
+
+
+def _sigma_column(sigma, name):
+    """float64 [n] on the host from a number or a 1-D sequence / tensor of sigmas, each finite and in [0, 8]."""
+    if isinstance(sigma, bool) or isinstance(sigma, str):
+        raise ValueError(f"{name} must be a number or a 1-D sequence of numbers, got {sigma!r}")
+    try:
+        s = torch.as_tensor(sigma).detach().cpu()
+        if s.dtype == torch.bool or s.is_complex():
+            raise TypeError
+        s = s.to(torch.float64)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must be a number or a 1-D sequence of numbers, got {sigma!r}") from None
+    if s.dim() > 1:
+        raise ValueError(f"{name} must be a number or a 1-D sequence of numbers, got shape {tuple(s.shape)}")
+    s = s.reshape(-1)
+    if s.numel() and (not bool(torch.isfinite(s).all()) or float(s.min()) < 0.0 or float(s.max()) > BLUR_U8_MAX_SIGMA):
+        raise ValueError(f"{name} must be finite and lie in [0, {BLUR_U8_MAX_SIGMA:g}] (box radius <= {L.BLUR_U8_MAX_BOX})")
+    return s
+
+
+def box_blur_params(sigma_x, sigma_y=None):
+    """int32 [n,6] on the host, the rows (r_x, ww_x, fw_x, r_y, ww_y, fw_y) `mil_gaussian_blur_u8` takes, from the sigmas of
+    `PIL.ImageFilter.GaussianBlur`: a number or n of them per axis (sigma_y None: sigma_x on both axes; a single number beside n
+    is repeated).  sigma 0 on an axis gives (0, 2^24, 0), the identity.  A sigma that is negative, not finite or above 8 raises
+    ValueError."""
+    sx = _sigma_column(sigma_x, "sigma_x")
+    sy = sx if sigma_y is None else _sigma_column(sigma_y, "sigma_y")
+    if sx.numel() != sy.numel():
+        if sx.numel() == 1:
+            sx = sx.expand(sy.numel())
+        elif sy.numel() == 1:
+            sy = sy.expand(sx.numel())
+        else:
+            raise ValueError(f"sigma_x holds {sx.numel()} values, sigma_y {sy.numel()}")
+    cache = {}
+    rows = []
+    for a, b in zip(sx.tolist(), sy.tolist()):
+        for v in (a, b):
+            if v not in cache:
+                cache[v] = _box_params(v)
+        rows.append(cache[a] + cache[b])
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 6)
+
+
+def checked_box_params(params, n):
+    """`params` as a contiguous int32 [n,6] HOST tensor, every row inside the kernel's contract: 0 <= r <= 7, ww >= 0, fw >= 0 and
+    (2 r + 1) ww + 2 fw <= 2^24 per axis — the check `mil_gaussian_blur_u8` leaves to its caller."""
+    if not isinstance(params, torch.Tensor) or params.is_floating_point() or params.dtype == torch.bool or params.is_complex():
+        raise ValueError(f"params must be an integer tensor [{n},6], got {getattr(params, 'dtype', type(params).__name__)}")
+    if tuple(params.shape) != (n, 6):
+        raise ValueError(f"params must be an integer tensor [{n},6], got {tuple(params.shape)}")
+    p = params.detach().cpu().to(torch.int64)
+    for axis in (0, 3):
+        r, ww, fw = p[:, axis], p[:, axis + 1], p[:, axis + 2]
+        if n and (int(r.min()) < 0 or int(r.max()) > L.BLUR_U8_MAX_BOX):
+            raise ValueError(f"params: a box radius outside 0..{L.BLUR_U8_MAX_BOX}")
+        if n and (int(ww.min()) < 0 or int(fw.min()) < 0 or int(((2 * r + 1) * ww + 2 * fw).max()) > 1 << 24):
+            raise ValueError("params: weights must be >= 0 with (2 r + 1) ww + 2 fw <= 2^24")
+    return p.to(torch.int32).contiguous()
+
+
+def gaussian_blur_u8(u8, params, planes_per_item, out=None):
+    """Pillow's Gaussian blur of every plane of u8 (see mil_gaussian_blur_u8): uint8, contiguous, at least 2 dimensions, the
+    leading ones being the planes — a stack [T,3,H,W] with planes_per_item 3, maps [T,H,W] with 1.  params: int32 [n,6] from
+    `box_blur_params` (on the host or on the device; its host copy is range-checked here), n = planes / planes_per_item.  out:
+    None (a fresh tensor) or the caller's, which may not overlap u8: the blur is never in place.  Returns out."""
+    if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() < 2:
+        raise ValueError(f"u8 must be a uint8 tensor [..., H, W], got {getattr(u8, 'dtype', type(u8).__name__)} "
+                         f"{tuple(getattr(u8, 'shape', ()))}")
+    h, w = u8.shape[-2], u8.shape[-1]
+    if h < 1 or w < 1:
+        raise ValueError(f"u8: planes of {h}x{w}")
+    if h * w > 2 ** 31 - 1 - 4096:
+        raise ValueError(f"u8: planes of {h} x {w} pixels are beyond 32-bit indexing")
+    if not u8.is_contiguous():
+        raise ValueError(f"u8 must be contiguous, got strides {tuple(u8.stride())}")
+    if isinstance(planes_per_item, bool) or not isinstance(planes_per_item, int) or planes_per_item < 1:
+        raise ValueError(f"planes_per_item must be a positive integer, got {planes_per_item!r}")
+    planes = u8.numel() // (h * w)
+    if planes % planes_per_item:
+        raise ValueError(f"{planes} planes are no multiple of planes_per_item = {planes_per_item}")
+    p = checked_box_params(params, planes // planes_per_item)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(u8.shape) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor like u8 {tuple(u8.shape)}, got {tuple(getattr(out, 'shape', ()))} "
+                             f"{getattr(out, 'dtype', None)}")
+        if _overlap(out, u8):
+            raise ValueError("out overlaps u8: the blur is never in place")
+    if not u8.is_cuda:
+        raise RuntimeError("the uint8 Gaussian blur runs on an AMD GPU only (no CPU fallback)")
+    _need(out, u8.shape, torch.uint8, "out")
+    if out is None:
+        out = torch.empty_like(u8)
+    if planes == 0:
+        return out
+    if (-(-h // 64)) * (-(-w // 64)) * planes > 2 ** 31 - 1:
+        raise ValueError(f"u8: {planes} planes of {h} x {w} pixels are more than 2^31 - 1 blocks of 64 x 64")
+    pd = p.to(u8.device)
+    _launch("mil_gaussian_blur_u8", ("gaussian_blur_u8", planes, planes_per_item, h, w), u8.data_ptr(), out.data_ptr(), pd.data_ptr(), planes,
+            planes_per_item, h, w, L.stream_ptr())
+    return out
+
+
 def momentum_scalars(lr, momentum, weight_decay):
     """(lr, weight_decay, momentum) of `pixel_momentum_step`, checked."""
     lr, mo, wd = float(lr), float(momentum), float(weight_decay)

@@ -152,7 +152,7 @@ class TilePreprocessor:
             self.kk_dev = torch.from_numpy(self.kk_host).to(dev)
         return self.bounds_dev, self.kk_dev
 
-    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None):
+    def __call__(self, rois, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None, blur=None):
         """rois: uint8 [T,S,S,3] on the GPU (the cached `data_cache` array).  params: int32 [T,4] from `draw_params`
         (train chain) or None (validation chain).  Returns fp32 [T,3,R,R] in [-1,1] (out="nchw": the reference's tensor), or
         — out="u8" — the same tiles as `U8Tiles` (the resized bytes, lossless: every compute mode, any resolution), or
@@ -166,7 +166,14 @@ class TilePreprocessor:
         does it (what lies outside the ROI becomes `affine_fill`, a byte or three), then goes through the chain above.  elastic:
         float64 [T,2,gy+3,gx+3], one control lattice per ROI in ROI pixels, before the resize (`ElasticDeform.draw_params(T,
         roi_size)`) — the ROI is deformed in the SAME resampling as `affine` (alone: with the identity matrix), one launch per
-        stack of AFFINE_CHUNK (`mil_affine_elastic_u8`)."""
+        stack of AFFINE_CHUNK (`mil_affine_elastic_u8`).  blur: float64 [T] (or [T,2]: (sx, sy)), one sigma per tile, 0 = untouched
+        (`GaussianBlurU8.draw_params(T)`) — the LAST step of the chain, after the stain map and the colour jitter: the bytes are
+        those of `GaussianBlurU8.apply` on what the same call returns without `blur=` (Pillow's `GaussianBlur`, bit for bit); out
+        as with a jitter."""
+        if blur is not None:
+            t = rois.shape[0] if isinstance(rois, torch.Tensor) and rois.dim() == 4 else -1
+            return self._blurred(out, blur, t, lambda: self(rois, params, "u8", jitter, stain=stain, affine=affine, affine_fill=affine_fill,
+                                                            elastic=elastic))
         if jitter is not None or stain is not None:
             t = rois.shape[0] if isinstance(rois, torch.Tensor) and rois.dim() == 4 else -1      # -1: rois are refused below
             return self._jittered(out, jitter, t, lambda: self(rois, params, "u8", affine=affine, affine_fill=affine_fill, elastic=elastic),
@@ -215,6 +222,20 @@ class TilePreprocessor:
             apply_stain(tiles, stain)
         if jitter is not None:
             apply_jitter(tiles, jitter)
+        return tiles if out == "u8" else tiles.float()
+
+    def _blurred(self, out, blur, t, make_u8):
+        """`make_u8()` (this preprocessor's U8Tiles of `t` tiles, every other step done) blurred with the per-tile sigmas `blur` and
+        returned as `out` asks; the sigmas and `out` are checked before anything is launched."""
+        from .blur_u8 import apply_blur, checked_sigmas
+        self._check_out(out)
+        if out == "s2d":
+            raise ValueError("the Gaussian blur works on the resized bytes: use out='u8' (or 'nchw')")
+        if not isinstance(blur, torch.Tensor) or blur.dim() not in (1, 2):
+            raise ValueError(f"blur must be a tensor of per-tile sigmas [T] or [T,2], got {blur!r}")
+        if t >= 0:
+            checked_sigmas(blur, t, "blur")
+        tiles = apply_blur(make_u8(), blur)
         return tiles if out == "u8" else tiles.float()
 
     def _transformed(self, source, coords, params, out, affine, fill, elastic=None):
@@ -276,7 +297,8 @@ class TilePreprocessor:
             return torch.empty((t, 3, r, r), dtype=torch.uint8, device=dev), "mil_tile_preprocess_u8"
         return torch.empty((t, 3, r, r), dtype=torch.float32, device=dev), "mil_tile_preprocess"
 
-    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None):
+    def from_slide(self, slide, coords, params=None, out="nchw", jitter=None, *, stain=None, affine=None, affine_fill=0, elastic=None,
+                   blur=None):
         """The same chains on windows of a slide that stays where it is (`array_read_region`, RoiBuilder.py:117-124, then
         :193-210): slide uint8 [H,W,3] on the GPU (any contiguous view, whatever its alignment), coords int [T,2] of (row, col)
         of `roi_size` windows.  No [T,S,S,3] stack is made: the kernel reads the windows in place (mil_tile_preprocess_win*).
@@ -290,7 +312,12 @@ class TilePreprocessor:
         `__call__` on those windows (origin: col added to a2, row to a5).  The transformed windows are made AFFINE_CHUNK at a
         time.  elastic: float64 [T,2,gy+3,gx+3], one control lattice per window in window pixels (`ElasticDeform.draw_params(T,
         roi_size)`): the deformation is one more term of the same source coordinate, so with both `affine` and `elastic` a window
-        is still resampled once, one launch per chunk, reading the slide."""
+        is still resampled once, one launch per chunk, reading the slide.  blur: as in `__call__`, the last step."""
+        if blur is not None:
+            t = int(source_windows(slide, coords, self.roi_size)[1].numel())
+            return self._blurred(out, blur, t,
+                                 lambda: self.from_slide(slide, coords, params, "u8", jitter, stain=stain, affine=affine,
+                                                         affine_fill=affine_fill, elastic=elastic))
         if jitter is not None or stain is not None:
             t = int(source_windows(slide, coords, self.roi_size)[1].numel())
             return self._jittered(out, jitter, t,

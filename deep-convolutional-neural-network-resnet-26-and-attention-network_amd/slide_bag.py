@@ -26,14 +26,16 @@ class SlideBag:
     centre BEFORE the train chain, reading the slide itself (the tissue beside the window, not a fill colour, fills the corners;
     only what lies outside the slide gets `affine.fill`); validation and inference data never are.  `elastic`: an `ElasticDeform`
     — every window of `get_train_data` is deformed with a drawn control lattice, in the same resampling as `affine` (one launch
-    per chunk of windows; without an `affine` the fill is `elastic.fill`); validation and inference data never are.
+    per chunk of windows; without an `affine` the fill is `elastic.fill`); validation and inference data never are.  `blur`: a
+    `GaussianBlurU8` — every tile of `get_train_data` is blurred with a drawn sigma (0: left as it is), the LAST step of the train
+    chain, after the stain map and the colour jitter; validation and inference data never are.
 
     Unlike the reference, a bag with no kept window returns an EMPTY stack [0,3,R,R] from the three `get_*` methods, not the
     `torch.zeros(20,3,128,128)` placeholder of RoiBuilder.py:236,257 (which has neither the bag's resolution nor any tile of
     it); the caller decides what to do with a slide without tissue."""
 
     def __init__(self, slide, roi_size=1200, padding=0, resolution=None, pad=100, max_tiles=2500, selector=None, coords=None,
-                 color_jitter=None, *, stain_normalizer=None, stain_jitter=None, affine=None, elastic=None):
+                 color_jitter=None, *, stain_normalizer=None, stain_jitter=None, affine=None, elastic=None, blur=None):
         if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
             raise ValueError(f"expected a uint8 [H,W,3] slide, got {getattr(slide, 'dtype', type(slide))} "
                              f"{tuple(getattr(slide, 'shape', ()))}")
@@ -48,6 +50,7 @@ class SlideBag:
         self.stain_normalizer, self.stain_jitter = stain_normalizer, stain_jitter
         self.affine = affine
         self.elastic = elastic
+        self.blur = blur
         self.stain_fit = None                                # the bag's StainFit once a stain_normalizer made it
         self.coords = None                                   # coor_cache: int64 [T,2] numpy (row, col) once built
         if coords is not None:
@@ -117,7 +120,7 @@ class SlideBag:
         return aff
 
     def get_train_data(self, generator=None, choice=None, params=None, out="u8", jitter_params=None, *, stain_jitter_params=None,
-                       affine_params=None, elastic_params=None):
+                       affine_params=None, elastic_params=None, blur_params=None):
         """`get_train_data` (RoiBuilder.py:215-238): the cap of `choose`, then the train chain on the chosen windows with
         `draw_params(generator)` or the injected `params` [n,4].  A bag with a `color_jitter` then jitters the tiles with
         `color_jitter.draw_params(n, generator)` (drawn after the crop / flip parameters) or the injected `jitter_params`;
@@ -126,10 +129,14 @@ class SlideBag:
         without one refuses `stain_jitter_params`.  A bag with an `affine` draws `affine.draw_params(n, roi_size, generator)`
         LAST, after every draw above (seeded sequences of bags without one do not move), or takes the injected `affine_params`
         (float64 [n,6], window coordinates); the windows are transformed before the train chain.  A bag without one refuses
-        `affine_params`.  A bag with an `elastic` draws `elastic.draw_params(n, roi_size, generator)` after that — the very last
-        draw — or takes the injected `elastic_params` (float64 [n,2,gy+3,gx+3], window pixels); a bag without one refuses
-        `elastic_params`."""
+        `affine_params`.  A bag with an `elastic` draws `elastic.draw_params(n, roi_size, generator)` after that, or
+        takes the injected `elastic_params` (float64 [n,2,gy+3,gx+3], window pixels); a bag without one refuses
+        `elastic_params`.  A bag with a `blur` draws `blur.draw_params(n, generator)` after that — the very last draw, so a
+        bag without one consumes the random numbers it always did — or takes the injected `blur_params` (float64 [n] of sigmas, 0 =
+        untouched); the blur is the last step of the chain.  A bag without one refuses `blur_params`."""
         self._ready()
+        if blur_params is not None and self.blur is None:
+            raise ValueError("blur_params given to a bag made without blur=")
         if elastic_params is not None and self.elastic is None:
             raise ValueError("elastic_params given to a bag made without elastic=")
         if affine_params is not None and self.affine is None:
@@ -146,18 +153,20 @@ class SlideBag:
             jitter_params = self.color_jitter.draw_params(len(c), generator)
         if self.stain_jitter is not None and stain_jitter_params is None and len(c):
             stain_jitter_params = self.stain_jitter.draw_params(len(c), generator)
-        if self.affine is None and self.elastic is None:
-            return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params))
         if self.affine is not None and affine_params is None:
             affine_params = self.affine.draw_params(len(c), self.roi_size, generator)
-        if self.elastic is None:
-            return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params),
-                                        affine=affine_params, affine_fill=self.affine.fill)
-        if elastic_params is None:
+        if self.elastic is not None and elastic_params is None:
             elastic_params = self.elastic.draw_params(len(c), self.roi_size, generator)
-        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params),
-                                    affine=affine_params, affine_fill=(self.elastic if self.affine is None else self.affine).fill,
-                                    elastic=elastic_params)
+        if self.blur is not None and blur_params is None:
+            blur_params = self.blur.draw_params(len(c), generator)
+        kw = {}                                              # only what the bag was made with: a plain bag makes the call it made
+        if self.affine is not None or self.elastic is not None:
+            kw.update(affine=affine_params, affine_fill=(self.elastic if self.affine is None else self.affine).fill)
+        if self.elastic is not None:
+            kw.update(elastic=elastic_params)
+        if self.blur is not None:
+            kw.update(blur=blur_params)
+        return self.prep.from_slide(self.slide, c, params, out, jitter=jitter_params, stain=self._stain(len(c), stain_jitter_params), **kw)
 
     def get_validation_data(self, out="u8"):
         """`get_validation_data` (RoiBuilder.py:240-259): the flat chain on every kept window."""

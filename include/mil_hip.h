@@ -759,6 +759,34 @@ int mil_pixel_shift(const float* x, float* out, int n, int H, int W, int dy, int
 #define MIL_BLUR_MAX_RADIUS 16
 int mil_pixel_blur(const float* x, float* out, const float* taps, int planes, int H, int W, int radius, int edge, void* stream);
 
+/* Pillow's `ImageFilter.GaussianBlur` on a stack of uint8 planes, bit for bit — the defocus augmentation of the train chain on planar
+ * tile stacks [T,3,H,W] (planes = 3 T, planes_per_item = 3) and the smoothing of uint8 maps [T,H,W] (planes_per_item = 1).  Pillow's
+ * Gaussian blur is three passes of an extended box blur along the rows, then three along the columns, in 32-bit integer fixed point,
+ * rounded to a byte after every pass.  in, out: uint8 [planes,H,W], contiguous, any H, W >= 1; never in place.  params: a DEVICE
+ * int32 [planes / planes_per_item, 6] = (r_x, ww_x, fw_x, r_y, ww_y, fw_y) per item; plane p takes row p / planes_per_item.  One pass
+ * along a line of length n, with c(i) = min(max(i, 0), n - 1) and all arithmetic in uint32:
+ *     out[x] = (ww * sum_{k=-r..r} in[c(x+k)] + fw * (in[c(x-r-1)] + in[c(x+r+1)]) + (1 << 23)) >> 24
+ * Three such passes run along W with the x parameters, then three along H with the y parameters; each pass reads the bytes the pass
+ * before wrote and clamps at the border of the PLANE.  The weights sum to at most 2^24, so nothing wraps; there is no floating point
+ * on the device and any summation order gives the same bits.  (r, ww, fw) = (0, 2^24, 0) is the identity on that axis (what Pillow
+ * does for a radius of 0: it skips the axis).  The host derives the integers from a sigma per axis in fp32, as Pillow's C does:
+ *     radius = f32(sigma);  sigma2 = f32(radius * radius / f32(3))
+ *     L = f32(sqrt(12.0 * double(sigma2) + 1.0));  l = f32(floor((double(L) - 1.0) / 2.0))
+ *     a = f32((2 l + 1) * (l (l + 1) - 3 sigma2));  a = f32(a / f32(6 * (sigma2 - (l + 1) (l + 1))))
+ *     fr = f32(l + a);  r = int(fr);  ww = int(f32(16777216) / f32(fr * 2 + 1))   (an fp32 division, truncated)
+ *     fw = ((1 << 24) - (2 r + 1) * ww) / 2
+ * r <= MIL_BLUR_U8_MAX_BOX on either axis, which admits every sigma <= 8.0; the halo of a 64 x 64 output block is then at most
+ * 3 (r + 1) = 24 pixels per side.  One workgroup per block: the block and this item's halo staged in LDS as bytes, six passes between
+ * two LDS byte arrays, the last written to global memory.
+ * WHO CHECKS WHAT.  This entry decides on the host, before any GPU call: null in / out / params, in and out overlapping in any byte,
+ * planes < 0, planes_per_item < 1, planes % planes_per_item != 0, H or W < 1: MIL_ERR_ARG; planes == 0: MIL_OK, no launch; a plane
+ * of more than 2^31 - 4097 bytes or more than 2^31 - 1 workgroups: MIL_ERR_UNSUPPORTED.  It does NOT read `params`, which lies in
+ * device memory: the caller (ops.gaussian_blur_u8 checks its host copy) guarantees 0 <= r <= MIL_BLUR_U8_MAX_BOX, ww >= 0, fw >= 0
+ * and (2 r + 1) ww + 2 fw <= 2^24 per axis.  The kernel forces r into 0..MIL_BLUR_U8_MAX_BOX, so no parameter can make it leave its
+ * arrays; weights outside the contract give bytes the contract does not define. */
+#define MIL_BLUR_U8_MAX_BOX 7
+int mil_gaussian_blur_u8(const uint8_t* in, uint8_t* out, const int32_t* params, int planes, int planes_per_item, int H, int W, void* stream);
+
 /* torch.optim.SGD with momentum (no dampening, no Nesterov) on an image stack, in place, in one pass — mil_pixel_step's kernel with a
  * third rule, behind an entry of its own (mil_pixel_step keeps refusing rule 2):
  *     g' = g + wd * x;   buf <- momentum * buf + g';   x <- x - lr * buf
