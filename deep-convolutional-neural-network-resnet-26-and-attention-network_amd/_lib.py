@@ -27,6 +27,7 @@ ATTR_SLICES = 32                             # MIL_ATTR_SLICES: partial sums per
 SEED_SLICES = 16                             # MIL_SEED_SLICES: partial sums per tile in mil_stage_seed's workspace
 REG_SLICES = 16                              # MIL_REG_SLICES: partial sums per tile and norm in mil_pixel_reg's workspace
 OD_SLICES = 16                               # MIL_OD_SLICES: partial sums per tile in mil_od_moments_u8's workspace
+SNMF_TERMS, SNMF_EXTRA = 12, 20              # MIL_SNMF_TERMS / MIL_SNMF_EXTRA: the sums of a coding pass; mil_od_snmf_fit_u8's extra doubles
 BLUR_MAX_RADIUS = 16                         # MIL_BLUR_MAX_RADIUS: the largest radius mil_pixel_blur takes
 BLUR_U8_MAX_BOX = 7                          # MIL_BLUR_U8_MAX_BOX: the largest box radius r per axis of mil_gaussian_blur_u8
 _ERR = {1: "invalid argument", 2: "unsupported shape / channel configuration", 3: "kernel launch failed"}
@@ -89,6 +90,9 @@ _SIGS = {
     "mil_stain_affine_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mil_od_moments_u8": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp], _i),
     "mil_od_project_u8": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp], _i),
+    "mil_od_snmf_sums_u8": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _vp, _vp], _i),
+    "mil_od_snmf_fit_u8": ([_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _sz, _vp, _vp], _i),
+    "mil_od_code_u8": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "mil_affine_u8": ([_vp] + [_c.c_int64] * 4 + [_i, _i, _vp, _c.c_int64, _c.c_int64, _i, _i, _vp, _c.c_uint32, _i, _vp], _i),
     "mil_affine_elastic_u8": ([_vp] + [_c.c_int64] * 4 + [_i, _i, _vp, _c.c_int64, _c.c_int64, _i, _i, _vp, _c.c_uint32, _i,
                                _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),

@@ -1455,12 +1455,98 @@ def od_moments(u8, beta=0.15, group="tile"):
     return out
 
 
-def od_project(u8, P, mode="concentrations", beta=0.15):
+def _snmf_lam(lam):
+    lam = float(lam)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"lam must be finite and >= 0, got {lam}")
+    return lam
+
+
+def snmf_dictionary(W, name="W"):
+    """`W` (a tensor, an array, nested lists) as a contiguous fp64 [3,2] host tensor; ValueError for another shape or a
+    non-finite entry."""
+    try:
+        W = torch.as_tensor(W).detach().to("cpu", torch.float64).contiguous()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name} must hold 3 x 2 finite numbers") from None
+    if tuple(W.shape) != (3, 2) or not bool(torch.isfinite(W).all()):
+        raise ValueError(f"{name} must hold 3 x 2 finite numbers, got {tuple(W.shape)}")
+    return W
+
+
+def snmf_coder(W, lam):
+    """The nine fp32 values the coder of the sparse factorisation takes (see mil_od_snmf_sums_u8), on the host: W row-major
+    rounded to fp32, c = W_0 . W_1 and d = 1 / (1 - c c) formed in fp64 in the header's order and rounded once (d = 0 for
+    collinear columns), lam."""
+    w = [float(v) for v in snmf_dictionary(W).reshape(6)]
+    c = (w[0] * w[1] + w[2] * w[3]) + w[4] * w[5]
+    e = 1.0 - c * c
+    d = 1.0 / e if e > 0.0 else 0.0
+    return torch.tensor(w + [c, d, _snmf_lam(lam)], dtype=torch.float64).to(torch.float32)
+
+
+def od_snmf_sums(u8, W, lam=0.1, beta=0.15):
+    """One coding pass of the sparse non-negative factorisation (see mil_od_snmf_sums_u8): every tissue pixel's code (h0, h1)
+    for the dictionary W [3,2] and the penalty lam, and fp64 [12] on the device = count, sum h0 h0, h0 h1, h1 h1, sum v_c h_j
+    (r0, r1, g0, g1, b0, b1), sum h0, sum h1.  Fixed summation tree: two calls give the same bits.  No host synchronisation."""
+    beta = _beta(beta)
+    t, h, w = _u8_stack(u8)
+    coder = snmf_coder(W, lam).to(u8.device)
+    if t == 0:                                                           # no tile: twelve zeros, no launch
+        return torch.zeros((L.SNMF_TERMS,), dtype=torch.float64, device=u8.device)
+    out = torch.empty((L.SNMF_TERMS,), dtype=torch.float64, device=u8.device)
+    ws = torch.empty((max(t, 1) * L.OD_SLICES, L.SNMF_TERMS), dtype=torch.float64, device=u8.device)
+    _launch("mil_od_snmf_sums_u8", ("od_snmf_sums", t, h, w), u8.data_ptr(), od_tables(u8.device).data_ptr(), coder.data_ptr(), t, h, w,
+            beta, ws.data_ptr(), ws.numel() * 8, out.data_ptr(), L.stream_ptr())
+    return out
+
+
+def od_snmf_fit(u8, W0, lam=0.1, iters=64, beta=0.15):
+    """`iters` iterations of the sparse non-negative factorisation from the dictionary W0 [3,2] (see mil_od_snmf_fit_u8): one
+    `od_moments` launch for sum |v|^2, then ONE C call that enqueues every coding pass and every update; the fp64 dictionary
+    stays on the device in between.  Returns (W fp64 [3,2], history fp64 [iters,2] = (objective of the W coded with, largest
+    |change of an entry of W|) per iteration, count fp64 [1] of the tissue pixels), all on the device, with no host
+    synchronisation."""
+    beta, lam, iters = _beta(beta), _snmf_lam(lam), int(iters)
+    if iters < 1:
+        raise ValueError(f"iters must be at least 1, got {iters}")
+    W0 = snmf_dictionary(W0, "W0")
+    t, h, w = _u8_stack(u8)
+    dev = u8.device
+    W = W0.to(dev)
+    if t == 0:                                                           # no tile: W as it came, a history of zeros, no launch
+        return W, torch.zeros((iters, 2), dtype=torch.float64, device=dev), torch.zeros((1,), dtype=torch.float64, device=dev)
+    moments = od_moments(u8, beta, "bag")
+    history = torch.empty((iters, 2), dtype=torch.float64, device=dev)
+    ws = torch.empty((t * L.OD_SLICES * L.SNMF_TERMS + L.SNMF_EXTRA,), dtype=torch.float64, device=dev)
+    _launch("mil_od_snmf_fit_u8", ("od_snmf_fit", t, h, w, iters), u8.data_ptr(), od_tables(dev).data_ptr(), W.data_ptr(),
+            moments.data_ptr(), t, h, w, lam, iters, beta, ws.data_ptr(), ws.numel() * 8, history.data_ptr(), L.stream_ptr())
+    return W, history, moments[0, :1]
+
+
+def od_project(u8, P, mode="concentrations", beta=0.15, lam=None):
     """Two projections of every pixel's OD as maps (see mil_od_project_u8): P [2,3] (rounded to fp32).  Returns (maps, valid):
     mode "concentrations" — maps fp32 [2,T,H,W] = (p_0, p_1) at tissue pixels; mode "ratio" — maps fp32 [T,H,W] = p_1 / p_0 at
-    tissue pixels with p_0 > 0; +inf everywhere else.  valid int32 [T]: the pixels of each tile that got a value."""
+    tissue pixels with p_0 > 0; +inf everywhere else.  valid int32 [T]: the pixels of each tile that got a value.  Mode
+    "sparse" (mil_od_code_u8) takes the dictionary W [3,2] in place of P and the penalty `lam`: maps fp32 [2,T,H,W] = the
+    non-negative lasso code (h0, h1) of every tissue pixel, the arithmetic of `od_snmf_sums`."""
+    if mode == "sparse":
+        beta = _beta(beta)
+        if lam is None:
+            raise ValueError("mode 'sparse' needs lam")
+        coder = snmf_coder(P, lam)
+        t, h, w = _u8_stack(u8)
+        maps = torch.empty((2, t, h, w), dtype=torch.float32, device=u8.device)
+        valid = torch.empty((t,), dtype=torch.int32, device=u8.device)
+        if t:
+            coder = coder.to(u8.device)
+            _launch("mil_od_code_u8", ("od_project", t, h, w, mode), u8.data_ptr(), od_tables(u8.device).data_ptr(), coder.data_ptr(),
+                    t, h, w, beta, maps.data_ptr(), valid.data_ptr(), L.stream_ptr())
+        return maps, valid
+    if lam is not None:
+        raise ValueError("lam belongs to mode 'sparse'")
     if mode not in PROJECT_MODES:
-        raise ValueError(f"mode must be one of {PROJECT_MODES}, got {mode!r}")
+        raise ValueError(f"mode must be one of {PROJECT_MODES + ('sparse',)}, got {mode!r}")
     beta = _beta(beta)
     t, h, w = _u8_stack(u8)
     P = torch.as_tensor(P).detach().to("cpu", torch.float64)

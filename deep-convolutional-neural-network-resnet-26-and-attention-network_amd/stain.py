@@ -11,7 +11,12 @@ eigen-decomposition and the 3 x 2 pseudo-inverse stay on the host, in fp64.
 
 Instead of the angle atan2(p_1, p_0) in the plane of the two leading eigenvectors the fit ranks the ratio p_1 / p_0: with
 p_0 > 0 the angle is monotone in it, so the order statistics are the same pixels; only the interpolation between two adjacent
-order statistics is taken in tan instead of in the angle.  Tissue pixels with p_0 <= 0 are dropped and counted (`n_dropped`)."""
+order statistics is taken in tan instead of in the angle.  Tissue pixels with p_0 <= 0 are dropped and counted (`n_dropped`).
+
+`StainNormalizer(method="vahadane")` fits the same two vectors as the dictionary of a sparse non-negative factorisation of the
+tissue pixels' ODs (Vahadane et al. 2016): `ops.od_snmf_fit` enqueues every coding pass and every dictionary update from one C
+call and the host reads the result back once; what follows the fit (pseudo-inverse, concentration percentiles, the affine map)
+is Macenko's tail unchanged."""
 import collections
 import math
 
@@ -114,16 +119,30 @@ def _unit(v):
 
 
 class StainFit:
-    """What a Macenko fit finds: `stains` fp64 [3,2], unit columns, haematoxylin first (the column with the larger red-channel
+    """What a stain fit finds: `stains` fp64 [3,2], unit columns, haematoxylin first (the column with the larger red-channel
     OD); `max_conc` [2], the `conc_q`-th percentile of each stain's concentration over the tissue pixels; `n_tissue`, the tissue
-    pixels of the fit; `n_dropped`, those of them left out of the ranking because p_0 <= 0."""
+    pixels of the fit; `n_dropped`, those of them left out of Macenko's ranking because p_0 <= 0 (0 for a Vahadane fit).  A
+    Vahadane fit also carries, read-only, `objective` (fp64 [iters]: the factorisation's objective before each update) and
+    `last_move` (the largest change of an entry of the dictionary in the last iteration); both are None otherwise."""
 
-    def __init__(self, stains, max_conc, n_tissue=0, n_dropped=0):
+    def __init__(self, stains, max_conc, n_tissue=0, n_dropped=0, *, objective=None, last_move=None):
         self.stains = _finite(stains, (3, 2), "stains")[0]
         self.max_conc = _finite(max_conc, (2,), "max_conc")[0]
         if abs(np.linalg.norm(self.stains, axis=0) - 1.0).max() > 1e-3:
             raise ValueError("the stain vectors must be unit columns")
         self.n_tissue, self.n_dropped = int(n_tissue), int(n_dropped)
+        self._objective = None if objective is None else np.array(objective, dtype=np.float64).reshape(-1)
+        if self._objective is not None:
+            self._objective.setflags(write=False)
+        self._last_move = None if last_move is None else float(last_move)
+
+    @property
+    def objective(self):
+        return self._objective
+
+    @property
+    def last_move(self):
+        return self._last_move
 
     @staticmethod
     def reference():
@@ -188,21 +207,82 @@ def percentile_from_stats(s_lo, s_hi, q_eff, n_total):
     return s_lo + d * t if t < 0.5 else s_hi - d * (1.0 - t)
 
 
+STAIN_METHODS = ("macenko", "vahadane")
+SNMF_MIN_SIN2 = 1e-3            # a Vahadane fit whose columns have 1 - (W_0 . W_1)^2 below this (within 1.8 degrees) is refused
+
+
+def snmf_start(init):
+    """The fp64 [3,2] dictionary a Vahadane fit starts from: "hed" (Ruifrok's haematoxylin and eosin columns of `HED`), a
+    `StainFit` (its stains: a Macenko fit can be polished) or a 3 x 2 array.  A negative entry or a column that is not unit to
+    1e-3 (the `StainFit` rule) raises ValueError."""
+    if isinstance(init, str):
+        if init != "hed":
+            raise ValueError(f"init must be 'hed', a StainFit or a 3 x 2 array, got {init!r}")
+        return HED[:, :2].copy()
+    W = init.stains.copy() if isinstance(init, StainFit) else _finite(init, (3, 2), "init")
+    if W.ndim == 3:
+        if len(W) != 1:
+            raise ValueError(f"init must be one 3 x 2 dictionary, got {W.shape}")
+        W = W[0]
+    if (W < 0).any() or abs(np.linalg.norm(W, axis=0) - 1.0).max() > 1e-3:
+        raise ValueError("init must have non-negative unit columns")
+    return W
+
+
 class StainNormalizer:
-    """Macenko stain normalisation for `U8Tiles` on the GPU: `fit` estimates a stack's two stain vectors and their strengths,
+    """Stain normalisation for `U8Tiles` on the GPU: `fit` estimates a stack's two stain vectors and their strengths,
     `affine` turns a fit into the `StainAffine` that maps the stack onto `target`, `transform` applies it in place.  beta: the
     OD below which a pixel is background (all three channels must reach it); q: the percentile (and 100 - q) of the ratio that
-    gives the two stain vectors; conc_q: the percentile of the concentrations that stands for "fully stained"."""
+    gives Macenko's two stain vectors; conc_q: the percentile of the concentrations that stands for "fully stained".
+    method: "macenko" (the default: the plane of the OD covariance and two percentiles of an angle in it) or "vahadane" (the
+    sparse non-negative factorisation of Vahadane et al. 2016 with penalty `lam`, `iters` iterations from `init`, see
+    `snmf_start`); every other step, and the normalising map, are the same for both."""
 
-    def __init__(self, target=None, beta=0.15, q=1.0, conc_q=99.0):
+    def __init__(self, target=None, beta=0.15, q=1.0, conc_q=99.0, *, method="macenko", lam=0.1, iters=64, init="hed"):
         self.target = StainFit.reference() if target is None else target
         if not isinstance(self.target, StainFit):
             raise ValueError(f"target must be a StainFit, got {type(self.target).__name__}")
         self.beta, self.q, self.conc_q = float(beta), float(q), float(conc_q)
         if not (self.beta >= 0.0 and math.isfinite(self.beta)) or not 0.0 < self.q < 50.0 or not 0.0 < self.conc_q <= 100.0:
             raise ValueError(f"beta must be finite and >= 0, q in (0, 50) and conc_q in (0, 100], got {beta}, {q}, {conc_q}")
+        if method not in STAIN_METHODS:
+            raise ValueError(f"method must be one of {STAIN_METHODS}, got {method!r}")
+        self.method, self.lam, self.iters = method, float(lam), int(iters)
+        if not (0.0 <= self.lam < math.inf) or self.iters < 1:
+            raise ValueError(f"lam must be finite and >= 0 and iters at least 1, got {lam}, {iters}")
+        self.init = snmf_start(init)
 
     def fit(self, tiles):
+        """`StainFit` of the stack by the normaliser's `method`: Macenko's plane and percentiles, or Vahadane's factorisation."""
+        if self.method == "vahadane":
+            return self._fit_vahadane(tiles)
+        return self._fit_macenko(tiles)
+
+    def _fit_vahadane(self, tiles):
+        """Vahadane's fit (method="vahadane"): the two stain vectors as the dictionary of a sparse non-negative factorisation of
+        the tissue pixels' ODs — `ops.od_snmf_fit` runs `iters` iterations from `init` on the device and the host reads the
+        dictionary, the history and the tissue count back once; the columns are ordered haematoxylin first and the tail of
+        Macenko's fit (pseudo-inverse, concentration maps, conc_q percentiles) follows unchanged: two synchronisations per fit.
+        Fewer than 2 tissue pixels, or a dictionary that is not finite or whose columns are collinear (1 - (W_0 . W_1)^2 below
+        `SNMF_MIN_SIN2`: the two vectors within 1.8 degrees of each other), raise ValueError."""
+        u8 = _on_gpu(_device_tiles(tiles, "the stain fit"), "the stain fit")
+        total = u8.shape[0] * u8.shape[2] * u8.shape[3]
+        if not total:
+            raise ValueError("a stain fit needs at least 2 tissue pixels, the stack has 0")
+        W, history, count = ops.od_snmf_fit(u8, self.init, self.lam, self.iters, self.beta)
+        back = torch.cat([W.reshape(-1), history.reshape(-1), count]).cpu().numpy()
+        W, history, n = back[:6].reshape(3, 2), back[6:-1].reshape(-1, 2), int(back[-1])
+        if n < 2:
+            raise ValueError(f"a stain fit needs at least 2 tissue pixels, the stack has {n}")
+        sin2 = 1.0 - float(W[:, 0] @ W[:, 1]) ** 2
+        if not (np.isfinite(W).all() and np.isfinite(history).all()) or not sin2 >= SNMF_MIN_SIN2:
+            raise ValueError(f"the factorisation found no two stains: 1 - (W_0 . W_1)^2 = {sin2:.3g} (at least {SNMF_MIN_SIN2} needed)")
+        stains = W if W[0, 0] > W[0, 1] else W[:, ::-1].copy()
+        conc, _ = ops.od_project(u8, np.linalg.pinv(stains), "concentrations", self.beta)
+        c = self._percentiles([(conc[0], self.conc_q, n), (conc[1], self.conc_q, n)], total)
+        return StainFit(stains, c, n, 0, objective=history[:, 0], last_move=history[-1, 1])
+
+    def _fit_macenko(self, tiles):
         """`StainFit` of the stack: one moments launch over the whole stack, the covariance and `numpy.linalg.eigh` on the
         host, the ratio map and its q / 100 - q percentiles, `pinv` of the stain vectors, the concentration maps and their
         conc_q percentiles.  The host steps read ten sums, a count and twice two percentiles back: four synchronisations per
@@ -250,13 +330,22 @@ class StainNormalizer:
         _on_gpu(u8, "the stain normalisation")
         return apply_stain(tiles, aff)
 
-    def separate(self, tiles, fit):
+    def separate(self, tiles, fit, *, sparse=False, lam=None):
         """fp32 [2,T,H,W]: the haematoxylin and the eosin concentration of every tissue pixel (+inf elsewhere) — the images
-        colour deconvolution gives."""
+        colour deconvolution gives.  sparse=True: the non-negative lasso code of every pixel with the fit's stains as the
+        dictionary and the penalty `lam` (None: the normaliser's) — what Vahadane's method calls the concentrations — instead
+        of the pseudo-inverse's."""
         u8 = _device_tiles(tiles, "the stain separation")
         if not isinstance(fit, StainFit):
             raise ValueError(f"expected a StainFit, got {type(fit).__name__}")
+        if not sparse and lam is not None:
+            raise ValueError("lam belongs to sparse=True")
+        lam = self.lam if lam is None else float(lam)
+        if sparse and not 0.0 <= lam < math.inf:
+            raise ValueError(f"lam must be finite and >= 0, got {lam}")
         _on_gpu(u8, "the stain separation")
+        if sparse:
+            return ops.od_project(u8, fit.stains, "sparse", self.beta, lam=lam)[0]
         return ops.od_project(u8, np.linalg.pinv(fit.stains), "concentrations", self.beta)[0]
 
 

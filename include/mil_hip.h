@@ -353,6 +353,55 @@ int mil_od_moments_u8(const uint8_t* tiles, const float* tables, int T, int H, i
 int mil_od_project_u8(const uint8_t* tiles, const float* tables, const float* P, int T, int H, int W, int mode, float beta,
                       float* maps, int32_t* valid, void* stream);
 
+/* Vahadane's stain fit (Vahadane et al. 2016) for the same stacks: the two stain vectors as a sparse non-negative
+ * factorisation of the tissue pixels' ODs v = (L[r], L[g], L[b]) — minimise over W (3 x 2, unit non-negative columns) and
+ * h_p >= 0   1/2 sum_p |v_p - W h_p|^2 + lam sum_p (h_p0 + h_p1)   by alternating an exact code step and a block-coordinate
+ * dictionary step.  tests/stain_snmf_reference.py restates all of it in numpy.
+ *
+ * The coder.  coder (float [9], DEVICE) = W[0,0], W[0,1], W[1,0], W[1,1], W[2,0], W[2,1] (W row-major, rounded to fp32), c, d,
+ * lam with, in fp64 from the fp64 W, every operation rounded once in the order written,
+ *     c = (W[0,0] W[0,1] + W[1,0] W[1,1]) + W[2,0] W[2,1] ;  e = 1 - c c ;  d = 1 / e if e > 0, else 0
+ * each rounded once to fp32.  Per pixel, in fp32, every operation rounded once (no FMA):
+ *     q_k = ((W[0,k] L[r] + W[1,k] L[g]) + W[2,k] L[b]) - lam
+ *     h0 = (q_0 - c q_1) d ;  h1 = (q_1 - c q_0) d
+ *     h0 >= 0 and h1 >= 0: (h0, h1);  else h1 < 0: (q_0 if q_0 > 0 else 0, 0);  else: (0, q_1 if q_1 > 0 else 0)
+ * — for unit columns with 0 <= c < 1 the exact minimiser of the two-variable non-negative lasso.  DEGENERATE W: collinear
+ * columns (e <= 0, or e NaN) get d = 0, which makes h0 = h1 = +-0 for every pixel: every code is zero, every sum below is
+ * zero, the update leaves both columns as they are.  d is finite whenever e > 0 (e >= 2^-53), so no NaN reaches a sum.
+ *
+ * mil_od_snmf_sums_u8: out (double [12]) over the TISSUE pixels of the stack (as mil_od_moments_u8 defines them) =
+ *     count, sum h0 h0, sum h0 h1, sum h1 h1, sum v_r h0, sum v_r h1, sum v_g h0, sum v_g h1, sum v_b h0, sum v_b h1, sum h0, sum h1
+ * the products of two fp32 values are exact in fp64, and they are added in mil_od_moments_u8's tree for bag 1 (slices, thread,
+ * butterfly, waves, one finishing workgroup): no floating-point atomics, two calls give the same bits.  workspace:
+ * T * MIL_OD_SLICES * 12 doubles.  T == 0 writes twelve zeros.
+ *
+ * mil_od_snmf_fit_u8: iters x (sums kernel + finishing kernel) enqueued by ONE call, no host synchronisation.  W (double [6],
+ * DEVICE, row-major [3,2]) is read and left updated; moments (double [10], DEVICE) is what mil_od_moments_u8 (bag 1) wrote for
+ * the same stack and beta; history (double [iters,2], DEVICE) gets one row per iteration.  One thread of the finishing
+ * workgroup, in fp64, every operation rounded once, with A = [[s1, s2], [s2, s3]], B[c,j] = s[4 + 2c + j] of the twelve sums:
+ *     f = ((sv2 / 2 - wb) + quad / 2) + lam (s10 + s11)        the objective of the W the codes were made with, where
+ *         sv2 = (m4 + m7) + m9 ,  n_jk = (W[0,j] W[0,k] + W[1,j] W[1,k]) + W[2,j] W[2,k]
+ *         wb = ((((W[0,0] B[0,0] + W[1,0] B[1,0]) + W[2,0] B[2,0]) + W[0,1] B[0,1]) + W[1,1] B[1,1]) + W[2,1] B[2,1]
+ *         quad = (A[0,0] n_00 + (2 A[0,1]) n_01) + A[1,1] n_11
+ *     for j = 0, 1 in turn, when A[j,j] > 0:   u_c = W[c,j] + (B[c,j] - (W[c,0] A[0,j] + W[c,1] A[1,j])) / A[j,j], u_c < 0 -> 0,
+ *         nn = (u_0 u_0 + u_1 u_1) + u_2 u_2 ;  when nn > 0:  W[c,j] = u_c / sqrt(nn)       (otherwise column j stays)
+ *     history row = (f, the largest |new W[c,j] - old W[c,j]|);  then c, d and the fp32 W of the next iteration's coder.
+ * workspace: T * MIL_OD_SLICES * 12 + MIL_SNMF_EXTRA doubles.  T == 0: the finishing kernel alone, W unchanged, f = 0.
+ *
+ * mil_od_code_u8: the "sparse" form of mil_od_project_u8 — maps (float [2,T,H,W]) = (h0, h1) of the coder at tissue pixels,
+ * +inf elsewhere; valid as there.
+ *
+ * All three: null pointers, T < 0, H or W < 1, beta NaN, lam NaN or negative, iters < 1, a workspace too small: MIL_ERR_ARG;
+ * shapes as above: MIL_ERR_UNSUPPORTED; decided on the host before any GPU call. */
+#define MIL_SNMF_TERMS 12
+#define MIL_SNMF_EXTRA 20
+int mil_od_snmf_sums_u8(const uint8_t* tiles, const float* tables, const float* coder, int T, int H, int W, float beta,
+                        double* workspace, size_t workspace_bytes, double* out, void* stream);
+int mil_od_snmf_fit_u8(const uint8_t* tiles, const float* tables, double* W, const double* moments, int T, int H, int Wd, float lam,
+                       int iters, float beta, double* workspace, size_t workspace_bytes, double* history, void* stream);
+int mil_od_code_u8(const uint8_t* tiles, const float* tables, const float* coder, int T, int H, int W, float beta, float* maps,
+                   int32_t* valid, void* stream);
+
 /* Rotation / affine augmentation of uint8 RGB images: torchvision's RandomAffine / RandomRotation as its PIL backend computes
  * them, Image.transform(size, Image.AFFINE, m, Image.BILINEAR, fillcolor=fill), bit for bit Pillow's bytes.  matrices (double
  * [n,6], DEVICE) holds a0..a5 per image: the map from OUTPUT pixel centres to INPUT coordinates.  For a source of W x H pixels

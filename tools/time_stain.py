@@ -75,6 +75,28 @@ def torch_project(u8, P, beta, ratio):
     return torch.where(m[None], p, inf)
 
 
+def torch_snmf_iteration(u8, W, lam, beta):
+    """One iteration of the sparse factorisation in torch ops: the closed-form code in fp32, the sums in fp64, the update."""
+    od = -torch.log((u8.float() + 1.0) / 256.0)
+    m = (od >= beta).all(dim=1)
+    Wf = W.float()
+    c = W[:, 0] @ W[:, 1]                                                 # stays on the device: no synchronisation
+    c, d = c.float(), (1.0 / (1.0 - c * c)).float()
+    q = torch.einsum("jk,tjhw->kthw", Wf, od) - lam
+    h0, h1 = (q[0] - c * q[1]) * d, (q[1] - c * q[0]) * d
+    both, zero = (h0 >= 0) & (h1 >= 0), torch.zeros((), device=u8.device)
+    a0 = torch.where(both, h0, torch.where(h1 < 0, q[0].clamp_min(0), zero))
+    a1 = torch.where(both, h1, torch.where(h1 < 0, zero, q[1].clamp_min(0)))
+    H = (torch.stack([a0, a1]) * m[None]).reshape(2, -1).double()
+    V = (od * m[:, None]).permute(1, 0, 2, 3).reshape(3, -1).double()
+    A, B = H @ H.t(), V @ H.t()
+    W = W.clone()
+    for j in (0, 1):
+        u = (W[:, j] + (B[:, j] - W @ A[:, j]) / A[j, j]).clamp_min(0)
+        W[:, j] = u / u.norm()
+    return W, H.sum(dim=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=500)
@@ -83,6 +105,7 @@ def main():
     ap.add_argument("--fit-resolution", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--snmf-iters", type=int, default=64)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_stain.py needs a GPU")
@@ -132,10 +155,21 @@ def main():
     times["fit_torch_project_ratio"] = timed(lambda: torch_project(tiles.u8, P1, 0.15, True), a.warmup, a.reps)
     times["fit_torch_project_concentrations"] = timed(lambda: torch_project(tiles.u8, P2, 0.15, False), a.warmup, a.reps)
 
+    # (iii) Vahadane's fit on the same stack
+    W0 = st.HED[:, :2].copy()
+    vnorm = mil_amd.StainNormalizer(method="vahadane", iters=a.snmf_iters)
+    times["snmf_sums_pass"] = timed(lambda: ops.od_snmf_sums(tiles.u8, W0, 0.1, 0.15), a.warmup, a.reps)
+    times["snmf_fit_device_loop"] = timed(lambda: ops.od_snmf_fit(tiles.u8, W0, 0.1, a.snmf_iters, 0.15), a.warmup, a.reps)
+    times["snmf_fit_whole"] = timed(lambda: vnorm.fit(tiles), a.warmup, a.reps)
+    Wt = torch.from_numpy(W0).cuda()
+    times["snmf_torch_one_iteration"] = timed(lambda: torch_snmf_iteration(tiles.u8, Wt, 0.1, 0.15), a.warmup, a.reps)
+    vfit = vnorm.fit(tiles)
+
     moved = 2 * t * 3 * r * r
     res = {"tiles": t, "resolution": r, "fit_tiles": ft, "fit_resolution": fr, "affine_algorithmic_bytes": moved, "reps": a.reps,
            "library": os.path.basename(mil_amd.LIB_PATH), "fit_n_tissue": fit.n_tissue,
-           "affine_vs_torch_chain": {"largest_byte_difference": int(diff.max()), "share_differing": float((diff != 0).float().mean())}}
+           "affine_vs_torch_chain": {"largest_byte_difference": int(diff.max()), "share_differing": float((diff != 0).float().mean())},
+           "snmf_iters": a.snmf_iters, "snmf_last_move": vfit.last_move}
     for k, v in times.items():
         res[k] = {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
     tbps = moved / statistics.median(times["affine_launch_per_tile"]) / 1e9
